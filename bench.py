@@ -1,7 +1,9 @@
 #!/usr/bin/env python
 """bench.py -- OpenVLA-OFT LoRA fine-tune step throughput on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+  A plain run sets up, warms up, times the K steps and prints the line; --full adds the side measurements after the timed steps
+  (per-kernel roofline step, batch-1 inference leg, stock-eager baselines B1 / B3, CPU baseline).
   N > 1: one rank per GPU over RCCL.  Either the caller starts the ranks (`python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`:
   RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment) or, when WORLD_SIZE is unset, this process starts them itself as children
   (the same torch.distributed.run command on 127.0.0.1, before anything here touches the GPU), relays rank 0's JSON line and exits with their status.
@@ -254,6 +256,35 @@ def measured_traffic(tiny: bool):
                                      "traffic_shape_mnk": rec.get("shape"), "traffic_stale": rec.get("gemm_nt_sha16") != sha}
 
 
+DUMP_SAMPLE = 1 << 21   # sampled elements per array: parameters + gradients = 16 MB of float32
+
+
+def dump_outputs(out_dir: Path, stores, loss_sum, pred):
+    """--dump-outputs: what the last timed step handed its caller, as float32 .npy files: `loss_sum` and `pred` as returned by
+    train_step_fwd_bwd, and `params` / `grads`, the same fixed seeded sample (with replacement, DUMP_SAMPLE elements) of the trainable tensors
+    after the optimizer step and of their gradients, taken over the tensors concatenated in name order.  Same arguments, same inputs: two builds
+    can be compared file for file: on the default path every gradient of the step is accumulated in a fixed order, so two runs agree bit for
+    bit in pred, params and grads after any number of steps (loss_sum, float atomics over the rows, up to rounding).  The opt-in fused LoRA
+    backward (OVLA_LORA_BWD=1) still adds dB with float atomics over row splits and is not reproducible."""
+    import numpy as np
+
+    params = sorted((p for st in stores for p in st.params), key=lambda p: p.name)
+    total = sum(p.numel for p in params)
+    idx = torch.randint(total, (min(DUMP_SAMPLE, total),), generator=torch.Generator().manual_seed(0)).sort().values
+    offsets = torch.tensor([0] + [p.numel for p in params]).cumsum(0)
+    bounds = torch.searchsorted(idx, offsets).tolist()
+    picked = {"params": [], "grads": []}
+    for p, off, lo, hi in zip(params, offsets.tolist(), bounds, bounds[1:]):
+        if hi > lo:
+            sel = (idx[lo:hi] - off).to(p.data.device)
+            picked["params"].append(p.data.reshape(-1)[sel].float())
+            picked["grads"].append(p.grad.reshape(-1)[sel].float())
+    out = {"loss_sum": loss_sum, "pred": pred, **{k: torch.cat(v) for k, v in picked.items()}}
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, t in out.items():
+        np.save(out_dir / f"{name}.npy", t.detach().float().cpu().numpy())
+
+
 def self_launch(n: int) -> int:
     """`python bench.py --gpus N` without a launcher: start the N ranks as CHILD processes through torch.distributed.run (the command the
     driver would type: vla-scripts/finetune.py:212-224,796 run under torchrun the same way), on 127.0.0.1 with a free port.  This parent never
@@ -280,14 +311,20 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=8, help="per-GPU batch (reference recipe: 8, LIBERO.md:91-113)")
     ap.add_argument("--tiny", action="store_true", help="reduced-size model (plumbing check only; NOT a valid benchmark number)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-eager-baseline", action="store_true", help="skip the in-process stock PyTorch-ROCm eager legs (BASELINE.md B1 and B3)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps write what the last one computed to DIR/<name>.npy (float32; "
+                    "rank 0): loss_sum, pred, and a fixed seeded sample of the updated trainable tensors (params) and of their gradients (grads)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also run the side measurements: the per-kernel roofline step, "
+                    "the batch-1 inference leg and, on one GPU, the stock-eager and CPU baselines (each can be left out with the --no-* options)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-eager-baseline", action="store_true", help="--full: skip the in-process stock PyTorch-ROCm eager legs (BASELINE.md B1 and B3)")
     ap.add_argument("--baseline-steps", type=int, default=10, help="timed steps of the B1 eager leg (after 3 warm-up steps)")
-    ap.add_argument("--no-inference", action="store_true", help="skip the batch-1 inference leg (configs[1])")
+    ap.add_argument("--no-inference", action="store_true", help="--full: skip the batch-1 inference leg (configs[1])")
     ap.add_argument("--aloha", action="store_true", help="SURVEY.md 8(d) config 5 instead of the headline workload: ALOHA shapes (3 images, 25x14 "
                     "chunk, proprio 14, S=1159), FiLM + diffusion head, batch 4 -- a side measurement, not the BASELINE metric")
     ap.add_argument("--eager-baseline", action="store_true", help="time the stock PyTorch-ROCm eager step instead (BASELINE.md B1) and exit")
     args = ap.parse_args()
+    if args.eager_baseline and args.dump_outputs:
+        ap.error("--dump-outputs writes the engine's step; --eager-baseline times the stock-eager one instead")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))          # no HIP call has happened in this process; the ranks are fresh children
@@ -368,12 +405,12 @@ def main():
             ts = torch.randint(0, 50, (args.batch,), generator=gen)
             diffusion = dict(noise=noise, noisy_actions=sched.add_noise(batch["actions"].float().cpu(), noise, ts).to(torch.bfloat16),
                              timestep_emb=enc(ts.float()).to(torch.bfloat16))
-        loss_sum, count, _ = eng.train_step_fwd_bwd(batch, diffusion=diffusion)
+        loss_sum, count, pred = eng.train_step_fwd_bwd(batch, diffusion=diffusion)
         if reducer is not None:
             reducer.all_reduce()
         eng.adamw_step(lr=5e-4, grad_scale=1.0 / world)
         eng.refresh_derived()
-        return loss_sum
+        return loss_sum, pred
 
     def barrier():
         if world > 1:
@@ -385,7 +422,7 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss_sum = step()
+        loss_sum, pred = step()
     barrier()
     elapsed = time.perf_counter() - t0
     if world > 1:
@@ -401,15 +438,18 @@ def main():
     value = world * args.batch * args.steps / elapsed
     final_loss = loss_sum.item() / (args.batch * cfg.chunk * cfg.action_dim)
     eng.head.check_fused_tail()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(Path(args.dump_outputs), eng.stores, loss_sum, pred)
 
     roofline = cpu = None
     # dominant kernel (gemm_nt) timed launch by launch with HIP events on the launch stream over one more step.  EVERY rank
     # runs the step (it contains the gradient collectives); only rank 0 records events.
-    if rank == 0:
-        ops.PROFILE = []
-    step()
-    torch.cuda.synchronize()
-    if rank == 0:
+    if args.full:
+        if rank == 0:
+            ops.PROFILE = []
+        step()
+        torch.cuda.synchronize()
+    if rank == 0 and args.full:
         fam = {}
         for family, e0, e1, fl in ops.PROFILE:
             d = fam.setdefault(family, [0, 0.0, 0.0])
@@ -450,11 +490,11 @@ def main():
     # engine: (1) adapters applied on the fly (the state during fine-tuning evaluation), (2) adapters merged into the base
     # weights as the reference deploys them (merge_lora_weights_and_save.py), (3) the merged forward replayed from a hipGraph.
     infer = None
-    if rank == 0 and not args.aloha:
+    if rank == 0 and args.full and not args.aloha:
         b1 = synth.make_batch(1, seed=77, num_images=cfg.num_images, chunk=cfg.chunk, action_dim=cfg.action_dim, proprio_dim=cfg.proprio_dim)
         b1["pixel_values"] = b1["pixel_values"].to(dev, torch.bfloat16)
         b1["proprio"] = b1["proprio"].to(dev, torch.bfloat16).reshape(1, -1)
-    if rank == 0 and not args.no_inference and not args.aloha:
+    if rank == 0 and args.full and not args.no_inference and not args.aloha:
 
         def infer_once():
             out = eng.forward(b1["input_ids"], b1["attention_mask"], b1["pixel_values"], b1["labels"], proprio=b1["proprio"], train=False,
@@ -523,7 +563,7 @@ def main():
     #   B1  stock PyTorch-ROCm eager fine-tune step (the denominator of north_star's ">= 1.5x" target), B3 stock eager batch-1 chunk,
     #   cpu_baseline  the CPU oracle on one full-size chunk (BASELINE.json configs[0] at full size)
     baselines = None
-    if rank == 0 and world == 1 and not args.tiny and not args.aloha and not (args.no_eager_baseline and args.no_cpu_baseline):
+    if rank == 0 and args.full and world == 1 and not args.tiny and not args.aloha and not (args.no_eager_baseline and args.no_cpu_baseline):
         graph = None
         torch.cuda.empty_cache()
         sd0 = weights_mod.random_state_dict(cfg, dev, seed=0, lm_head=True)      # the same seeded tensors the engine was built from

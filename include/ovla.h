@@ -132,8 +132,10 @@ int ovla_gemm_bf16(const ovla_gemm_args* a, void* stream);
  * "TN" GEMM (weight gradients)   C[P,Q] (+)= alpha * X[M,P]^T . Y[M,Q]     bf16 in, fp32 accumulate
  * Replaces autograd's weight-gradient matmuls for the trainable tensors: LoRA A/B (peft, finetune.py:862-871),
  * L1RegressionActionHead / ProprioProjector / NoisyActionProjector / FiLM Linears (finetune.py:894-932).
- * out_mode 0: fp32 atomicAdd into C (C must hold the running sum; the M range is split over workgroups)
- *          1: fp32 store    2: bf16 store   (modes 1/2: no M split)
+ * out_mode 0: fp32 accumulation into C (C must hold the running sum).  The M range is split over workgroups; with more than one split
+ *             each writes its partial product to the fp32 workspace W ([splits, P, Q], ovla_gemm_tn_workspace_floats) and a second
+ *             launch adds the partials to C in split order: the result is bit-reproducible run to run (no atomic order).
+ *          1: fp32 store    2: bf16 store   (modes 1/2: no M split, W unused)
  */
 typedef struct {
   const void* X; int64_t ldx;
@@ -142,7 +144,10 @@ typedef struct {
   int32_t M, P, Q;
   float alpha;
   int32_t out_mode;
+  float* W;
 } ovla_gemm_tn_args;
+/* fp32 elements of W the problem needs when launched alone (group_size 1) or as one of group_size problems of ovla_gemm_tn_grouped. */
+int64_t ovla_gemm_tn_workspace_floats(const ovla_gemm_tn_args* a, int32_t group_size);
 int ovla_gemm_tn_bf16(const ovla_gemm_tn_args* a, void* stream);
 /* Up to OVLA_TN_MAX_GROUP independent TN problems in ONE launch (the dA / dB_g products of one LoRA linear): the small
  * problems then overlap on the chip instead of running back to back. */

@@ -87,9 +87,8 @@ __global__ __launch_bounds__(256) void norm_fwd_kernel(const bf16_bits* __restri
 //   RMS: dx = rstd * (g - xhat * mean(g * xhat));   LN: dx = rstd * (g - mean(g) - xhat * mean(g * xhat))
 __global__ __launch_bounds__(256) void norm_bwd_kernel(const bf16_bits* __restrict__ x, const bf16_bits* __restrict__ dy,
                                                        const bf16_bits* __restrict__ w, const float* __restrict__ mean_in,
-                                                       const float* __restrict__ rstd_in, bf16_bits* __restrict__ dx,
-                                                       float* __restrict__ dw, float* __restrict__ db, int dim, int is_rms,
-                                                       int dx_accum) {
+                                                       const float* __restrict__ rstd_in, bf16_bits* __restrict__ dx, int dim,
+                                                       int is_rms, int dx_accum) {
   __shared__ float red[4];
   const int64_t row = blockIdx.x;
   const bf16_bits* xr = x + row * dim;
@@ -124,11 +123,27 @@ __global__ __launch_bounds__(256) void norm_bwd_kernel(const bf16_bits* __restri
       const float xhat = (f[j] - mean) * rstd;
       const float v = rstd * (g[j] * wf[j] - m1 - xhat * m2);
       o[j] = dx_accum ? o[j] + v : v;
-      if (dw) atomicAdd(dw + c * 8 + j, g[j] * xhat);
-      if (db) atomicAdd(db + c * 8 + j, g[j]);
     }
     store8(dxr + c * 8, o);
   }
+}
+
+// Norm weight / bias gradients: dw[c] += sum_r dy[r,c] * xhat[r,c], db[c] += sum_r dy[r,c], one thread per column walking the rows in order
+// (coalesced across the block's 256 columns): bit-reproducible, unlike per-row atomics.  ovla_norm_bwd runs it whenever dw or db is asked for.
+__global__ __launch_bounds__(256) void norm_dwdb_kernel(const bf16_bits* __restrict__ x, const bf16_bits* __restrict__ dy,
+                                                        const float* __restrict__ mean_in, const float* __restrict__ rstd_in,
+                                                        float* __restrict__ dw, float* __restrict__ db, int rows, int dim, int is_rms) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= dim) return;
+  float sw = 0.f, sb = 0.f;
+  for (int r = 0; r < rows; ++r) {
+    const float g = bf2f(dy[(int64_t)r * dim + c]);
+    const float xhat = (bf2f(x[(int64_t)r * dim + c]) - (is_rms ? 0.f : mean_in[r])) * rstd_in[r];
+    sw += g * xhat;
+    sb += g;
+  }
+  if (dw) dw[c] += sw;
+  if (db) db[c] += sb;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1180,9 +1195,14 @@ extern "C" int ovla_norm_bwd(const ovla_norm_bwd_args* a, void* stream_) {
   OVLA_REQUIRE(a->rows > 0 && a->dim > 0 && (a->dim % 8) == 0, "ovla_norm_bwd: rows=%d dim=%d", a->rows, a->dim);
   OVLA_REQUIRE(aligned16(a->x) && aligned16(a->dy) && aligned16(a->dx) && aligned16(a->weight), "ovla_norm_bwd: 16-byte alignment");
   hipLaunchKernelGGL(norm_bwd_kernel, dim3(a->rows), dim3(256), 0, stream, (const bf16_bits*)a->x, (const bf16_bits*)a->dy,
-                     (const bf16_bits*)a->weight, a->mean, a->rstd, (bf16_bits*)a->dx, a->dweight, a->dbias, a->dim, a->is_rms,
+                     (const bf16_bits*)a->weight, a->mean, a->rstd, (bf16_bits*)a->dx, a->dim, a->is_rms,
                      a->dx_accum);
   OVLA_CHECK_LAUNCH("ovla_norm_bwd");
+  if (a->dweight || a->dbias) {
+    hipLaunchKernelGGL(norm_dwdb_kernel, dim3(cdiv(a->dim, 256)), dim3(256), 0, stream, (const bf16_bits*)a->x, (const bf16_bits*)a->dy,
+                       a->mean, a->rstd, a->dweight, a->dbias, a->rows, a->dim, a->is_rms);
+    OVLA_CHECK_LAUNCH("ovla_norm_bwd");
+  }
   return OVLA_OK;
 }
 
@@ -1317,7 +1337,7 @@ extern "C" int ovla_copy_rows(const ovla_copy_rows_args* a, void* stream_) {
 extern "C" int ovla_film_bwd(const ovla_film_bwd_args* a, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   OVLA_REQUIRE(a && a->dy && a->x_pre && a->gamma && a->dgamma && a->dbeta && a->B > 0 && a->rows_per_batch > 0 && a->dim > 0, "ovla_film_bwd: bad arguments");
-  const int chunk = 32;
+  const int chunk = a->rows_per_batch;   // one row range per (batch, column): a single add per dgamma / dbeta element, bit-reproducible
   hipLaunchKernelGGL(film_bwd_kernel, dim3(cdiv(a->dim, 256), a->B, cdiv(a->rows_per_batch, chunk)), dim3(256), 0, stream, (bf16_bits*)a->dy,
                      (const bf16_bits*)a->x_pre, (const bf16_bits*)a->gamma, a->dgamma, a->dbeta, a->rows_per_batch, a->dim, chunk);
   OVLA_CHECK_LAUNCH("ovla_film_bwd");
@@ -1417,7 +1437,7 @@ extern "C" int ovla_transpose_batched(const ovla_transpose_args* table, const in
 extern "C" int ovla_colsum_bf16(const ovla_colsum_args* a, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   OVLA_REQUIRE(a && a->X && a->out && a->M > 0 && a->N > 0, "ovla_colsum_bf16: bad arguments");
-  const int rpb = 256;
+  const int rpb = a->M;   // one row range per column block: a single add per output element, bit-reproducible
   hipLaunchKernelGGL(colsum_kernel, dim3(cdiv(a->N, 64), cdiv(a->M, rpb)), dim3(256), 0, stream, (const bf16_bits*)a->X, a->ldx, a->out,
                      a->M, a->N, rpb);
   OVLA_CHECK_LAUNCH("ovla_colsum_bf16");

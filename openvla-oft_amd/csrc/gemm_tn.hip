@@ -7,7 +7,9 @@
 // LDS (coalesced 16-byte global loads, register-staged one tile ahead) and the MFMA fragments are fetched with
 // ds_read_b64_tr_b16, the gfx950 transposing LDS read.  mfma_f32_32x32x16_bf16 is used unswapped so that one accumulator
 // register is two 128-byte row segments of C: the shape global float atomics run at full rate with
-// (MI355X_MICROARCH.md "Global float atomics").  The M range is split over workgroups only in atomic mode.
+// (MI355X_MICROARCH.md "Global float atomics").  The M range is split over workgroups only in accumulate mode (out_mode 0); with more
+// than one split the partial products go to the fp32 workspace and gemm_tn_reduce_kernel adds them to C in split order, so the
+// weight gradients are bit-reproducible run to run (a float atomicAdd per split made them depend on the order the splits finished).
 #include "common.h"
 
 namespace {
@@ -19,7 +21,8 @@ struct TnParams {
   const bf16_bits *X, *Y;
   int64_t ldx, ldy, ldc;
   void* C;
-  int M, P, Q, tiles_p, tiles_q, m_chunk, out_mode;
+  float* W;   // [splits, P, Q] partial products (out_mode 0, splits > 1)
+  int M, P, Q, tiles_p, tiles_q, m_chunk, splits, out_mode;
   float alpha;
 };
 
@@ -127,8 +130,10 @@ OVLA_DEV void gemm_tn_body(const TnParams& p, bf16_bits* smem, int tile, int msp
         if (pp >= p.P) continue;
         const float v = acc[a][b][r] * p.alpha;
         const int64_t off = (int64_t)pp * p.ldc + qq;
-        if (p.out_mode == 0) atomicAdd(reinterpret_cast<float*>(p.C) + off, v);
-        else if (p.out_mode == 1) reinterpret_cast<float*>(p.C)[off] = v;
+        if (p.out_mode == 0) {
+          if (p.splits > 1) p.W[((int64_t)msplit * p.P + pp) * p.Q + qq] = v;
+          else atomicAdd(reinterpret_cast<float*>(p.C) + off, v);   // one writer per element: order-free
+        } else if (p.out_mode == 1) reinterpret_cast<float*>(p.C)[off] = v;
         else reinterpret_cast<bf16_bits*>(p.C)[off] = f2bf(v);
       }
     }
@@ -177,16 +182,75 @@ static int plan_tn(TnParams& p, int bp, int bq, int target_blocks) {
   }
   p.m_chunk = cdiv(cdiv(p.M, splits), BMK) * BMK;
   splits = cdiv(p.M, p.m_chunk);
+  p.splits = splits;
   return tiles * splits;
+}
+
+static void tn_tile(const TnParams& p, int& bp, int& bq) {
+  bp = p.P <= 32 ? 32 : 128;
+  bq = (p.P > 32 && p.Q <= 32) ? 32 : 128;
+}
+
+// C[p, q] += sum over s = 0 .. splits-1 of W[s, p, q], in that order: one thread per element of C, problems of one launch back to back.
+struct TnReduce {
+  float* C[OVLA_TN_MAX_GROUP];
+  const float* W[OVLA_TN_MAX_GROUP];
+  int64_t ldc[OVLA_TN_MAX_GROUP];
+  int P[OVLA_TN_MAX_GROUP], Q[OVLA_TN_MAX_GROUP], S[OVLA_TN_MAX_GROUP], blocks[OVLA_TN_MAX_GROUP];
+  int n;
+};
+
+__global__ __launch_bounds__(256) void gemm_tn_reduce_kernel(const TnReduce r) {
+  int b = blockIdx.x, i = 0;
+  while (i < r.n - 1 && b >= r.blocks[i]) {
+    b -= r.blocks[i];
+    ++i;
+  }
+  const int64_t pq = (int64_t)r.P[i] * r.Q[i];
+  const int64_t e = (int64_t)b * 256 + threadIdx.x;
+  if (e >= pq) return;
+  const float* w = r.W[i] + e;
+  float s = w[0];
+  for (int k = 1; k < r.S[i]; ++k) s += w[k * pq];
+  r.C[i][(e / r.Q[i]) * r.ldc[i] + e % r.Q[i]] += s;
+}
+
+// After the GEMM launch of `n` planned problems: the split-order reduction of every problem that was split (none: no launch).
+static int reduce_tn(const TnParams* probs, int n, hipStream_t stream, const char* who) {
+  TnReduce r;
+  r.n = 0;
+  int total = 0;
+  for (int i = 0; i < n; ++i) {
+    const TnParams& p = probs[i];
+    if (p.out_mode != 0 || p.splits <= 1) continue;
+    const int k = r.n++;
+    r.C[k] = reinterpret_cast<float*>(p.C); r.W[k] = p.W; r.ldc[k] = p.ldc;
+    r.P[k] = p.P; r.Q[k] = p.Q; r.S[k] = p.splits;
+    r.blocks[k] = (int)cdiv((int64_t)p.P * p.Q, 256);
+    total += r.blocks[k];
+  }
+  if (r.n == 0) return OVLA_OK;
+  hipLaunchKernelGGL(gemm_tn_reduce_kernel, dim3(total), dim3(256), 0, stream, r);
+  OVLA_CHECK_LAUNCH(who);
+  return OVLA_OK;
+}
+
+static int require_workspace(const TnParams& p, const char* who) {
+  if (p.out_mode == 0 && p.splits > 1 && !p.W) {
+    ovla_set_error("%s: %d M splits need the fp32 workspace W (ovla_gemm_tn_workspace_floats)", who, p.splits);
+    return OVLA_EINVAL;
+  }
+  return OVLA_OK;
 }
 
 template <int BP, int BQ, int WP, int WQ>
 int launch_tn(TnParams& p, hipStream_t stream) {
   const int blocks = plan_tn(p, BP, BQ, 768);
   const int tiles = p.tiles_p * p.tiles_q;
+  if (int rc = require_workspace(p, "ovla_gemm_tn_bf16")) return rc;
   hipLaunchKernelGGL((gemm_tn_kernel<BP, BQ, WP, WQ>), dim3(tiles, blocks / tiles), dim3(256), 0, stream, p);
   OVLA_CHECK_LAUNCH("ovla_gemm_tn_bf16");
-  return OVLA_OK;
+  return reduce_tn(&p, 1, stream, "ovla_gemm_tn_bf16");
 }
 
 int fill_params(const ovla_gemm_tn_args* a, TnParams& p, const char* who) {
@@ -197,11 +261,21 @@ int fill_params(const ovla_gemm_tn_args* a, TnParams& p, const char* who) {
   if (a->ldx < a->P || a->ldy < a->Q || a->ldc < a->Q) { ovla_set_error("%s: leading dimension smaller than extent", who); return OVLA_EINVAL; }
   if (a->out_mode < 0 || a->out_mode > 2) { ovla_set_error("%s: out_mode %d", who, a->out_mode); return OVLA_EINVAL; }
   p.X = (const bf16_bits*)a->X; p.Y = (const bf16_bits*)a->Y; p.C = a->C;
+  p.W = a->W;
   p.ldx = a->ldx; p.ldy = a->ldy; p.ldc = a->ldc; p.M = a->M; p.P = a->P; p.Q = a->Q; p.alpha = a->alpha; p.out_mode = a->out_mode;
   return OVLA_OK;
 }
 
 }  // namespace
+
+extern "C" int64_t ovla_gemm_tn_workspace_floats(const ovla_gemm_tn_args* a, int32_t group_size) {
+  TnParams p;
+  if (group_size < 1 || group_size > OVLA_TN_MAX_GROUP || fill_params(a, p, "ovla_gemm_tn_workspace_floats")) return -1;
+  int bp, bq;
+  tn_tile(p, bp, bq);
+  plan_tn(p, bp, bq, 768 / group_size);
+  return (p.out_mode == 0 && p.splits > 1) ? (int64_t)p.splits * p.P * p.Q : 0;
+}
 
 extern "C" int ovla_gemm_tn_bf16(const ovla_gemm_tn_args* a, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
@@ -224,9 +298,10 @@ extern "C" int ovla_gemm_tn_grouped(const ovla_gemm_tn_args* problems, int32_t n
     g.cfg[i] = p.P <= 32 ? 0 : (p.Q <= 32 ? 1 : 2);
     const int bp = g.cfg[i] == 0 ? 32 : 128, bq = g.cfg[i] == 1 ? 32 : 128;
     g.blocks[i] = plan_tn(g.prob[i], bp, bq, 768 / n);
+    if (int rc = require_workspace(g.prob[i], "ovla_gemm_tn_grouped")) return rc;
     total += g.blocks[i];
   }
   hipLaunchKernelGGL(gemm_tn_grouped_kernel, dim3(total), dim3(256), 0, stream, g);
   OVLA_CHECK_LAUNCH("ovla_gemm_tn_grouped");
-  return OVLA_OK;
+  return reduce_tn(g.prob, n, stream, "ovla_gemm_tn_grouped");
 }

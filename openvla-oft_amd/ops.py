@@ -170,7 +170,7 @@ def _gemm_family(g):
 
 
 def gemm_tn(x, y, *, out=None, alpha=1.0, accumulate=True, out_dtype=torch.float32):
-    """out[P,Q] (+)= alpha * x[M,P]^T @ y[M,Q].  accumulate=True: fp32 atomic accumulation into `out`."""
+    """out[P,Q] (+)= alpha * x[M,P]^T @ y[M,Q].  accumulate=True: fp32 accumulation into `out`, in a fixed order (bit-reproducible)."""
     _chk(x, name="x"); _chk(y, name="y")
     M, P = x.shape
     Q = y.shape[1]
@@ -186,10 +186,33 @@ def gemm_tn(x, y, *, out=None, alpha=1.0, accumulate=True, out_dtype=torch.float
         g.out_mode = 0
     else:
         g.out_mode = 1 if out.dtype == torch.float32 else 2
+    ws = _tn_workspace(g, 1, x.device)
     e0 = _prof_begin()
     _lib.call("ovla_gemm_tn_bf16", g, _stream())
     _prof_end(e0, "gemm_tn", 2.0 * M * P * Q)
     return out
+
+
+_TN_WS_FLOATS = {}
+
+
+def _tn_workspace(g, group_size, device):
+    """The fp32 split-partial workspace one TN problem needs (None when it is not split); sets g.W.  Allocated on the current stream, so the
+    caching allocator hands it to nothing else before the launch that uses it has run."""
+    import ctypes
+
+    key = (g.M, g.P, g.Q, g.out_mode, group_size)   # everything the split plan depends on
+    n = _TN_WS_FLOATS.get(key)
+    if n is None:
+        n = _lib.lib().ovla_gemm_tn_workspace_floats(ctypes.byref(g), group_size)
+        if n < 0:
+            raise _lib.OvlaError(f"ovla_gemm_tn_workspace_floats: invalid problem ({_lib.lib().ovla_last_error().decode()})")
+        _TN_WS_FLOATS[key] = n
+    if n == 0:
+        return None
+    ws = torch.empty(n, dtype=torch.float32, device=device)
+    g.W = ws.data_ptr()
+    return ws
 
 
 def gemm_tn_grouped(problems):
@@ -198,6 +221,7 @@ def gemm_tn_grouped(problems):
 
     n = len(problems)
     arr = (STRUCTS["ovla_gemm_tn_args"] * n)()
+    ws = []   # kept alive until the launch is enqueued
     flops = 0.0
     for i, (x, y, out) in enumerate(problems):
         _chk(x, name="x"); _chk(y, name="y")
@@ -207,6 +231,7 @@ def gemm_tn_grouped(problems):
         g = arr[i]
         g.X, g.ldx, g.Y, g.ldy, g.C, g.ldc = x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0), out.data_ptr(), out.stride(0)
         g.M, g.P, g.Q, g.alpha, g.out_mode = M, P, Q, 1.0, 0
+        ws.append(_tn_workspace(g, n, x.device))
         flops += 2.0 * M * P * Q
     e0 = _prof_begin()
     _lib.check(_lib.lib().ovla_gemm_tn_grouped(arr, n, _stream()), "ovla_gemm_tn_grouped")

@@ -260,3 +260,37 @@ def test_bench_starts_its_own_ranks_when_no_launcher_did(monkeypatch):
     with pytest.raises(SystemExit) as e:
         bench.main()
     assert "WORLD_SIZE=2" in str(e.value.code) and len(calls) == 1
+
+
+def test_bench_dump_outputs_is_a_fixed_sample_of_the_step(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: float32 .npy files of what the step returned plus the SAME seeded sample of every trainable tensor and of its
+    gradient, in name order across stores; two calls write identical files; the default sample stays far below 64 MB."""
+    bench = importlib.import_module("bench")
+    eng = load("openvla-oft_amd.engine")
+    assert 2 * bench.DUMP_SAMPLE * 4 <= 32 << 20
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 700)
+    numel = {"b.w": 1200, "a.w": 300, "c.w": 900}
+    stores = []
+    for names in (("b.w", "a.w"), ("c.w",)):
+        st = eng.ParamStore("cpu")
+        for n in names:   # value = 1e6 * (1 + rank of the name) + position: tells where each sampled element came from
+            st.add(n, 1e6 * (1 + sorted(numel).index(n)) + torch.arange(numel[n], dtype=torch.float32).reshape(-1, 3))
+        st.finalize()
+        for p in st.params:
+            p.grad.copy_(-p.data)
+        stores.append(st)
+    loss, pred = torch.tensor([2.5]), torch.linspace(-1, 1, 56, dtype=torch.bfloat16).reshape(8, 7)
+    bench.dump_outputs(tmp_path / "a", stores, loss, pred)
+    bench.dump_outputs(tmp_path / "b", stores, loss, pred)
+    out = {f.stem: np.load(f) for f in sorted((tmp_path / "a").glob("*.npy"))}
+    assert sorted(out) == ["grads", "loss_sum", "params", "pred"] and all(v.dtype == np.float32 for v in out.values())
+    for k, v in out.items():
+        assert np.array_equal(v, np.load(tmp_path / "b" / f"{k}.npy")), k
+    assert out["loss_sum"].tolist() == [2.5] and np.array_equal(out["pred"], pred.float().numpy())
+    vals = out["params"].astype(np.int64)
+    assert vals.shape == (700,) and np.array_equal(out["grads"], -out["params"])
+    which, pos = vals // 1_000_000 - 1, vals % 1_000_000
+    sizes = np.array([numel[n] for n in sorted(numel)])
+    assert ((0 <= which) & (which < 3)).all() and (pos < sizes[which]).all()
+    flat = np.concatenate([[0], np.cumsum(sizes)])[which] + pos   # index into the name-ordered concatenation: sorted
+    assert (np.diff(flat) >= 0).all() and len(np.unique(which)) == 3
