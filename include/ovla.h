@@ -128,6 +128,33 @@ int ovla_gemm_resolved_tile(const ovla_gemm_args* a, int32_t* tile);
 int64_t ovla_gemm_workspace_bytes(int32_t M, int32_t N, int32_t split_k);
 int ovla_gemm_bf16(const ovla_gemm_args* a, void* stream);
 
+/* Batch-invariant GEMM: ovla_gemm_bf16's kernels under a schedule the CALLER fixes, so that the bits of an output row depend on
+ * (N, K, K2, k2_group_n, epilogue) only -- never on M, on the row's tile or on how many rows share the launch.  Every output tile runs the
+ * same way: whole (splits = 1), or split `splits` ways along K with the fp32 partial slabs summed in slab order and the epilogue applied by
+ * the hybrid-remainder reduce (the same body as gemm_hybrid_reduce_kernel: no third arithmetic).  No hybrid full/remainder mix, no skinny or
+ * small-M special case.  Batched inference (ops.batch_invariant) runs every forward GEMM through it.
+ *   tile    1 (128x128), 2 (64x128), 5 (128x32), 17 (256x256), 18 (4-wave 256x256) or 22 (4-wave 128x256)
+ *   splits  1 .. 8; splits * 4 K tiles of 64 must fit in K (the K-extension is not split) */
+typedef struct {
+  int32_t tile;
+  int32_t splits;
+} ovla_gemm_schedule;
+/* Epilogue classes of ovla_gemm_fixed_schedule (bit flags): which tile configurations can run a problem. */
+enum { OVLA_EPI_ROPE = 1,     /* rope_cos / rope_sin */
+       OVLA_EPI_ROWSCALE = 2, /* rowscale_part (RMSNorm fold, consumer side) */
+       OVLA_EPI_SWIGLU = 4,   /* act = OVLA_ACT_SWIGLU */
+       OVLA_EPI_GENERAL = 8,  /* an activation, C_pre, colscale, FiLM, or a bias / residual operand not 16-byte aligned: 8-wave kernels only */
+       OVLA_EPI_ROWSQ = 16    /* rowsq_out (RMSNorm fold, producer side) */ };
+/* Host-only (no launch, no device query): the fixed schedule for a problem class, picked by the GEMM cost model over a ladder of row counts
+ * (8 ... 9728: action-head rows up to a 16-observation decoder batch) as the one with the smallest summed slowdown against the best uniform
+ * schedule at each row count.  The same (N, K, K2, k2_group_n, epi_flags) always gives the same schedule. */
+int ovla_gemm_fixed_schedule(int32_t N, int32_t K, int32_t K2, int32_t k2_group_n, int32_t epi_flags, ovla_gemm_schedule* out);
+/* fp32 workspace bytes ovla_gemm_bf16_fixed needs for M rows (0 when splits == 1): tiles * splits * tile_rows * tile_cols * 4. */
+int64_t ovla_gemm_fixed_workspace_bytes(int32_t M, int32_t N, const ovla_gemm_schedule* s);
+/* ovla_gemm_bf16 under schedule `s`.  `a->tile` and `a->split_k` must be 0 / <= 1, block-diagonal mode and the backward epilogues are not
+ * supported; `a->workspace` must hold ovla_gemm_fixed_workspace_bytes.  A schedule whose tile cannot run the epilogue is OVLA_EINVAL. */
+int ovla_gemm_bf16_fixed(const ovla_gemm_args* a, const ovla_gemm_schedule* s, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * "TN" GEMM (weight gradients)   C[P,Q] (+)= alpha * X[M,P]^T . Y[M,Q]     bf16 in, fp32 accumulate
  * Replaces autograd's weight-gradient matmuls for the trainable tensors: LoRA A/B (peft, finetune.py:862-871),

@@ -1863,6 +1863,16 @@ static int pick_tile(int M, int N, int T, int k2_group_n, int64_t ws_floats, Hyb
   return tile;
 }
 
+// ovla_gemm_bf16_fixed: the caller's schedule for the launch in progress (launch_cfg / launch_w4 read it instead of planning).
+static thread_local const ovla_gemm_schedule* g_fixed = nullptr;
+
+// The uniform schedule: every tile whole (splits 1) or every tile split the same number of ways -- the hybrid launch with no full tiles.
+static void apply_fixed(GemmParams& p, int tiles) {
+  p.full_tiles = tiles; p.rem_tiles = 0; p.rem_splits = 1;
+  if (g_fixed->splits > 1) { p.full_tiles = 0; p.rem_tiles = tiles; p.rem_splits = g_fixed->splits; }
+  p.hyb_cnt = nullptr;   // separate reduce launch
+}
+
 template <int BM, int BN, int WM, int WN>
 int launch_cfg(GemmParams& p, hipStream_t stream, int64_t ws_bytes = 0, bool hybrid = false) {
   p.tiles_m = cdiv(p.M, BM);
@@ -1895,6 +1905,7 @@ int launch_cfg(GemmParams& p, hipStream_t stream, int64_t ws_bytes = 0, bool hyb
     const HybridPlan pl = plan_hybrid(p.M, p.N, p.T1 + p.T2, tile_cfg(BM, BN), ws_bytes / 4);
     p.full_tiles = pl.full_tiles; p.rem_tiles = pl.rem_tiles; p.rem_splits = pl.rem_splits;
   }
+  if (g_fixed) apply_fixed(p, tiles);
   if (p.rem_tiles == 0 || p.rem_tiles > p.hyb_cnt_n) p.hyb_cnt = nullptr;    // no remainder, or more remainder tiles than counters: separate reduce launch
   const unsigned nblk = p.rem_tiles > 0 ? (unsigned)(p.full_tiles + p.rem_tiles * p.rem_splits) : (unsigned)(tiles * splits);
   hipLaunchKernelGGL(kern, dim3(nblk), dim3(64 * WM * WN), lds, stream, p);
@@ -1982,6 +1993,7 @@ int launch_w4(GemmParams& p, hipStream_t stream, int64_t ws_bytes, bool hybrid) 
     const HybridPlan pl = plan_hybrid(p.M, p.N, p.T1 + p.T2, WNW == 2 ? tile_cfg(256, 256) : cfg128, ws_bytes / 4);   // (256x256: same plan as the 8-wave config; the K-extension is not a K tile here)
     p.full_tiles = pl.full_tiles; p.rem_tiles = pl.rem_tiles; p.rem_splits = pl.rem_splits;
   }
+  if (g_fixed) apply_fixed(p, tiles);
   p.hyb_cnt = nullptr;
   const unsigned nblk = p.rem_tiles > 0 ? (unsigned)(p.full_tiles + p.rem_tiles * p.rem_splits) : (unsigned)(tiles * splits);
   hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds, stream, p);
@@ -2245,4 +2257,111 @@ extern "C" int ovla_gemm_bf16(const ovla_gemm_args* a, void* stream_) {
     case 105: return launch_cfg<128, 32, 4, 1>(p, stream, wsb, true);
     default: ovla_set_error("ovla_gemm_bf16: unknown tile id %d", tile); return OVLA_EINVAL;
   }
+}
+
+// ---- batch-invariant schedules (ovla.h: ovla_gemm_fixed_schedule / ovla_gemm_bf16_fixed) --------------------------------------------------
+namespace {
+struct FixedCand { int tile, BM, BN; bool w4; };
+const FixedCand kFixedCands[] = {{22, 128, 256, true}, {18, 256, 256, true}, {17, 256, 256, false}, {1, 128, 128, false}, {2, 64, 128, false}, {5, 128, 32, false}};
+const FixedCand* fixed_cand(int tile) {
+  for (const FixedCand& c : kFixedCands)
+    if (c.tile == tile) return &c;
+  return nullptr;
+}
+
+// Can tile configuration `c` run this problem class, split `splits` ways?  (The same rules ovla_gemm_bf16's launch paths enforce; splits keep
+// >= 4 K tiles per part, and a launch whose epilogue a configuration would run differently for other M -- RoPE fused or not on the 256x256
+// tile depends on M % 256 -- is not offered.)
+bool fixed_ok(const FixedCand& c, int N, int K, int K2, int k2_group_n, int flags, int splits) {
+  const int T1 = cdiv(K, BK);
+  if (splits < 1 || splits > 8 || (splits > 1 && splits * 4 > T1)) return false;
+  if (k2_group_n > 0 && k2_group_n % c.BN != 0) return false;
+  const bool rope = flags & OVLA_EPI_ROPE, rowscale = flags & OVLA_EPI_ROWSCALE, rowsq = flags & OVLA_EPI_ROWSQ, swiglu = flags & OVLA_EPI_SWIGLU;
+  if (c.w4) {
+    if ((flags & OVLA_EPI_GENERAL) || K % BK != 0 || T1 < 8) return false;   // (the hand-scheduled loop is measured and tested on long K only)
+    if (c.tile == 22) {
+      if (!(K2 == 0 || (K2 == 32 && !rope && !swiglu))) return false;
+      if ((rope || swiglu) && N % 256 != 0) return false;
+      if (rowscale && K > 4096) return false;
+      if (rope && rowsq) return false;
+      return true;
+    }
+    if (rowscale || rowsq) return false;   // tile 18
+    if (swiglu) return (K2 == 0 || K2 == 32) && N % 256 == 0;
+    return K2 == 0 || K2 == 32 || K2 == 64 || K2 == 96;
+  }
+  if (swiglu) return false;
+  if (rowscale || rowsq || rope) return c.tile == 1 && (!rope || N % 128 == 0);
+  return true;
+}
+
+// Uniform-schedule time from the planner's cost model (plan_hybrid), on the MI355X's 256 CUs: ceil(units / slots) rounds of tk K tiles each,
+// plus the slab traffic and the reduce launch when split.
+double fixed_est(int M, int N, int T, const FixedCand& fc, int splits) {
+  static const TileCfg cfg128 = {22, 128, 256, 1, 1.2e15, 5e-6, 0.0};
+  const TileCfg& c = fc.tile == 22 ? cfg128 : tile_cfg(fc.BM, fc.BN);
+  const int C = 256, slots = C * c.bpc;
+  const double tkc = 2.0 * c.BM * c.BN * BK / (c.rate / C);
+  auto round_time = [&](int units, int tk) { return tk * std::max(c.tk1, std::min(c.bpc, cdiv(units, C)) * tkc) + c.t0; };
+  const int units = cdiv(M, c.BM) * cdiv(N, c.BN) * splits, tk = cdiv(T, splits);
+  const int rounds = cdiv(units, slots);
+  double t = (rounds - 1) * round_time(slots, tk) + round_time(units - (rounds - 1) * slots, tk);
+  if (splits > 1) t += 1.0 * units * (4.0 * c.BM * c.BN) / 5e12 + 5e-6;
+  return t;
+}
+}  // namespace
+
+extern "C" int ovla_gemm_fixed_schedule(int32_t N, int32_t K, int32_t K2, int32_t k2_group_n, int32_t epi_flags, ovla_gemm_schedule* out) {
+  OVLA_REQUIRE(out != nullptr && N > 0 && K > 0 && K2 >= 0 && k2_group_n >= 0, "ovla_gemm_fixed_schedule: bad arguments");
+  static const int kSplits[] = {1, 2, 3, 4, 6, 8};
+  static const int kRows[] = {8, 64, 608, 1216, 2432, 4864, 9728};   // action-head rows ... a 16-observation decoder batch
+  const int T = cdiv(K, BK) + (K2 > 0 ? cdiv(K2, BK) : 0);
+  double best_at[sizeof(kRows) / sizeof(kRows[0])];
+  for (double& b : best_at) b = 1e30;
+  for (const FixedCand& c : kFixedCands)
+    for (int s : kSplits)
+      if (fixed_ok(c, N, K, K2, k2_group_n, epi_flags, s))
+        for (size_t i = 0; i < sizeof(kRows) / sizeof(kRows[0]); ++i) best_at[i] = std::min(best_at[i], fixed_est(kRows[i], N, T, c, s));
+  double best = 1e30;
+  out->tile = 0; out->splits = 0;
+  for (const FixedCand& c : kFixedCands)
+    for (int s : kSplits) {
+      if (!fixed_ok(c, N, K, K2, k2_group_n, epi_flags, s)) continue;
+      double score = 0.0;   // summed slowdown against the best uniform schedule at each row count
+      for (size_t i = 0; i < sizeof(kRows) / sizeof(kRows[0]); ++i) score += fixed_est(kRows[i], N, T, c, s) / best_at[i];
+      if (score < best - 1e-9) { best = score; out->tile = c.tile; out->splits = s; }
+    }
+  OVLA_REQUIRE(out->tile != 0, "ovla_gemm_fixed_schedule: no tile configuration runs N=%d K=%d K2=%d k2_group_n=%d epilogue flags %d", N, K, K2, k2_group_n, epi_flags);
+  return OVLA_OK;
+}
+
+extern "C" int64_t ovla_gemm_fixed_workspace_bytes(int32_t M, int32_t N, const ovla_gemm_schedule* s) {
+  const FixedCand* c = s ? fixed_cand(s->tile) : nullptr;
+  if (!c || s->splits <= 1 || M <= 0 || N <= 0) return 0;
+  return (int64_t)cdiv(M, c->BM) * cdiv(N, c->BN) * s->splits * c->BM * c->BN * 4;
+}
+
+extern "C" int ovla_gemm_bf16_fixed(const ovla_gemm_args* a, const ovla_gemm_schedule* s, void* stream) {
+  OVLA_REQUIRE(a != nullptr && s != nullptr, "ovla_gemm_bf16_fixed: null argument");
+  const FixedCand* c = fixed_cand(s->tile);
+  OVLA_REQUIRE(c != nullptr && s->splits >= 1 && s->splits <= 8, "ovla_gemm_bf16_fixed: tile %d / splits %d is not a fixed schedule (tile 1, 2, 5, 17, 18 or 22; splits 1 .. 8)",
+               s->tile, s->splits);
+  OVLA_REQUIRE(a->tile == 0 && a->split_k <= 1 && a->a_group_n == 0 && !a->dact_src,
+               "ovla_gemm_bf16_fixed: the schedule replaces tile / split_k; block-diagonal mode and the backward epilogues are not supported");
+  OVLA_REQUIRE(a->K > 0 && (s->splits == 1 || s->splits * 4 <= cdiv(a->K, BK)), "ovla_gemm_bf16_fixed: %d splits need K >= %d (K=%d)", s->splits, s->splits * 4 * BK, a->K);
+  if (c->w4) {
+    const bool fast_epi = !a->film_gamma && !a->C_pre && !a->colscale && (a->act == OVLA_ACT_NONE || a->act == OVLA_ACT_SWIGLU) &&
+                          (!a->residual || ((((uintptr_t)a->residual) & 15) == 0 && (a->ldr % 8) == 0)) && (!a->bias || (((uintptr_t)a->bias) & 15) == 0);
+    OVLA_REQUIRE(fast_epi, "ovla_gemm_bf16_fixed: the 4-wave configurations take alpha, 16-byte aligned bias / residual, RoPE, the RMSNorm fold and SwiGLU only");
+  }
+  if (a->rope_cos) OVLA_REQUIRE(s->tile == 1 || s->tile == 18 || s->tile == 22, "ovla_gemm_bf16_fixed: RoPE runs fused on tiles 1, 18 and 22 only");
+  if (s->splits > 1)
+    OVLA_REQUIRE(a->workspace && aligned16(a->workspace) && a->workspace_bytes >= ovla_gemm_fixed_workspace_bytes(a->M, a->N, s),
+                 "ovla_gemm_bf16_fixed: needs a 16-byte aligned workspace of %lld bytes", (long long)ovla_gemm_fixed_workspace_bytes(a->M, a->N, s));
+  ovla_gemm_args b = *a;
+  b.tile = s->tile; b.split_k = 1; b.hybrid_counters = nullptr; b.n_hybrid_counters = 0;
+  g_fixed = s;
+  const int rc = ovla_gemm_bf16(&b, stream);
+  g_fixed = nullptr;
+  return rc;
 }

@@ -558,6 +558,22 @@ class LlamaStack:
             self._fold_plan[M] = ok
         return ok
 
+    def _fold_fixed_ok(self) -> bool:
+        """Batch-invariant mode: the fold is usable when the fixed schedule of each folded projection's class exists -- a property of the
+        shapes, never of M (so M = B * S beyond 1024 keeps the fold)."""
+        ok = getattr(self, "_fold_fixed", None)
+        if ok is None:
+            D, F = self.cfg.llm_dim, self.cfg.llm_ff
+            ok = D % 512 == 0 and self.hd == 128
+            try:
+                for n, k, epi in ((3 * D, D, ops.EPI_ROPE | ops.EPI_ROWSCALE), (D, D, ops.EPI_ROWSQ), (D, F, ops.EPI_ROWSQ)):
+                    ok = ok and ops.gemm_fixed_schedule(n, k, epi=epi)[0] > 0
+                self._swiglu_fixed = ok and ops.gemm_fixed_schedule(2 * F, D, epi=ops.EPI_ROWSCALE | ops.EPI_SWIGLU)[0] > 0
+            except _lib.OvlaError:
+                ok, self._swiglu_fixed = False, False
+            self._fold_fixed = ok
+        return ok
+
     def _tables(self, S, device):
         if self.cos is None or self.cos.shape[0] < S:
             n = max(S, self.cfg.max_positions)
@@ -578,13 +594,16 @@ class LlamaStack:
         if sel is not None and (sel.numel() % 8 != 0 or sel.numel() == 0):
             raise ValueError("LlamaStack.fwd: the number of selected rows must be a positive multiple of 8")
         M = x.shape[0]
-        fold = (not train) and getattr(self, "folded", False) and _FOLD_RMSNORM and self._fold_ok(M)
+        invariant = ops.batch_invariant_enabled()
+        fold = (not train) and getattr(self, "folded", False) and _FOLD_RMSNORM and (self._fold_fixed_ok() if invariant else self._fold_ok(M))
         part = rbuf = None
         itile = 0
         if fold:   # sums of squares of the first layer's input rows; every later layer's come out of the down projection's epilogue
             part = ops.row_sumsq(x)
             rbuf = torch.empty(M, dtype=F32, device=x.device)
             itile = self._infer_tile(M)
+            if invariant:   # (ops.gemm ignores the tile in this mode; 122 only keeps the one-launch SwiGLU branch, chosen by shape alone)
+                itile = 122 if self._swiglu_fixed else 0
         for li, l in enumerate(self.layers):
             last_sel = sel is not None and li == len(self.layers) - 1
             if fold:   # RMSNorm + RoPE + q|k|v in ONE launch: rstd from `part`, folded weight, rotation in the epilogue
@@ -614,7 +633,7 @@ class LlamaStack:
             else:
                 x2, s_o = l["o"].fwd(o, residual=x)
             h2, _, r2 = ops.norm_fwd(x2, l["n2"], eps=cfg.rms_eps, rms=True, save_stats=train)
-            if _FUSE_SWIGLU_FWD and x2.shape[0] >= 256 and self._swiglu_pair_ok(l["gu"]):
+            if _FUSE_SWIGLU_FWD and x2.shape[0] >= 256 and not invariant and self._swiglu_pair_ok(l["gu"]):
                 # gate|up + SwiGLU in ONE launch (ovla.h OVLA_ACT_SWIGLU on the 4-wave 256x256 configuration): h comes out of the projection's read-back;
                 # the [M, 2F] projection output is still written (C_pre) when the backward needs it, but never read again in the forward
                 gu = torch.empty((x2.shape[0], 2 * F), dtype=BF16, device=x.device) if train else None
@@ -710,7 +729,7 @@ class ActionHead:
         split = 8 if rows <= 256 else 1      # small-M weight stream: split K over the chip
         x, s1 = self.fc1.fwd(h0, act=ops.ACT_RELU, c_pre=z1, split_k=split)
         D = cfg.llm_dim
-        if bool(_FUSE_HEAD) and rows <= 64 and D % 64 == 0 and D // 16 <= 256 and (D // 16) % 4 == 0 and \
+        if bool(_FUSE_HEAD) and rows <= 64 and not ops.batch_invariant_enabled() and D % 64 == 0 and D // 16 <= 256 and (D // 16) % 4 == 0 and \
                 _lib.lib().ovla_head_tail_resident_blocks() >= D // 16:      # software grid barriers: only when the whole grid is co-resident
             # everything after fc1 -- both MLPResNet blocks, LayerNorm 2, fc2 and the loss -- is ONE launch (ovla_head_tail_fwd), bit-identical
             # to the unfused sequence below; its backward is the unfused one, fed from the tensors the kernel saves
@@ -1105,7 +1124,7 @@ class VLAEngine:
         return ops.language_average(ids_dev, lab_dev, self.embed, avg)
 
     def forward(self, input_ids, attention_mask, pixel_values, labels, proprio=None, noisy_actions=None, timestep_emb=None, train=False,
-                proprio_projector=None, noisy_action_projector=None, cached_patches=None, sel=None):
+                proprio_projector=None, noisy_action_projector=None, cached_patches=None, sel=None, film_avg=None):
         """Multimodal forward (modeling_prismatic.py:571-643 without the discarded lm_head/CE in L1/diffusion mode).
         Returns dict(hidden [B,S,D], P, action_rows [B,A], patches, saved).  `cached_patches` (the `patches` of a previous
         call) skips the vision towers / projector / proprio projector: the DDIM sampler reuses them across its steps
@@ -1129,7 +1148,7 @@ class VLAEngine:
             lens_dev = packed_dev[2 * B * L:].to(torch.int32)
         return self.forward_dev(ids, lab, lens_dev, pixel_values, proprio=proprio, noisy_actions=noisy_actions,
                                 timestep_emb=timestep_emb, train=train, proprio_projector=proprio_projector,
-                                noisy_action_projector=noisy_action_projector, cached_patches=cached_patches, sel=sel)
+                                noisy_action_projector=noisy_action_projector, cached_patches=cached_patches, sel=sel, film_avg=film_avg)
 
     @staticmethod
     def check_right_padding(attention_mask) -> torch.Tensor:
@@ -1362,9 +1381,11 @@ class ChunkGraph:
     long as this object does.  Text length L is part of the captured shapes: callers pad the prompt to a bucket (right
     padding is masked exactly: padded keys contribute exact zeros) or keep one ChunkGraph per L."""
 
-    def __init__(self, engine: "VLAEngine", B: int, L: int, pixel_shape, *, head=None, use_proprio: bool = True, proprio_projector=None):
+    def __init__(self, engine: "VLAEngine", B: int, L: int, pixel_shape, *, head=None, use_proprio: bool = True, proprio_projector=None,
+                 invariant: bool = False):
         dev = engine.device
         self.engine, self.head, self.B, self.L = engine, head, B, L
+        self.invariant = invariant   # capture every GEMM under its fixed schedule (ops.batch_invariant): the batched inference API
         self.proprio_projector = proprio_projector
         self.ids = torch.zeros((B, L), dtype=torch.int64, device=dev)
         self.lab = torch.full((B, L), -100, dtype=torch.int64, device=dev)
@@ -1376,10 +1397,11 @@ class ChunkGraph:
 
     def _run(self):
         eng = self.engine
-        out = eng.forward_dev(self.ids, self.lab, self.lens, self.pixels, proprio=self.proprio, train=False,
-                              proprio_projector=self.proprio_projector, sel="actions")
-        ah, _ = eng.action_hidden(out)
-        pred = self.head.fwd(ah)[0] if self.head is not None else None
+        with ops.batch_invariant(self.invariant):
+            out = eng.forward_dev(self.ids, self.lab, self.lens, self.pixels, proprio=self.proprio, train=False,
+                                  proprio_projector=self.proprio_projector, sel="actions")
+            ah, _ = eng.action_hidden(out)
+            pred = self.head.fwd(ah)[0] if self.head is not None else None
         return pred, ah
 
     def load(self, input_ids, attention_mask, pixel_values, labels, proprio=None):

@@ -210,3 +210,59 @@ def get_vla_action(cfg: Any, vla, processor: Any, obs: Dict[str, Any], task_labe
                                            proprio_projector=proprio_projector, noisy_action_projector=noisy_action_projector,
                                            action_head=action_head, use_film=use_film)
     return [action[i] for i in range(min(len(action), cfg.num_open_loop_steps))]
+
+
+def device_pixel_values_batch(per_obs: List[List[np.ndarray]], cfg: Any) -> torch.Tensor:
+    """device_pixel_values of B observations' images (I each) in one pass: all B * I frames go through the device preprocessing together
+    (one launch per stage) -> bf16 [B, 6 * I, 224, 224], row b equal to device_pixel_values(per_obs[b], cfg)[0]."""
+    if len({len(images) for images in per_obs}) != 1:
+        raise ValueError("device_pixel_values_batch: every observation must carry the same number of images")
+    pv = device_pixel_values([im for images in per_obs for im in images], cfg)   # [1, 6 * B * I, H, W]: image k's channels at [6 k, 6 k + 6)
+    return pv.view(len(per_obs), -1, *pv.shape[2:])
+
+
+def get_vla_action_batch(cfg: Any, vla, processor: Any, observations: List[Dict[str, Any]], task_labels: List[str], action_head=None,
+                         proprio_projector=None, noisy_action_projector=None, use_film: bool = False, noise=None) -> List[List[np.ndarray]]:
+    """get_vla_action for B observations in one batched forward (OpenVLAForActionPrediction.predict_action_batch): per observation the same
+    semantics -- including the in-place normalisation of obs["state"] -- and one list of num_open_loop_steps actions per observation.  On the
+    device image path all B * I frames go through device_pixel_values together (one launch per stage)."""
+    if len(observations) != len(task_labels):
+        raise ValueError(f"get_vla_action_batch: {len(observations)} observations but {len(task_labels)} task labels")
+    if not observations:
+        raise ValueError("get_vla_action_batch: no observations")
+    with torch.inference_mode():
+        per_obs = []
+        for obs in observations:
+            images = [obs["full_image"]]
+            if cfg.num_images_in_input > 1:
+                images.extend([obs[k] for k in obs.keys() if "wrist" in k or "camera_gripper_image" in k])
+            per_obs.append(images)
+        if len({len(im) for im in per_obs}) != 1:
+            raise ValueError("get_vla_action_batch: every observation must carry the same number of images")
+        prompts = [f"In: What action should the robot take to {label.lower()}?\nOut:" for label in task_labels]
+        if (isinstance(processor, PrismaticProcessor) and processor.device_image_prep and torch.cuda.is_available()
+                and vla.config.image_sizes[0] == image_prep.OPENVLA_IMAGE_SIZE):
+            toks = [processor.tokenize(p) for p in prompts]
+            pixel_values = device_pixel_values_batch(per_obs, cfg)
+        else:
+            toks, pvs = [], []
+            for p, images in zip(prompts, per_obs):
+                images = prepare_images_for_vla(list(images), cfg)
+                inputs = processor(p, images.pop(0))
+                if images:
+                    inputs["pixel_values"] = torch.cat([inputs["pixel_values"]] + [processor(p, im)["pixel_values"] for im in images], dim=1)
+                toks.append(inputs)
+                pvs.append(inputs["pixel_values"])
+            pixel_values = torch.cat(pvs, dim=0)
+        batch = [(t["input_ids"], t.get("attention_mask")) for t in toks]
+        proprio = None
+        if cfg.use_proprio:
+            for obs in observations:
+                obs["state"] = normalize_proprio(obs["state"], vla.norm_stats[cfg.unnorm_key]["proprio"])
+            proprio = np.stack([np.asarray(obs["state"]) for obs in observations])
+        if action_head is None:
+            actions, _ = vla.predict_action_batch(batch, pixel_values, unnorm_key=cfg.unnorm_key)
+        else:
+            actions, _ = vla.predict_action_batch(batch, pixel_values, unnorm_key=cfg.unnorm_key, proprio=proprio, proprio_projector=proprio_projector,
+                                                  noisy_action_projector=noisy_action_projector, action_head=action_head, use_film=use_film, noise=noise)
+    return [[a[i] for i in range(min(len(a), cfg.num_open_loop_steps))] for a in actions]

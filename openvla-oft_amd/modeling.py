@@ -386,6 +386,7 @@ class OpenVLAForActionPrediction(_StoreModule):
         # buffers it was captured with, so it is for deployment (weights frozen), not for evaluation inside a training loop.
         self.use_graph = os.environ.get("OVLA_INFER_GRAPH", "0") == "1"
         self._graphs: Dict[tuple, ChunkGraph] = {}
+        self.max_batch_graphs = 8   # predict_action_batch: captured graphs kept per (B, bucket, ...), least recently used evicted first
 
     def merge_and_unload(self):
         """peft `merge_and_unload()` of merge_lora_weights_and_save.py:60-67 on device: W += (alpha/r) B A for every adapted
@@ -518,6 +519,110 @@ class OpenVLAForActionPrediction(_StoreModule):
             d = np.clip(self.vocab_size - tok - 1, a_min=0, a_max=self.bin_centers.shape[0] - 1)
             normalized = self.bin_centers[d].reshape(cfg.chunk, cfg.action_dim)
         return self._unnormalize_actions(normalized, unnorm_key), actions_hidden_states
+
+    # -- batched inference (not in the reference: its predict_action asserts batch size 1) -----------------------------------------------
+    @torch.no_grad()
+    def predict_action_batch(self, prompts, pixel_values, unnorm_key=None, proprio=None, proprio_projector=None, action_head=None,
+                             noisy_action_projector=None, use_film: bool = False, noise=None):
+        """predict_action for B observations in one forward.  prompts: list of B (input_ids, attention_mask) pairs ([1, L_b] or [L_b], lengths may
+        differ; masks right-padded), pixel_values [B, 6 I, H, W], proprio [B, proprio_dim], noise [B, chunk, action_dim] (diffusion: each sample's
+        DDIM trajectory starts from its own noise).  Returns (actions [B, chunk, action_dim] unnormalised with `unnorm_key`, action hidden states
+        [B, A, D]).  Every GEMM runs under its fixed schedule (ops.batch_invariant), so each observation's outputs are the same bits whatever else
+        is in the batch and in whatever order (OVLA_BATCH_INVARIANT=0: the planner's schedules, for A/B measurement only)."""
+        cfg = self.cfg
+        if use_film != self.engine.use_film:
+            raise ValueError(f"use_film={use_film} but the model was built with use_film={self.engine.use_film}")
+        B, A, D = len(prompts), cfg.num_action_tokens, cfg.llm_dim
+        if B == 0:
+            raise ValueError("predict_action_batch: no observations")
+        if pixel_values.shape[0] != B:
+            raise ValueError(f"predict_action_batch: {B} prompts but pixel_values holds {pixel_values.shape[0]} observations")
+        use_proprio = proprio_projector is not None and proprio is not None
+        prop = None
+        if use_proprio:
+            prop = torch.as_tensor(np.asarray(proprio), dtype=torch.float32)
+            if prop.ndim != 2 or prop.shape[0] != B:
+                raise ValueError(f"predict_action_batch: proprio must be [{B}, proprio_dim], got {tuple(prop.shape)}")
+        use_diffusion = noisy_action_projector is not None and hasattr(action_head, "noise_scheduler")
+        rows = []   # per sample: prompt (+ 29871) + A action slots + stop, as predict_action builds it (:974-993)
+        for ids, mask in prompts:
+            ids = torch.as_tensor(ids).to("cpu", torch.int64).reshape(-1)
+            mask = torch.ones_like(ids, dtype=torch.bool) if mask is None else torch.as_tensor(mask).to("cpu").reshape(-1).bool()
+            if mask.shape != ids.shape:
+                raise ValueError("predict_action_batch: input_ids and attention_mask lengths differ")
+            n = int(self.engine.check_right_padding(mask[None])[0])
+            ids = ids[:n]
+            if n == 0 or int(ids[-1]) != 29871:
+                ids = torch.cat([ids, torch.tensor([29871], dtype=torch.int64)])
+            rows.append(torch.cat([ids, torch.ones(A, dtype=torch.int64), torch.tensor([STOP_INDEX], dtype=torch.int64)]))
+        # right-pad to a bucket (a multiple of 8; at least 65 - P so that every composition takes the same attention variant, S > 64)
+        P = self.engine.num_patches_total(pixel_values.shape[1] // 6, use_proprio, use_diffusion)
+        Lb = max(max(len(r) for r in rows), 65 - P)
+        Lb = (Lb + 7) // 8 * 8
+        ids = torch.full((B, Lb), cfg.pad_token_id, dtype=torch.int64)
+        mask = torch.zeros((B, Lb), dtype=torch.bool)
+        labels = torch.full((B, Lb), IGNORE_INDEX, dtype=torch.int64)
+        for b, r in enumerate(rows):
+            ids[b, : len(r)], mask[b, : len(r)] = r, True
+            labels[b, len(r) - A - 1: len(r)] = ACTION_TOKEN_BEGIN_IDX + 1
+            labels[b, len(r) - 1] = STOP_INDEX
+        film_avg = None
+        if self.engine.use_film:   # FiLM's language average over each prompt's OWN tokens (padding would enter the mean: film_vit_wrapper.py:243)
+            film_avg = torch.zeros(((B + 7) // 8 * 8, D), dtype=BF16, device=self.device)
+            for b, r in enumerate(rows):
+                rid = r[None].to(self.device)
+                rlab = labels[b: b + 1, : len(r)].to(self.device)
+                ops.language_average(rid, rlab, self.engine.embed, film_avg[b: b + 1])
+        pp_comp = proprio_projector.comp if use_proprio else None
+        with ops.batch_invariant(ops.BATCH_INVARIANT_DEFAULT):
+            if use_diffusion:                                                                 # :793-877, per sample
+                sched = action_head.noise_scheduler
+                sched.set_timesteps(action_head.num_diffusion_steps)
+                if noise is None:
+                    noise = torch.randn((B, cfg.chunk, cfg.action_dim))
+                cur = torch.as_tensor(noise).to("cpu", torch.float32).reshape(B, cfg.chunk, cfg.action_dim).to(BF16).float()
+                cached, ah = None, None
+                for t in sched.timesteps:
+                    temb = action_head.time_encoder(torch.tensor([float(t)])).to(BF16).reshape(1, D).expand(B, D)
+                    out = self.engine.forward(ids, mask, pixel_values, labels, proprio=prop, train=False, noisy_actions=cur.to(BF16),
+                                              timestep_emb=temb, proprio_projector=pp_comp, noisy_action_projector=noisy_action_projector.comp,
+                                              cached_patches=cached, sel="actions", film_avg=film_avg)
+                    cached = out["patches"]
+                    ah, _ = self.engine.action_hidden(out)
+                    eps = action_head.predict_noise(ah.view(B, A, D)).reshape(cur.shape).float().cpu()
+                    cur = sched.step(eps, int(t), cur).prev_sample.to(BF16).float()
+                normalized = cur.numpy()
+                hidden = ah.view(B, A, D).clone()
+            else:
+                head_comp = getattr(action_head, "comp", None) if action_head is not None else None
+                if self.use_graph and film_avg is None:
+                    key = ("batch", B, Lb, tuple(pixel_values.shape), id(head_comp), id(pp_comp), ops.BATCH_INVARIANT_DEFAULT)
+                    g = self._graphs.pop(key, None)
+                    if g is None:
+                        batched = [k for k in self._graphs if k[0] == "batch"]
+                        if len(batched) >= self.max_batch_graphs:   # B and the bucket come from callers (/act_batch): keep the most recent few
+                            del self._graphs[batched[0]]
+                        g = ChunkGraph(self.engine, B, Lb, pixel_values.shape, head=head_comp, use_proprio=use_proprio, proprio_projector=pp_comp,
+                                       invariant=ops.BATCH_INVARIANT_DEFAULT)
+                        g._keep = (head_comp, pp_comp)
+                    self._graphs[key] = g   # (re)inserted last: dict order is least recently used first
+                    pred, ah = g(ids, mask, pixel_values, labels, prop)
+                    hidden = ah.view(B, A, D).clone()
+                    pred = pred.clone() if pred is not None else None
+                else:
+                    out = self.engine.forward(ids, mask, pixel_values, labels, proprio=prop, train=False, proprio_projector=pp_comp,
+                                              sel="actions", film_avg=film_avg)
+                    ah, _ = self.engine.action_hidden(out)
+                    hidden = ah.view(B, A, D).clone()
+                    pred = action_head.predict_action(hidden) if action_head is not None else None
+                if action_head is not None:
+                    normalized = pred.reshape(B, cfg.chunk, cfg.action_dim).float().cpu().numpy()
+                else:
+                    tok = self.logits_for(hidden.view(B * A, D)).argmax(dim=1).cpu().numpy()
+                    d = np.clip(self.vocab_size - tok - 1, a_min=0, a_max=self.bin_centers.shape[0] - 1)
+                    normalized = self.bin_centers[d].reshape(B, cfg.chunk, cfg.action_dim)
+        actions = np.stack([self._unnormalize_actions(normalized[b], unnorm_key) for b in range(B)])
+        return actions, hidden
 
     # -- statistics (:772-791, :1062-1087) -------------------------------------------------------------------------------
     @staticmethod

@@ -4,6 +4,10 @@ module falls back to torch math: a missing library or a failed launch raises.
 """
 from __future__ import annotations
 
+import contextlib
+import ctypes
+import threading
+
 import torch
 
 from . import _lib
@@ -146,6 +150,19 @@ def gemm(a, b, *, out=None, bias=None, act=ACT_NONE, residual=None, colscale=Non
         parts, eps, rbuf = rowscale
         assert parts.dtype == torch.float32 and parts.shape == (M, K // 64) and parts.is_contiguous() and rbuf.dtype == torch.float32 and rbuf.numel() >= M
         g.rowscale_part, g.rowscale_slots, g.rowscale_eps, g.rowscale_r = parts.data_ptr(), K // 64, eps, rbuf.data_ptr()
+    if getattr(_mode, "invariant", False) and dact is None and not a_group_n:   # batch-invariant mode: the caller's tile / split_k give way to the fixed schedule
+        g.M, g.N, g.K, g.act, g.split_k, g.tile, g.alpha = M, N, K, act, 0, 0, alpha
+        general = (act not in (ACT_NONE, ACT_SWIGLU) or c_pre is not None or colscale is not None or film is not None
+                   or (bias is not None and bias.data_ptr() % 16) or (residual is not None and (residual.data_ptr() % 16 or residual.stride(0) % 8)))
+        epi = ((EPI_ROPE if rope is not None else 0) | (EPI_ROWSCALE if rowscale is not None else 0) | (EPI_ROWSQ if rowsq_out is not None else 0)
+               | (EPI_SWIGLU if act == ACT_SWIGLU else 0) | (EPI_GENERAL if general else 0))
+        sched = _fixed_schedule_struct(N, K, g.K2, g.k2_group_n, epi)
+        ws = _workspace(a.device, max(gemm_fixed_workspace_bytes(M, N, sched), _WS_BYTES))
+        g.workspace, g.workspace_bytes = ws.data_ptr(), ws.numel() * 4
+        e0 = _prof_begin()
+        _lib.check(_lib.lib().ovla_gemm_bf16_fixed(ctypes.byref(g), ctypes.byref(sched), _stream()), "ovla_gemm_bf16_fixed")
+        _prof_end(e0, f"gemm_fixed_t{sched.tile}s{sched.splits}", 2.0 * M * N * (K + g.K2))
+        return out
     g.M, g.N, g.K, g.act, g.split_k, g.tile, g.alpha, g.a_group_n = M, N, K, act, split_k, tile, alpha, a_group_n
     ws = _workspace(a.device, max(4 * split_k * M * N if split_k > 1 else 0, _WS_BYTES))
     g.workspace, g.workspace_bytes = ws.data_ptr(), ws.numel() * 4
@@ -257,6 +274,55 @@ def gemm_plan(M, N, K, K2=0, k2_group_n=0, workspace_bytes=_WS_BYTES):
     _lib.check(_lib.lib().ovla_gemm_plan(M, N, K, K2, k2_group_n, ctypes.c_int64(workspace_bytes), ctypes.byref(t), ctypes.byref(f), ctypes.byref(r),
                                          ctypes.byref(sp), ctypes.byref(est)), "ovla_gemm_plan")
     return t.value, f.value, r.value, sp.value, est.value
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Batch-invariant mode (ovla.h: ovla_gemm_bf16_fixed).  Inside `with batch_invariant():` every forward GEMM runs under the fixed schedule of its
+# (N, K, K2, k2_group_n, epilogue) class instead of the planner's M-dependent one, so an output row's bits do not depend on how many rows share
+# the launch: the batched inference API (predict_action_batch) gives each observation the same actions whatever else is in the batch.
+# OVLA_BATCH_INVARIANT=0 leaves the batched API on the planner's schedules (A/B measurement only: results then depend on the batch).
+EPI_ROPE, EPI_ROWSCALE, EPI_SWIGLU, EPI_GENERAL, EPI_ROWSQ = 1, 2, 4, 8, 16
+BATCH_INVARIANT_DEFAULT = _os.environ.get("OVLA_BATCH_INVARIANT", "1") != "0"
+_mode = threading.local()   # per thread, like the library's own schedule pointer: another thread's GEMMs keep the planner
+_fixed_cache = {}
+
+
+@contextlib.contextmanager
+def batch_invariant(on: bool = True):
+    prev = getattr(_mode, "invariant", False)
+    _mode.invariant = bool(on)
+    try:
+        yield
+    finally:
+        _mode.invariant = prev
+
+
+def batch_invariant_enabled() -> bool:
+    return getattr(_mode, "invariant", False)
+
+
+def _fixed_schedule_struct(N, K, K2=0, k2_group_n=0, epi=0):
+    key = (N, K, K2, k2_group_n, epi)
+    s = _fixed_cache.get(key)
+    if s is None:
+        s = STRUCTS["ovla_gemm_schedule"]()
+        _lib.check(_lib.lib().ovla_gemm_fixed_schedule(N, K, K2, k2_group_n, epi, ctypes.byref(s)), "ovla_gemm_fixed_schedule")
+        _fixed_cache[key] = s
+    return s
+
+
+def gemm_fixed_schedule(N, K, K2=0, k2_group_n=0, epi=0):
+    """The fixed schedule (tile id, splits) of a problem class (ovla_gemm_fixed_schedule, host only; independent of M by construction)."""
+    s = _fixed_schedule_struct(N, K, K2, k2_group_n, epi)
+    return s.tile, s.splits
+
+
+def gemm_fixed_workspace_bytes(M, N, sched):
+    if isinstance(sched, tuple):
+        s = STRUCTS["ovla_gemm_schedule"]()
+        s.tile, s.splits = sched
+        sched = s
+    return int(_lib.lib().ovla_gemm_fixed_workspace_bytes(M, N, ctypes.byref(sched)))
 
 
 def lora_bwd(dy, Bt, t, dB_grad, *, gn, G, scale, dt=None):

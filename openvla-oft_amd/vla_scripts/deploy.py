@@ -20,7 +20,7 @@ import threading
 import traceback
 from dataclasses import dataclass
 from pathlib import Path
-from typing import Any, Dict, Optional, Union
+from typing import Any, Dict, List, Optional, Union
 
 import numpy as np
 
@@ -121,6 +121,24 @@ class OpenVLAServer:
                             "{'observation': dict, 'instruction': str}\\n")
             return "error"
 
+    def act_batch(self, payloads):
+        """The body of `/act_batch`: a list of `/act` payloads -> the list of their action chunks, each encoded like `/act` answers it, from ONE
+        batched forward (OpenVLAForActionPrediction.predict_action_batch); "error" if the request or any element of it is malformed."""
+        try:
+            if not isinstance(payloads, list) or not payloads:
+                raise ValueError("/act_batch takes a non-empty list of observation payloads")
+            decoded = [decode_payload(p) for p in payloads]
+            observations = [o for o, _ in decoded]
+            instructions = [o["instruction"] for o in observations]
+            with self._lock:
+                actions = U.get_vla_action_batch(self.cfg, self.vla, self.processor, observations, instructions, action_head=self.action_head,
+                                                 proprio_projector=self.proprio_projector, use_film=self.cfg.use_film)
+            return [json.dumps(_encode(a)) if double else _encode(a) for a, (_, double) in zip(actions, decoded)]
+        except Exception:  # noqa: BLE001 -- like /act
+            logging.error(traceback.format_exc())
+            logging.warning("Your request threw an error; make sure your request is a list of {'observation': dict, 'instruction': str}\n")
+            return "error"
+
     def build_app(self):
         from fastapi import FastAPI
         from fastapi.responses import JSONResponse
@@ -130,6 +148,10 @@ class OpenVLAServer:
         @app.post("/act")
         def get_server_action(payload: Dict[str, Any]):
             return JSONResponse(self.act(payload))
+
+        @app.post("/act_batch")
+        def get_server_action_batch(payloads: List[Dict[str, Any]]):
+            return JSONResponse(self.act_batch(payloads))
 
         self.app = app
         return app
