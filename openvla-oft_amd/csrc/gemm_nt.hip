@@ -1799,48 +1799,108 @@ static int num_cus() {
   return g_num_cus;
 }
 
+// ---- tile configurations -------------------------------------------------------------------------------------------------------------------
+// Everything the host half knows about a tile configuration is ONE row of kTiles (below the launchers it points to): the planner, the
+// launch-time checks, the fixed-schedule query and the dispatch all read it.  DESIGN.md "GEMM tile ids" is the same table in prose.
+enum Family { FAM_W8, FAM_PIPE, FAM_W4, FAM_SKINNY };   // gemm_nt_kernel | gemm_nt_pipe_kernel | gemm_nt_w4_kernel | gemm_skinny_kernel
+// When the RoPE epilogue is fused (rope_fused); every other case computes the plain projection and rotates it with one ovla_rope launch (same arithmetic).
+enum RopeFuse {
+  ROPE_UNFUSED,
+  ROPE_WAVE_SLAB,   // 256x256, 4x2 waves: one wave slab is one head, the epilogue runs in-kernel or in the hybrid reduce
+  ROPE_INTERIOR,    // 256x256, 2x4 waves: every q | k tile an interior tile whose waves take the columns together with their rotation partners
+                    // (gemm_nt_kernel: rope_tile): M, N and rope_cols multiples of 256
+  ROPE_HEAD_TILE,   // one head per column tile / wave slab, any M (edge rows are skipped in the read-back): N a multiple of 128
+  ROPE_COLMAP,      // 128x256 4-wave: two heads per column tile, the RoPE column map; N a multiple of 256, no K-extension
+};
+enum : unsigned {
+  CFG_PLUS100 = 2,   // id + 100 is accepted: the same configuration with the hybrid schedule forced
+  CFG_BDIAG = 8,     // runs block-diagonal mode (a_group_n > 0)
+  CFG_FOLD = 16,     // runs the RMSNorm fold, producer (rowsq_out) and consumer (rowscale_part) side
+  CFG_SWIGLU = 32,   // runs act = OVLA_ACT_SWIGLU (the SwiGLU pair map)
+};
+constexpr int KEXT_ANY = -1;   // K-extension limits: 32-column steps up to this many columns; KEXT_ANY any K2 (the 8-wave kernels zero-fill K tails)
+
 // Hybrid schedule of one tile config: whole rounds of the chip as full tiles, the partial last round split along K.
 // ONE cost model (seconds) picks the split and, in auto mode, the tile config itself.  Per config (calibrated on MI355X with
 // tools/gemm_sweep.py, gemm_m608.py, gemm_small_m.py): `rate` = sustained in-loop FLOP/s with every CU saturated, `t0` = fixed
 // per-workgroup cost (prologue latency + epilogue), `tk1` = time per K tile of a workgroup that has its CU to itself (its own
 // latency chain: a lone 4-wave 128x128 workgroup needs 0.86 us per K tile, two sharing a CU 0.95 us for both).  A round with u
 // units on C CUs puts w = min(bpc, ceil(u / C)) workgroups on a CU and takes  Tk * max(tk1, w * tkc) + t0.
-struct TileCfg { int id, BM, BN, bpc; double rate, t0, tk1; };
-static const TileCfg kTileCfgs[] = {
-    {17, 256, 256, 1, 1.30e15, 7e-6, 0.0},
-    {1, 128, 128, 2, 1.13e15, 4e-6, 0.86e-6},
-    {2, 64, 128, 3, 0.90e15, 3e-6, 0.57e-6},
-    {5, 128, 32, 4, 0.60e15, 3e-6, 0.53e-6},
+struct Cost { int bpc; double rate, t0, tk1; };
+constexpr Cost kCost256x256 = {1, 1.30e15, 7e-6, 0.0};   // every configuration of the 256x256 tile (the 4-wave one: same plan as the 8-wave one; the K-extension is not a K tile there)
+constexpr Cost kCostGeneric = {1, 0.9e15, 5e-6, 0.0};    // experimental configs: no hybrid tuning
+
+struct TileCfg;
+struct LaunchCtx { const TileCfg* cfg; hipStream_t stream; int64_t ws_bytes; bool hybrid; const ovla_gemm_schedule* fixed; };
+struct TileCfg {
+  int id, BM, BN;
+  Family fam;
+  Cost cost;
+  int auto_rank;    // > 0: `tile = 0` may pick the row by the cost model, tried in this order (pick_tile); the earlier rank wins a tie
+  int fixed_rank;   // > 0: candidate of ovla_gemm_fixed_schedule, tried in this order; the earlier rank wins a tie
+  unsigned flags;
+  int kext, kext_swiglu, kext_rope;        // widest accepted K-extension: plain | with SwiGLU | with RoPE fused
+  int fold_max_k;                          // consumer side of the fold: largest K (0: no limit)
+  RopeFuse rope;
+  int (*launch)(GemmParams&, const LaunchCtx&);
 };
-static const TileCfg& tile_cfg(int BM, int BN) {
-  for (const TileCfg& c : kTileCfgs)
-    if (c.BM == BM && c.BN == BN) return c;
-  static const TileCfg generic = {0, 128, 128, 1, 0.9e15, 5e-6, 0.0};   // experimental configs: no hybrid tuning
-  return generic;
+
+// ---- capability predicates: one per question, asked by the launch paths (which turn "no" into their error text) and by fixed_ok ------------
+static bool group_ok(const TileCfg& c, int k2_group_n) { return k2_group_n <= 0 || k2_group_n % c.BN == 0; }   // a LoRA group never straddles an N tile
+static bool k_ok(const TileCfg& c, int K) { return c.fam != FAM_W4 || K % BK == 0; }                           // the hand-scheduled loop has no K tail
+static bool kext_ok(const TileCfg& c, int K2, bool swiglu, bool rope) {
+  const int widest = swiglu ? c.kext_swiglu : rope ? c.kext_rope : c.kext;
+  return widest == KEXT_ANY || (K2 % 32 == 0 && K2 <= widest);
 }
+static bool swiglu_ok(const TileCfg& c, int N) { return (c.flags & CFG_SWIGLU) && N % 256 == 0; }   // N = 2 F, F % 128 == 0
+// `rope`: the RoPE epilogue is fused in the same launch (the column map of ROPE_COLMAP leaves no 64-column groups to the producer side)
+static bool fold_ok(const TileCfg& c, bool rowsq, bool rowscale, int K, bool rope) {
+  if (!rowsq && !rowscale) return true;
+  if (!(c.flags & CFG_FOLD)) return false;
+  if (rowscale && c.fold_max_k > 0 && K > c.fold_max_k) return false;
+  return !(rowsq && rope && c.rope == ROPE_COLMAP);
+}
+static bool rope_n_ok(const TileCfg& c, int N) { return N % (c.rope == ROPE_HEAD_TILE ? 128 : 256) == 0; }
+// Is the RoPE epilogue of this launch fused?  `plain`: nothing else in the epilogue but alpha.
+static bool rope_fused(const TileCfg& c, const GemmParams& p, const ovla_gemm_args* a, bool plain) {
+  if (c.rope == ROPE_UNFUSED || p.split_k > 1) return false;
+  if (c.rope == ROPE_WAVE_SLAB) return true;
+  if (!plain || (a->rope_cols % 128) != 0 || (((uintptr_t)a->rope_cos | (uintptr_t)a->rope_sin | (uintptr_t)a->C) & 15) != 0 || (a->ldc % 8) != 0 || !rope_n_ok(c, p.N)) return false;
+  if (c.rope == ROPE_INTERIOR) return (p.M % 256) == 0 && (a->rope_cols % 256) == 0;
+  return c.rope == ROPE_HEAD_TILE || kext_ok(c, p.K2, false, true);
+}
+
+// The planner's cost model on C CUs.  plan_hybrid asks with num_cus(); fixed_est with the MI355X's 256, which keeps a fixed schedule a function
+// of the problem class only.  (The callers add rounds, slab traffic and the reduce launch's 5 us in their own order: estimates are compared.)
+struct CostModel {
+  const TileCfg& c;
+  int C;
+  int slots() const { return C * c.cost.bpc; }
+  double round_time(int units, int tk) const {
+    const double tkc = 2.0 * c.BM * c.BN * BK / (c.cost.rate / C);
+    const int w = std::min(c.cost.bpc, cdiv(units, C));
+    return tk * std::max(c.cost.tk1, w * tkc) + c.cost.t0;
+  }
+  double slab_traffic(int units) const { return 1.0 * units * (4.0 * c.BM * c.BN) / 5e12; }   // slab writes overlap; the reduce kernel reads them
+};
 
 struct HybridPlan { int full_tiles, rem_tiles, rem_splits; double est; };
 
 static HybridPlan plan_hybrid(int M, int N, int T, const TileCfg& c, int64_t ws_floats) {
-  const int C = num_cus(), slots = C * c.bpc;
-  const double tkc = 2.0 * c.BM * c.BN * BK / (c.rate / C);
-  auto round_time = [&](int units, int tk) {
-    const int w = std::min(c.bpc, cdiv(units, C));
-    return tk * std::max(c.tk1, w * tkc) + c.t0;
-  };
+  const CostModel cm{c, num_cus()};
+  const int slots = cm.slots();
   const int tiles = cdiv(M, c.BM) * cdiv(N, c.BN);
   HybridPlan pl{tiles, 0, 1, 0.0};
   const int full_rounds = tiles / slots, rem = tiles % slots;
-  pl.est = full_rounds * round_time(slots, T);
+  pl.est = full_rounds * cm.round_time(slots, T);
   if (rem == 0) return pl;
-  double best_t = round_time(rem, T);   // unsplit: one more (partial) round
+  double best_t = cm.round_time(rem, T);   // unsplit: one more (partial) round
   int best = 1;
   if (ws_floats > 0) {
     for (int sp = 2; sp <= 8 && sp * 4 <= T; ++sp) {
       if ((int64_t)rem * sp * c.BM * c.BN > ws_floats) break;
       const int units = rem * sp, tk = cdiv(T, sp);
-      const double t = (units <= slots ? round_time(units, tk) : cdiv(units, slots) * round_time(slots, tk)) +
-                       1.0 * rem * sp * (4.0 * c.BM * c.BN) / 5e12 + 5e-6;   // slab writes overlap; the reduce kernel reads them
+      const double t = (units <= slots ? cm.round_time(units, tk) : cdiv(units, slots) * cm.round_time(slots, tk)) + cm.slab_traffic(units) + 5e-6;
       if (t < best_t) { best_t = t; best = sp; }
     }
   }
@@ -1849,11 +1909,237 @@ static HybridPlan plan_hybrid(int M, int N, int T, const TileCfg& c, int64_t ws_
   return pl;
 }
 
+// ---- launchers: one per kernel family; each keeps its LDS size, its kernel and its family's checks ---------------------------------------
+// Before the launch: the tile grid and the K-extension group rule; then, once the family's own checks have passed, the LDS limit of the
+// instantiation (set once: `attr_set` is the instantiation's own flag).
+static int launch_prologue(GemmParams& p, const TileCfg& c) {
+  p.tiles_m = cdiv(p.M, c.BM);
+  p.tiles_n = cdiv(p.N, c.BN);
+  if (!group_ok(c, p.k2_group_n)) {
+    ovla_set_error("ovla_gemm_bf16: k2_group_n=%d is not a multiple of the N tile %d", p.k2_group_n, c.BN);
+    return OVLA_EINVAL;
+  }
+  return OVLA_OK;
+}
+static void set_lds_limit(const void* kern, size_t lds, bool* attr_set) {
+  if (!*attr_set) {
+    (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    *attr_set = true;
+  }
+}
+
+// Full / remainder / split counts of the launch: every tile whole; the planner's hybrid schedule; or the caller's fixed schedule -- the uniform
+// one: every tile whole (splits 1) or every tile split the same number of ways, the hybrid launch with no full tiles and a separate reduce launch.
+// A fixed schedule never plans: its counts must not depend on M.
+static void set_schedule(GemmParams& p, const LaunchCtx& x, int tiles, int splits) {
+  p.full_tiles = tiles; p.rem_tiles = 0; p.rem_splits = 1;
+  if (x.hybrid && !x.fixed && splits == 1 && p.ws != nullptr) {
+    const HybridPlan pl = plan_hybrid(p.M, p.N, p.T1 + p.T2, *x.cfg, x.ws_bytes / 4);
+    p.full_tiles = pl.full_tiles; p.rem_tiles = pl.rem_tiles; p.rem_splits = pl.rem_splits;
+  }
+  if (x.fixed) {
+    if (x.fixed->splits > 1) { p.full_tiles = 0; p.rem_tiles = tiles; p.rem_splits = x.fixed->splits; }
+    p.hyb_cnt = nullptr;
+  }
+}
+static unsigned grid_size(const GemmParams& p, int tiles, int splits) {
+  return p.rem_tiles > 0 ? (unsigned)(p.full_tiles + p.rem_tiles * p.rem_splits) : (unsigned)(tiles * splits);
+}
+
+// After the launch.  The plain split-K reduce (`name`: the launch-failure text):
+static int launch_splitk_reduce(const GemmParams& p, const char* name, hipStream_t stream) {
+  const int64_t quads = (int64_t)p.M * (p.N / 4);
+  int blocks = cdiv(quads, 256);
+  if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3(blocks), dim3(256), 0, stream, p);
+  OVLA_CHECK_LAUNCH(name);
+  return OVLA_OK;
+}
+// ... and the tail of the families with a hybrid schedule: the remainder's reduce launch, unless each tile's last-arriving unit reduces inside
+// the GEMM launch (hyb_cnt); the plain split-K reduce; or nothing.
+struct ReduceTail { void (*hybrid_reduce)(const GemmParams); const char* hybrid_name; const char* splitk_name; };
+static int launch_reduce(const GemmParams& p, const TileCfg& c, int splits, const ReduceTail& t, hipStream_t stream) {
+  if (p.rem_tiles > 0 && p.hyb_cnt == nullptr) {
+    hipLaunchKernelGGL(t.hybrid_reduce, dim3(c.BM * c.BN / 4 / 256 / 4, p.rem_tiles), dim3(256), 0, stream, p);
+    OVLA_CHECK_LAUNCH(t.hybrid_name);
+  } else if (p.rem_tiles == 0 && splits > 1) {
+    return launch_splitk_reduce(p, t.splitk_name, stream);
+  }
+  return OVLA_OK;
+}
+
+template <int BM, int BN, int WM, int WN>
+int launch_cfg(GemmParams& p, const LaunchCtx& x) {
+  const TileCfg& c = *x.cfg;
+  size_t lds = (size_t)2 * (BM + BN) * BK * sizeof(bf16_bits);
+  const size_t epi = (size_t)WM * WN * 32 * (BN / WN + 4) * sizeof(float);   // epilogue staging slabs reuse the same LDS
+  static_assert((size_t)WM * WN * 32 * (BN / WN + 4) * sizeof(float) <= 160 * 1024, "epilogue slabs exceed LDS");
+  if (epi > lds) lds = epi;
+  if (BM == 128 && BN == 128) lds += BM * sizeof(float);                       // s_rstd of the RMSNorm fold, behind both
+  auto kern = gemm_nt_kernel<BM, BN, WM, WN>;
+  static bool attr_set = false;
+  if (int rc = launch_prologue(p, c)) return rc;
+  if (!fold_ok(c, p.rowsq_out, p.rowscale_part, p.K, false)) {
+    ovla_set_error("ovla_gemm_bf16: the RMSNorm fold (rowsq_out / rowscale_part) runs on the 128x128 tile only; this problem resolved to %dx%d", BM, BN);
+    return OVLA_EINVAL;
+  }
+  set_lds_limit(reinterpret_cast<const void*>(kern), lds, &attr_set);
+  const int splits = p.split_k > 1 ? p.split_k : 1, tiles = p.tiles_m * p.tiles_n;
+  set_schedule(p, x, tiles, splits);
+  if (p.rem_tiles == 0 || p.rem_tiles > p.hyb_cnt_n) p.hyb_cnt = nullptr;    // no remainder, or more remainder tiles than counters: separate reduce launch
+  hipLaunchKernelGGL(kern, dim3(grid_size(p, tiles, splits)), dim3(64 * WM * WN), lds, x.stream, p);
+  OVLA_CHECK_LAUNCH("ovla_gemm_bf16");
+  return launch_reduce(p, c, splits, {gemm_hybrid_reduce_kernel<BM, BN>, "ovla_gemm_bf16(hybrid reduce)", "ovla_gemm_bf16(split-k reduce)"}, x.stream);
+}
+
+template <int BM, int BN, int WM, int WN, int STAGES, int MODE = 0>
+int launch_pipe(GemmParams& p, const LaunchCtx& x) {
+  size_t lds = (size_t)STAGES * (BM + BN) * PK * sizeof(bf16_bits);
+  const size_t epi = (size_t)WM * WN * 32 * (BN / WN + 4) * sizeof(float);
+  if (epi > lds) lds = epi;
+  auto kern = gemm_nt_pipe_kernel<BM, BN, WM, WN, STAGES, MODE>;
+  static bool attr_set = false;
+  if (int rc = launch_prologue(p, *x.cfg)) return rc;
+  set_lds_limit(reinterpret_cast<const void*>(kern), lds, &attr_set);
+  const int T = cdiv(p.K, PK) + (p.K2 > 0 ? cdiv(p.K2, PK) : 0);
+  if (p.split_k > T) p.split_k = T;
+  const int splits = p.split_k > 1 ? p.split_k : 1;
+  hipLaunchKernelGGL(kern, dim3((unsigned)(p.tiles_m * p.tiles_n * splits)), dim3(64 * WM * WN), lds, x.stream, p);
+  OVLA_CHECK_LAUNCH("ovla_gemm_bf16(pipe)");
+  return splits > 1 ? launch_splitk_reduce(p, "ovla_gemm_bf16(split-k reduce)", x.stream) : OVLA_OK;   // (no hybrid schedule in this family)
+}
+
+template <int KEXT, int ABL = 0, int WNW = 2, bool RMAP = false, bool GMAP = false>
+int launch_w4(GemmParams& p, const LaunchCtx& x) {
+  const TileCfg& c = *x.cfg;
+  constexpr int BM = 128 * (4 / WNW), BN = 256;
+  if (!k_ok(c, p.K) || p.K2 != 32 * KEXT || !p.fast_addr || p.a_group_n > 0 || !group_ok(c, p.k2_group_n)) {
+    ovla_set_error("ovla_gemm_bf16: the 4-wave configs need K %% 64 == 0, a K-extension of 0, 32, 64 or 96 columns and no block-diagonal mode");
+    return OVLA_EINVAL;
+  }
+  if (!fold_ok(c, p.rowsq_out, p.rowscale_part, p.K, RMAP)) {
+    ovla_set_error("ovla_gemm_bf16: among the 4-wave configs the RMSNorm fold runs on the 128x256 one only (rowscale_part: K <= 4096)");
+    return OVLA_EINVAL;
+  }
+  if (GMAP) {
+    if (!swiglu_ok(c, p.N) || p.split_k > 1 || p.rowsq_out || p.bias || p.residual || p.colscale || p.film_gamma || p.dact_src || p.rope_cos ||
+        (p.Cpre && ((((uintptr_t)p.Cpre) & 15) != 0 || (p.N % 8) != 0)) || (p.k2_group_n > 0 && p.k2_group_n != p.N / 2)) {
+      ovla_set_error("ovla_gemm_bf16: act = OVLA_ACT_SWIGLU needs N = 2 F with F %% 128 == 0, a K-extension grouped by F (or not at all) and nothing else in the epilogue but alpha, "
+                     "the RMSNorm-fold row scale and C_pre (the [M, 2 F] projection output)");
+      return OVLA_EINVAL;
+    }
+  }
+  const size_t lds = (size_t)2 * (BM + BN) * BK * sizeof(bf16_bits) + (WNW == 4 ? 128 * sizeof(float) : 0);   // + s_rstd of the RMSNorm fold
+  auto kern = gemm_nt_w4_kernel<KEXT, ABL, WNW, RMAP, GMAP>;
+  static bool attr_set = false;
+  if (int rc = launch_prologue(p, c)) return rc;
+  set_lds_limit(reinterpret_cast<const void*>(kern), lds, &attr_set);
+  if (GMAP) p.tiles_n = (p.N / 2) / 128;   // a column tile = 128 gate columns and their up partners
+  const int splits = p.split_k > 1 ? p.split_k : 1, tiles = p.tiles_m * p.tiles_n;
+  set_schedule(p, x, tiles, splits);
+  p.hyb_cnt = nullptr;
+  hipLaunchKernelGGL(kern, dim3(grid_size(p, tiles, splits)), dim3(256), lds, x.stream, p);
+  OVLA_CHECK_LAUNCH("ovla_gemm_bf16(w4)");
+  return launch_reduce(p, c, splits, {gemm_hybrid_reduce_kernel<BM, BN>, "ovla_gemm_bf16(w4 hybrid reduce)", "ovla_gemm_bf16(w4 split-k reduce)"}, x.stream);
+}
+
+static int launch_skinny(GemmParams& p, const LaunchCtx& x) {
+  hipLaunchKernelGGL(gemm_skinny_kernel<2>, dim3((unsigned)cdiv(p.M, 32)), dim3(256), 0, x.stream, p);
+  OVLA_CHECK_LAUNCH("ovla_gemm_bf16(skinny)");
+  return OVLA_OK;
+}
+
+static int launch_w4_256x256(GemmParams& p, const LaunchCtx& x);   // the 4-wave rows: defined below the table
+static int launch_w4_128x256(GemmParams& p, const LaunchCtx& x);
+
+// ---- the table ----------------------------------------------------------------------------------------------------------------------------
+// Row makers: the template arguments of the instantiation give the row its BM x BN and its launcher, so a new tile is one line here.
+template <int BM, int BN, int WM, int WN>
+constexpr TileCfg w8_row(int id, Cost cost, int auto_rank, int fixed_rank, unsigned flags, RopeFuse rope = ROPE_UNFUSED) {
+  return {id, BM, BN, FAM_W8, cost, auto_rank, fixed_rank, flags, KEXT_ANY, 0, KEXT_ANY, 0, rope, launch_cfg<BM, BN, WM, WN>};
+}
+template <int BM, int BN, int WM, int WN, int STAGES, int MODE = 0>
+constexpr TileCfg pipe_row(int id) {
+  return {id, BM, BN, FAM_PIPE, kCostGeneric, 0, 0, 0, KEXT_ANY, 0, 0, 0, ROPE_UNFUSED, launch_pipe<BM, BN, WM, WN, STAGES, MODE>};
+}
+
+// Rows stay in the order the kernels have always been instantiated in (8-wave, skinny, ring, 4-wave): the compiler emits the kernels in that
+// order, and a kernel's distance to its .bss data is a literal in its code, so reordering rows changes the library's disassembly.  What
+// has an order of its own -- who `tile = 0` and the fixed-schedule query try first -- is therefore a rank field, not the row order.
+constexpr TileCfg kTiles[] = {
+    // 8-wave gemm_nt_kernel (BK = 64, LDS-DMA double buffer):  id, cost, auto rank, fixed rank, flags, RoPE
+    w8_row<128, 128, 2, 2>(1, {2, 1.13e15, 4e-6, 0.86e-6}, 2, 4, CFG_PLUS100 | CFG_BDIAG | CFG_FOLD, ROPE_HEAD_TILE),
+    w8_row<64, 128, 1, 4>(2, {3, 0.90e15, 3e-6, 0.57e-6}, 3, 5, CFG_PLUS100 | CFG_BDIAG),
+    w8_row<256, 128, 4, 2>(3, kCostGeneric, 0, 0, 0),
+    w8_row<128, 32, 4, 1>(5, {4, 0.60e15, 3e-6, 0.53e-6}, 4, 6, CFG_PLUS100 | CFG_BDIAG),
+    {6, 32, 32, FAM_SKINNY, kCostGeneric, 0, 0, 0, 0, 0, 0, 0, ROPE_UNFUSED, launch_skinny},   // single launch, 32 rows per workgroup; `tile = 0` takes it for LoRA t / dt (gemm_run)
+    // gemm_nt_pipe_kernel (BK = 32 ring): experimental
+    pipe_row<256, 256, 2, 4, 4>(10), pipe_row<256, 128, 2, 4, 5>(11), pipe_row<256, 128, 4, 2, 5>(12), pipe_row<128, 256, 2, 4, 5>(13), pipe_row<128, 128, 2, 2, 4>(14),
+    pipe_row<256, 256, 2, 4, 3>(15),
+    pipe_row<256, 256, 2, 4, 4, 1>(20), pipe_row<256, 256, 2, 4, 3, 1>(21),   // round-3 tuned ring (deferred row + spread refill), 4 and 3 stages
+    w8_row<256, 256, 4, 2>(16, kCost256x256, 0, 0, CFG_PLUS100, ROPE_WAVE_SLAB),   // 4x2 waves (64x128 wave tiles): 1-3 % behind 2x4
+    w8_row<256, 256, 2, 4>(17, kCost256x256, 1, 3, CFG_PLUS100, ROPE_INTERIOR),    // 2x4 waves (128x64 wave tiles)
+    // 4-wave gemm_nt_w4_kernel.  18 is what a launch that resolved to 17 is upgraded to where it measured ahead (gemm_run); 22 has cost
+    // constants of its own but `tile = 0` never picks it by itself
+    {18, 256, 256, FAM_W4, kCost256x256, 0, 2, CFG_PLUS100 | CFG_SWIGLU, 96, 32, 96, 0, ROPE_HEAD_TILE, launch_w4_256x256},
+    {22, 128, 256, FAM_W4, {1, 1.2e15, 5e-6, 0.0}, 0, 1, CFG_PLUS100 | CFG_FOLD | CFG_SWIGLU, 32, 0, 0, 4096, ROPE_COLMAP, launch_w4_128x256},
+};
+// How many rows carry a rank: the ranks of a field must be 1 .. n, each on exactly one row (-1 otherwise).
+constexpr int rank_count(int TileCfg::*rank) {
+  int n = 0;
+  for (const TileCfg& c : kTiles) n = c.*rank > n ? c.*rank : n;
+  for (int r = 1; r <= n; ++r) {
+    int rows = 0;
+    for (const TileCfg& c : kTiles) rows += c.*rank == r;
+    if (rows != 1) return -1;
+  }
+  return n;
+}
+constexpr int kAutoRanks = rank_count(&TileCfg::auto_rank), kFixedRanks = rank_count(&TileCfg::fixed_rank);   // auto: 17, 1, 2, 5; fixed: 22, 18, 17, 1, 2, 5
+static_assert(kAutoRanks > 0 && kFixedRanks > 0, "kTiles: auto_rank / fixed_rank must each number their rows 1 .. n without gaps or repeats");
+
+// The instantiation of a 4-wave config for this launch: template arguments KEXT (K-extension / 32), WNW, RMAP (RoPE column map), GMAP (SwiGLU pair map).
+static int launch_w4_256x256(GemmParams& p, const LaunchCtx& x) {   // register-staged operands, hand-scheduled K loop
+  const bool swiglu = p.act == OVLA_ACT_SWIGLU;   // the fine-tune step's gate | up projection: LoRA rank 32, C_pre = the projection output
+  if (!kext_ok(*x.cfg, p.K2, swiglu, false)) {
+    if (swiglu) ovla_set_error("ovla_gemm_bf16: act = OVLA_ACT_SWIGLU takes a K-extension of 0 or 32 columns, not %d", p.K2);
+    else ovla_set_error("ovla_gemm_bf16: the 4-wave 256x256 config takes a K-extension of 0, 32, 64 or 96 columns, not %d", p.K2);
+    return OVLA_EINVAL;
+  }
+  if (swiglu) return p.K2 == 0 ? launch_w4<0, 0, 2, false, true>(p, x) : launch_w4<1, 0, 2, false, true>(p, x);
+  static constexpr decltype(&launch_w4<0>) by_kext[] = {launch_w4<0>, launch_w4<1>, launch_w4<2>, launch_w4<3>};
+  return by_kext[p.K2 / 32](p, x);
+}
+static int launch_w4_128x256(GemmParams& p, const LaunchCtx& x) {   // 1 x 4 waves of 128x64, the same loop (batch-1 shapes: M = 608 = 4.75 row tiles)
+  const bool swiglu = p.act == OVLA_ACT_SWIGLU, rope = !swiglu && p.rope_cos;   // (RoPE fused: the merged / adapter-free decoder of the batch-1 chunk)
+  if (!kext_ok(*x.cfg, p.K2, swiglu, rope)) {
+    if (swiglu) ovla_set_error("ovla_gemm_bf16: on the 128x256 config act = OVLA_ACT_SWIGLU takes no K-extension");
+    else if (rope) ovla_set_error("ovla_gemm_bf16: the 128x256 config fuses RoPE only without a K-extension");
+    else ovla_set_error("ovla_gemm_bf16: the 4-wave 128x256 config takes a K-extension of 0 or 32 columns, not %d", p.K2);
+    return OVLA_EINVAL;
+  }
+  if (swiglu) return launch_w4<0, 0, 4, false, true>(p, x);
+  if (rope) return launch_w4<0, 0, 4, true>(p, x);
+  return p.K2 == 0 ? launch_w4<0, 0, 4>(p, x) : launch_w4<1, 0, 4>(p, x);
+}
+
+static const TileCfg* find_cfg(int id) {
+  for (const TileCfg& c : kTiles)
+    if (c.id == id) return &c;
+  return nullptr;
+}
+static const TileCfg& by_rank(int TileCfg::*rank, int r) {   // r in 1 .. rank_count(rank): the row exists
+  const TileCfg* c = kTiles;
+  while (c->*rank != r) ++c;
+  return *c;
+}
+
 static int pick_tile(int M, int N, int T, int k2_group_n, int64_t ws_floats, HybridPlan* out) {
   double best = 1e30;
   int tile = 1;
-  for (const TileCfg& c : kTileCfgs) {
-    if (k2_group_n > 0 && k2_group_n % c.BN != 0) continue;
+  for (int r = 1; r <= kAutoRanks; ++r) {
+    const TileCfg& c = by_rank(&TileCfg::auto_rank, r);
+    if (!group_ok(c, k2_group_n)) continue;
     const HybridPlan pl = plan_hybrid(M, N, T, c, ws_floats);
     if (pl.est < best) {
       best = pl.est; tile = c.id;
@@ -1863,185 +2149,9 @@ static int pick_tile(int M, int N, int T, int k2_group_n, int64_t ws_floats, Hyb
   return tile;
 }
 
-// ovla_gemm_bf16_fixed: the caller's schedule for the launch in progress (launch_cfg / launch_w4 read it instead of planning).
-static thread_local const ovla_gemm_schedule* g_fixed = nullptr;
-
-// The uniform schedule: every tile whole (splits 1) or every tile split the same number of ways -- the hybrid launch with no full tiles.
-static void apply_fixed(GemmParams& p, int tiles) {
-  p.full_tiles = tiles; p.rem_tiles = 0; p.rem_splits = 1;
-  if (g_fixed->splits > 1) { p.full_tiles = 0; p.rem_tiles = tiles; p.rem_splits = g_fixed->splits; }
-  p.hyb_cnt = nullptr;   // separate reduce launch
-}
-
-template <int BM, int BN, int WM, int WN>
-int launch_cfg(GemmParams& p, hipStream_t stream, int64_t ws_bytes = 0, bool hybrid = false) {
-  p.tiles_m = cdiv(p.M, BM);
-  p.tiles_n = cdiv(p.N, BN);
-  if (p.k2_group_n > 0 && (p.k2_group_n % BN) != 0) {
-    ovla_set_error("ovla_gemm_bf16: k2_group_n=%d is not a multiple of the N tile %d", p.k2_group_n, BN);
-    return OVLA_EINVAL;
-  }
-  const int splits = p.split_k > 1 ? p.split_k : 1;
-  size_t lds = (size_t)2 * (BM + BN) * BK * sizeof(bf16_bits);
-  const size_t epi = (size_t)WM * WN * 32 * (BN / WN + 4) * sizeof(float);   // epilogue staging slabs reuse the same LDS
-  if (epi > lds) lds = epi;
-  if (BM == 128 && BN == 128) lds += BM * sizeof(float);                       // s_rstd of the RMSNorm fold, behind both
-  if ((p.rowsq_out || p.rowscale_part) && !(BM == 128 && BN == 128 && WM == 2 && WN == 2)) {
-    ovla_set_error("ovla_gemm_bf16: the RMSNorm fold (rowsq_out / rowscale_part) runs on the 128x128 tile only; this problem resolved to %dx%d", BM, BN);
-    return OVLA_EINVAL;
-  }
-  auto kern = gemm_nt_kernel<BM, BN, WM, WN>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  const int tiles = p.tiles_m * p.tiles_n;
-  p.full_tiles = tiles;
-  p.rem_tiles = 0;
-  p.rem_splits = 1;
-  if (hybrid && splits == 1 && p.ws != nullptr) {
-    static_assert((size_t)WM * WN * 32 * (BN / WN + 4) * sizeof(float) <= 160 * 1024, "epilogue slabs exceed LDS");
-    const HybridPlan pl = plan_hybrid(p.M, p.N, p.T1 + p.T2, tile_cfg(BM, BN), ws_bytes / 4);
-    p.full_tiles = pl.full_tiles; p.rem_tiles = pl.rem_tiles; p.rem_splits = pl.rem_splits;
-  }
-  if (g_fixed) apply_fixed(p, tiles);
-  if (p.rem_tiles == 0 || p.rem_tiles > p.hyb_cnt_n) p.hyb_cnt = nullptr;    // no remainder, or more remainder tiles than counters: separate reduce launch
-  const unsigned nblk = p.rem_tiles > 0 ? (unsigned)(p.full_tiles + p.rem_tiles * p.rem_splits) : (unsigned)(tiles * splits);
-  hipLaunchKernelGGL(kern, dim3(nblk), dim3(64 * WM * WN), lds, stream, p);
-  OVLA_CHECK_LAUNCH("ovla_gemm_bf16");
-  if (p.rem_tiles > 0 && p.hyb_cnt == nullptr) {
-    hipLaunchKernelGGL((gemm_hybrid_reduce_kernel<BM, BN>), dim3(BM * BN / 4 / 256 / 4, p.rem_tiles), dim3(256), 0, stream, p);
-    OVLA_CHECK_LAUNCH("ovla_gemm_bf16(hybrid reduce)");
-  } else if (p.rem_tiles > 0) {
-    // reduced inside the GEMM launch by each tile's last-arriving unit
-  } else if (splits > 1) {
-    const int64_t quads = (int64_t)p.M * (p.N / 4);
-    int blocks = cdiv(quads, 256);
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3(blocks), dim3(256), 0, stream, p);
-    OVLA_CHECK_LAUNCH("ovla_gemm_bf16(split-k reduce)");
-  }
-  return OVLA_OK;
-}
-
-template <int BM, int BN, int WM, int WN, int STAGES, int MODE = 0>
-int launch_pipe(GemmParams& p, hipStream_t stream) {
-  p.tiles_m = cdiv(p.M, BM);
-  p.tiles_n = cdiv(p.N, BN);
-  if (p.k2_group_n > 0 && (p.k2_group_n % BN) != 0) {
-    ovla_set_error("ovla_gemm_bf16: k2_group_n=%d is not a multiple of the N tile %d", p.k2_group_n, BN);
-    return OVLA_EINVAL;
-  }
-  const int T = cdiv(p.K, PK) + (p.K2 > 0 ? cdiv(p.K2, PK) : 0);
-  if (p.split_k > T) p.split_k = T;
-  const int splits = p.split_k > 1 ? p.split_k : 1;
-  size_t lds = (size_t)STAGES * (BM + BN) * PK * sizeof(bf16_bits);
-  const size_t epi = (size_t)WM * WN * 32 * (BN / WN + 4) * sizeof(float);
-  if (epi > lds) lds = epi;
-  auto kern = gemm_nt_pipe_kernel<BM, BN, WM, WN, STAGES, MODE>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)(p.tiles_m * p.tiles_n * splits)), dim3(64 * WM * WN), lds, stream, p);
-  OVLA_CHECK_LAUNCH("ovla_gemm_bf16(pipe)");
-  if (splits > 1) {
-    const int64_t quads = (int64_t)p.M * (p.N / 4);
-    int blocks = cdiv(quads, 256);
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3(blocks), dim3(256), 0, stream, p);
-    OVLA_CHECK_LAUNCH("ovla_gemm_bf16(split-k reduce)");
-  }
-  return OVLA_OK;
-}
-
-template <int KEXT, int ABL = 0, int WNW = 2, bool RMAP = false, bool GMAP = false>
-int launch_w4(GemmParams& p, hipStream_t stream, int64_t ws_bytes, bool hybrid) {
-  constexpr int BM = 128 * (4 / WNW), BN = 256;
-  if (p.K % BK != 0 || p.K2 != 32 * KEXT || !p.fast_addr || p.a_group_n > 0 || (p.k2_group_n > 0 && (p.k2_group_n % 256) != 0)) {
-    ovla_set_error("ovla_gemm_bf16: the 4-wave configs need K %% 64 == 0, a K-extension of 0, 32, 64 or 96 columns and no block-diagonal mode");
-    return OVLA_EINVAL;
-  }
-  if ((p.rowsq_out || p.rowscale_part) && (WNW != 4 || (p.rowscale_part && p.rowscale_slots > 64) || (p.rowsq_out && RMAP))) {
-    ovla_set_error("ovla_gemm_bf16: among the 4-wave configs the RMSNorm fold runs on the 128x256 one only (rowscale_part: K <= 4096)");
-    return OVLA_EINVAL;
-  }
-  p.tiles_m = cdiv(p.M, BM);
-  p.tiles_n = GMAP ? (p.N / 2) / 128 : cdiv(p.N, BN);
-  if (GMAP) {
-    if ((p.N % 256) != 0 || p.split_k > 1 || p.rowsq_out || p.bias || p.residual || p.colscale || p.film_gamma || p.dact_src || p.rope_cos ||
-        (p.Cpre && ((((uintptr_t)p.Cpre) & 15) != 0 || (p.N % 8) != 0)) || (p.k2_group_n > 0 && p.k2_group_n != p.N / 2)) {
-      ovla_set_error("ovla_gemm_bf16: act = OVLA_ACT_SWIGLU needs N = 2 F with F %% 128 == 0, a K-extension grouped by F (or not at all) and nothing else in the epilogue but alpha, "
-                     "the RMSNorm-fold row scale and C_pre (the [M, 2 F] projection output)");
-      return OVLA_EINVAL;
-    }
-  }
-  const int splits = p.split_k > 1 ? p.split_k : 1;
-  const size_t lds = (size_t)2 * (BM + BN) * BK * sizeof(bf16_bits) + (WNW == 4 ? 128 * sizeof(float) : 0);   // + s_rstd of the RMSNorm fold
-  auto kern = gemm_nt_w4_kernel<KEXT, ABL, WNW, RMAP, GMAP>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  const int tiles = p.tiles_m * p.tiles_n;
-  p.full_tiles = tiles; p.rem_tiles = 0; p.rem_splits = 1;
-  if (hybrid && splits == 1 && p.ws != nullptr) {
-    static const TileCfg cfg128 = {22, 128, 256, 1, 1.2e15, 5e-6, 0.0};   // (not in kTileCfgs: tile = 0 does not pick this configuration by itself)
-    const HybridPlan pl = plan_hybrid(p.M, p.N, p.T1 + p.T2, WNW == 2 ? tile_cfg(256, 256) : cfg128, ws_bytes / 4);   // (256x256: same plan as the 8-wave config; the K-extension is not a K tile here)
-    p.full_tiles = pl.full_tiles; p.rem_tiles = pl.rem_tiles; p.rem_splits = pl.rem_splits;
-  }
-  if (g_fixed) apply_fixed(p, tiles);
-  p.hyb_cnt = nullptr;
-  const unsigned nblk = p.rem_tiles > 0 ? (unsigned)(p.full_tiles + p.rem_tiles * p.rem_splits) : (unsigned)(tiles * splits);
-  hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds, stream, p);
-  OVLA_CHECK_LAUNCH("ovla_gemm_bf16(w4)");
-  if (p.rem_tiles > 0) {
-    hipLaunchKernelGGL((gemm_hybrid_reduce_kernel<BM, BN>), dim3(BM * BN / 4 / 256 / 4, p.rem_tiles), dim3(256), 0, stream, p);
-    OVLA_CHECK_LAUNCH("ovla_gemm_bf16(w4 hybrid reduce)");
-  } else if (splits > 1) {
-    const int64_t quads = (int64_t)p.M * (p.N / 4);
-    int blocks = cdiv(quads, 256);
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3(blocks), dim3(256), 0, stream, p);
-    OVLA_CHECK_LAUNCH("ovla_gemm_bf16(w4 split-k reduce)");
-  }
-  return OVLA_OK;
-}
-
-}  // namespace
-
-extern "C" int ovla_gemm_plan(int32_t M, int32_t N, int32_t K, int32_t K2, int32_t k2_group_n, int64_t workspace_bytes, int32_t* tile,
-                              int32_t* full_tiles, int32_t* rem_tiles, int32_t* rem_splits, double* est_seconds) {
-  OVLA_REQUIRE(M > 0 && N > 0 && K > 0 && K2 >= 0 && tile, "ovla_gemm_plan: bad arguments");
-  HybridPlan pl{0, 0, 1, 0.0};
-  *tile = pick_tile(M, N, cdiv(K, BK) + (K2 > 0 ? cdiv(K2, BK) : 0), k2_group_n, workspace_bytes / 4, &pl);
-  if (full_tiles) *full_tiles = pl.full_tiles;
-  if (rem_tiles) *rem_tiles = pl.rem_tiles;
-  if (rem_splits) *rem_splits = pl.rem_splits;
-  if (est_seconds) *est_seconds = pl.est;
-  return OVLA_OK;
-}
-
-extern "C" int64_t ovla_gemm_workspace_bytes(int32_t M, int32_t N, int32_t split_k) {
-  return split_k > 1 ? (int64_t)split_k * M * N * 4 : 0;
-}
-
-static thread_local int32_t* g_resolve_only = nullptr;   // ovla_gemm_resolved_tile: run the argument checks and the schedule decision, launch nothing
-
-extern "C" int ovla_gemm_resolved_tile(const ovla_gemm_args* a, int32_t* tile) {
-  OVLA_REQUIRE(tile != nullptr, "ovla_gemm_resolved_tile: null output");
-  *tile = -1;
-  g_resolve_only = tile;
-  const int rc = ovla_gemm_bf16(a, nullptr);
-  g_resolve_only = nullptr;
-  return rc;
-}
-
-extern "C" int ovla_gemm_bf16(const ovla_gemm_args* a, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
+// ovla_gemm_bf16 with its two hidden parameters made arguments.  `fixed`: the caller's schedule (ovla_gemm_bf16_fixed), read by the launchers
+// instead of planning.  `resolve_only`: run the argument checks and the schedule decision, store the tile id, launch nothing (ovla_gemm_resolved_tile).
+static int gemm_run(const ovla_gemm_args* a, const ovla_gemm_schedule* fixed, int32_t* resolve_only, hipStream_t stream) {
   OVLA_REQUIRE(a != nullptr, "ovla_gemm_bf16: null args");
   OVLA_REQUIRE(a->M > 0 && a->N > 0 && a->K > 0, "ovla_gemm_bf16: empty problem M=%d N=%d K=%d", a->M, a->N, a->K);
   OVLA_REQUIRE(a->A && a->B && a->C, "ovla_gemm_bf16: null A/B/C");
@@ -2052,7 +2162,8 @@ extern "C" int ovla_gemm_bf16(const ovla_gemm_args* a, void* stream_) {
   if (a->a_group_n > 0) {
     OVLA_REQUIRE(a->K2 <= 0 && (a->N % a->a_group_n) == 0 && (a->a_group_n == 32 || a->a_group_n % 128 == 0) && a->lda >= (int64_t)(a->N / a->a_group_n) * a->K,
                  "ovla_gemm_bf16: block-diagonal mode needs N %% a_group_n == 0, a_group_n 32 or a multiple of 128, lda >= groups*K, no K-extension");
-    OVLA_REQUIRE(a->tile == 0 || a->tile == 5 || a->tile == 2 || a->tile == 1, "ovla_gemm_bf16: block-diagonal mode runs on the BK=64 kernel tiles only");
+    const TileCfg* c = find_cfg(a->tile);   // (the base id itself: not its +100 form)
+    OVLA_REQUIRE(a->tile == 0 || (c && (c->flags & CFG_BDIAG)), "ovla_gemm_bf16: block-diagonal mode runs on the BK=64 kernel tiles only");
   }
   if (a->K2 > 0) {
     OVLA_REQUIRE(a->A2 && a->B2, "ovla_gemm_bf16: K2>0 but A2/B2 null");
@@ -2121,12 +2232,16 @@ extern "C" int ovla_gemm_bf16(const ovla_gemm_args* a, void* stream_) {
                (!a->residual || ((((uintptr_t)a->residual) & 15) == 0 && (a->ldr % 8) == 0)) && (!a->bias || (((uintptr_t)a->bias) & 15) == 0);
   p.fast_addr = ((int64_t)p.M * p.lda * 2 < (int64_t)4e9 && (int64_t)p.N * p.ldb * 2 < (int64_t)4e9) ? 1 : 0;
 
+  // The tile argument, decoded once: a->tile / 1000 = the timing ablation (above); of the rest, tile % 100 = the base id (a row of kTiles) and
+  // tile / 100 == 1 the same row with the hybrid schedule forced, where the row accepts that.  Anything else is no configuration (cfg stays null).
   int tile = a->tile % 1000;
+  const TileCfg* cfg = (tile / 100 == 0 || tile / 100 == 1) ? find_cfg(tile % 100) : nullptr;
+  if (cfg && tile >= 100 && !(cfg->flags & CFG_PLUS100)) cfg = nullptr;
+  bool hybrid = cfg && tile >= 100;
   const int64_t wsb = a->workspace ? a->workspace_bytes : 0;
   if (a->act == OVLA_ACT_SWIGLU)
-    OVLA_REQUIRE((tile == 0 || tile == 18 || tile == 118 || tile == 22 || tile == 122) && a->ldc >= a->N / 2 && (a->K % BK) == 0,
+    OVLA_REQUIRE((tile == 0 || (cfg && (cfg->flags & CFG_SWIGLU))) && a->ldc >= a->N / 2 && (a->K % BK) == 0,
                  "ovla_gemm_bf16: act = OVLA_ACT_SWIGLU (C [M, N / 2] = silu(gate) * up of the stacked [gate; up] projection) runs on the 4-wave configurations only (tile 0 / 18 / 118 / 22 / 122, K %% 64 == 0)");
-  bool hybrid = false;
   if (tile == 0) {
     // auto schedule.  Skinny outputs (LoRA t / dt, N <= 128) and small M (action head) are HBM-bound weight/activation
     // streams: split K so that >= ~256 workgroups stream concurrently.  Large problems take the 256x256 tile (in-kernel
@@ -2139,13 +2254,8 @@ extern "C" int ovla_gemm_bf16(const ovla_gemm_args* a, void* stream_) {
     };
     static const bool skinny_on = []() { const char* e = getenv("OVLA_SKINNY"); return !(e && e[0] == '0'); }();   // A/B switch
     if (skinny_on && p.N == 32 && p.a_group_n == 0 && p.K <= 3072 && p.M >= 512 && p.K2 == 0 && p.split_k <= 1 && !a->bias && !a->C_pre && !a->colscale &&
-        !a->residual && !a->film_gamma && !a->dact_src && !a->rope_cos && a->act == OVLA_ACT_NONE) {
-      if (g_resolve_only) { *g_resolve_only = 6; return OVLA_OK; }
-      hipLaunchKernelGGL(gemm_skinny_kernel<2>, dim3((unsigned)cdiv(p.M, 32)), dim3(256), 0, stream, p);
-      OVLA_CHECK_LAUNCH("ovla_gemm_bf16(skinny)");
-      return OVLA_OK;
-    }
-    if (a->act == OVLA_ACT_SWIGLU) { tile = 18; hybrid = true; }
+        !a->residual && !a->film_gamma && !a->dact_src && !a->rope_cos && a->act == OVLA_ACT_NONE) { tile = 6; }
+    else if (a->act == OVLA_ACT_SWIGLU) { tile = 18; hybrid = true; }
     else if (p.N <= 32 || p.a_group_n == 32) { tile = 5; if (p.split_k <= 1) p.split_k = want_split(cdiv(p.M, 128) * cdiv(p.N, 32)); }
     else if (p.a_group_n > 0) { tile = 1; }
     else if (p.M <= 64 || p.N <= 128) { tile = 2; if (p.split_k <= 1) p.split_k = want_split(cdiv(p.M, 64) * cdiv(p.N, 128)); }
@@ -2153,160 +2263,108 @@ extern "C" int ovla_gemm_bf16(const ovla_gemm_args* a, void* stream_) {
       hybrid = true;
       tile = pick_tile(p.M, p.N, T, p.k2_group_n, wsb / 4, nullptr);
       // The 4-wave config of the 256x256 tile (hand-scheduled K loop) where it measured ahead of the 8-wave one (tools/gemm_w4_probe.py: +4...9 % per launch on
-      // the decoder shapes): K >= 4096 in whole K tiles, a LoRA K-extension of 0 / 32 / 64 / 96 columns, the alpha / bias / residual or the RoPE epilogue.  OVLA_GEMM_W4=0 switches it off.
+      // the decoder shapes): K >= 4096 in whole K tiles, a LoRA K-extension it accepts (0 / 32 / 64 / 96 columns), the alpha / bias / residual or the RoPE epilogue.  OVLA_GEMM_W4=0 switches it off.
       static const bool w4_on = []() { const char* e = getenv("OVLA_GEMM_W4"); return !(e && e[0] == '0'); }();
       static const int w4_min_k = []() { const char* e = getenv("OVLA_GEMM_W4_MINK"); return e ? atoi(e) : 4096; }();   // tuning switch
-      if (w4_on && tile == 17 && p.K >= w4_min_k && (p.K % BK) == 0 && (p.K2 == 0 || p.K2 == 32 || p.K2 == 64 || p.K2 == 96) && (p.k2_group_n % 256) == 0 && p.fast_addr &&
+      const TileCfg& w4 = *find_cfg(18);
+      if (w4_on && tile == 17 && p.K >= w4_min_k && k_ok(w4, p.K) && kext_ok(w4, p.K2, false, false) && (p.k2_group_n % w4.BN) == 0 && p.fast_addr &&
           (p.fast_epi || (a->rope_cos && rope_plain)) && p.act == OVLA_ACT_NONE && !a->C_pre && !a->colscale && !a->rowsq_out && !a->rowscale_part && p.split_k <= 1)
         tile = 18;
     }
+    cfg = find_cfg(tile);
   }
-  if (g_resolve_only) { *g_resolve_only = tile; return OVLA_OK; }
+  if (resolve_only) { *resolve_only = tile; return OVLA_OK; }
   if (a->rope_cos) {
-    // fused only where one wave slab is one head (256x256 tile, 4x2 waves) and the epilogue runs in-kernel or in the hybrid reduce;
-    // every other schedule computes the plain projection and rotates it with one ovla_rope launch (same arithmetic)
-    // ... or, on the default 2x4 layout, where every q | k tile is an interior tile whose waves take the columns together with their
-    // rotation partners (gemm_nt_kernel: rope_tile): M, N and rope_cols multiples of 256, nothing but alpha in the epilogue
-    const bool fused17 = (tile == 17 || tile == 117) && p.split_k <= 1 && rope_plain && (p.M % 256) == 0 && (p.N % 256) == 0 && (a->rope_cols % 256) == 0 &&
-                         (((uintptr_t)a->rope_cos | (uintptr_t)a->rope_sin | (uintptr_t)a->C) & 15) == 0 && (a->ldc % 8) == 0;
-    // ... and on the 128x128 tile (2x2 waves; batch-1 inference, M = 608): one head per column tile, any M (edge rows are skipped in the read-back)
-    const bool fused1 = (tile == 1 || tile == 101) && p.split_k <= 1 && rope_plain && (p.N % 128) == 0 && (a->rope_cols % 128) == 0 &&
-                        (((uintptr_t)a->rope_cos | (uintptr_t)a->rope_sin | (uintptr_t)a->C) & 15) == 0 && (a->ldc % 8) == 0;
-    // ... and on the 4-wave 256x256 config (one head per wave slab, any M)
-    const bool fused18 = (tile == 18 || tile == 118) && p.split_k <= 1 && rope_plain && (p.N % 128) == 0 && (a->rope_cols % 128) == 0 &&
-                         (((uintptr_t)a->rope_cos | (uintptr_t)a->rope_sin | (uintptr_t)a->C) & 15) == 0 && (a->ldc % 8) == 0;
-    // ... and on the 4-wave 128x256 config (two heads per column tile, the RoPE column map; no K-extension)
-    const bool fused22 = (tile == 22 || tile == 122) && p.split_k <= 1 && rope_plain && p.K2 == 0 && (p.N % 256) == 0 && (a->rope_cols % 128) == 0 &&
-                         (((uintptr_t)a->rope_cos | (uintptr_t)a->rope_sin | (uintptr_t)a->C) & 15) == 0 && (a->ldc % 8) == 0;
-    const bool fused = ((tile == 16 || tile == 116) && p.split_k <= 1) || fused17 || fused1 || fused18 || fused22;
-    if (fused) {
+    if (cfg && rope_fused(*cfg, p, a, rope_plain)) {
       p.rope_cos = (const bf16_bits*)a->rope_cos; p.rope_sin = (const bf16_bits*)a->rope_sin;
-    } else {
+    } else {   // the plain projection under the same tile id and the same fixed schedule, then one ovla_rope launch
       ovla_gemm_args plain = *a;
       plain.rope_cos = plain.rope_sin = nullptr;
-      if (int rc = ovla_gemm_bf16(&plain, stream_)) return rc;
+      if (int rc = gemm_run(&plain, fixed, nullptr, stream)) return rc;
       ovla_rope_args r = {};
       r.qk = a->C; r.ld = a->ldc; r.rows = a->M; r.S = a->rope_S; r.n_heads = a->rope_cols / 128; r.head_dim = 128;
       r.cos_table = a->rope_cos; r.sin_table = a->rope_sin; r.inverse = 0;
-      return ovla_rope(&r, stream_);
+      return ovla_rope(&r, (void*)stream);
     }
   }
-  switch (tile) {
-    case 1: return launch_cfg<128, 128, 2, 2>(p, stream, wsb, hybrid);
-    case 2: return launch_cfg<64, 128, 1, 4>(p, stream, wsb, hybrid);
-    case 3: return launch_cfg<256, 128, 4, 2>(p, stream);
-    case 5: return launch_cfg<128, 32, 4, 1>(p, stream, wsb, hybrid);
-    case 6:
-      hipLaunchKernelGGL(gemm_skinny_kernel<2>, dim3((unsigned)cdiv(p.M, 32)), dim3(256), 0, stream, p);
-      OVLA_CHECK_LAUNCH("ovla_gemm_bf16(skinny)");
-      return OVLA_OK;
-    case 10: return launch_pipe<256, 256, 2, 4, 4>(p, stream);
-    case 11: return launch_pipe<256, 128, 2, 4, 5>(p, stream);
-    case 12: return launch_pipe<256, 128, 4, 2, 5>(p, stream);
-    case 13: return launch_pipe<128, 256, 2, 4, 5>(p, stream);
-    case 14: return launch_pipe<128, 128, 2, 2, 4>(p, stream);
-    case 15: return launch_pipe<256, 256, 2, 4, 3>(p, stream);
-    case 20: return launch_pipe<256, 256, 2, 4, 4, 1>(p, stream);   // round-3 tuned ring (deferred row + spread refill), 4 and 3 stages
-    case 21: return launch_pipe<256, 256, 2, 4, 3, 1>(p, stream);
-    case 16: return launch_cfg<256, 256, 4, 2>(p, stream, wsb, hybrid);   // 4x2 waves (64x128 wave tiles): 1-3 % behind 2x4; one head per wave slab (fused RoPE)
-    case 116: return launch_cfg<256, 256, 4, 2>(p, stream, wsb, true);
-    case 17: return launch_cfg<256, 256, 2, 4>(p, stream, wsb, hybrid);   // 2x4 waves (128x64 wave tiles)
-    case 117: return launch_cfg<256, 256, 2, 4>(p, stream, wsb, true);
-    case 18: case 118: {   // 4-wave 256x256, register-staged operands, hand-scheduled K loop
-      const bool hy = hybrid || tile == 118;
-      if (p.act == OVLA_ACT_SWIGLU) {   // the SwiGLU pair map on the 256x256 tile (the fine-tune step's gate | up projection: LoRA rank 32, C_pre = the projection output)
-        if (p.K2 == 0) return launch_w4<0, 0, 2, false, true>(p, stream, wsb, hy);
-        if (p.K2 == 32) return launch_w4<1, 0, 2, false, true>(p, stream, wsb, hy);
-        ovla_set_error("ovla_gemm_bf16: act = OVLA_ACT_SWIGLU takes a K-extension of 0 or 32 columns, not %d", p.K2);
-        return OVLA_EINVAL;
-      }
-      switch (p.K2) {
-        case 0: return launch_w4<0>(p, stream, wsb, hy);
-        case 32: return launch_w4<1>(p, stream, wsb, hy);
-        case 64: return launch_w4<2>(p, stream, wsb, hy);
-        case 96: return launch_w4<3>(p, stream, wsb, hy);
-        default: ovla_set_error("ovla_gemm_bf16: the 4-wave 256x256 config takes a K-extension of 0, 32, 64 or 96 columns, not %d", p.K2); return OVLA_EINVAL;
-      }
-    }
-    case 22: case 122: {   // 128x256 tile on 1 x 4 waves of 128x64, the same hand-scheduled loop (batch-1 shapes: M = 608 = 4.75 row tiles)
-      const bool hy = hybrid || tile == 122;
-      if (p.act == OVLA_ACT_SWIGLU) {   // the SwiGLU pair map (no K-extension on this tile)
-        if (p.K2 != 0) { ovla_set_error("ovla_gemm_bf16: on the 128x256 config act = OVLA_ACT_SWIGLU takes no K-extension"); return OVLA_EINVAL; }
-        return launch_w4<0, 0, 4, false, true>(p, stream, wsb, hy);
-      }
-      if (p.rope_cos) {   // the RoPE column map (only without a K-extension: the merged / adapter-free decoder of the batch-1 chunk)
-        if (p.K2 != 0) { ovla_set_error("ovla_gemm_bf16: the 128x256 config fuses RoPE only without a K-extension"); return OVLA_EINVAL; }
-        return launch_w4<0, 0, 4, true>(p, stream, wsb, hy);
-      }
-      switch (p.K2) {
-        case 0: return launch_w4<0, 0, 4>(p, stream, wsb, hy);
-        case 32: return launch_w4<1, 0, 4>(p, stream, wsb, hy);
-        default: ovla_set_error("ovla_gemm_bf16: the 4-wave 128x256 config takes a K-extension of 0 or 32 columns, not %d", p.K2); return OVLA_EINVAL;
-      }
-    }
+  const LaunchCtx x{cfg, stream, wsb, hybrid, fixed};
 #ifdef OVLA_GEMM_ABLATE
-    case 218: return launch_w4<0, 1>(p, stream, wsb, false);
-    case 318: return launch_w4<0, 2>(p, stream, wsb, false);
-    case 418: return launch_w4<0, 3>(p, stream, wsb, false);
-    case 518: return launch_w4<0, 4>(p, stream, wsb, false);    // no lgkmcnt waits in the rows (wrong results, timing only)
-    case 618: return launch_w4<0, 8>(p, stream, wsb, false);    // no vmcnt waits in the rows
-    case 718: return launch_w4<0, 12>(p, stream, wsb, false);   // neither
-#endif
-    case 101: return launch_cfg<128, 128, 2, 2>(p, stream, wsb, true);
-    case 102: return launch_cfg<64, 128, 1, 4>(p, stream, wsb, true);
-    case 105: return launch_cfg<128, 32, 4, 1>(p, stream, wsb, true);
-    default: ovla_set_error("ovla_gemm_bf16: unknown tile id %d", tile); return OVLA_EINVAL;
+  const LaunchCtx xa{find_cfg(18), stream, wsb, false, fixed};
+  switch (tile) {   // timing ablations of id 18's K loop (tools/gemm_ablate.py)
+    case 218: return launch_w4<0, 1>(p, xa);
+    case 318: return launch_w4<0, 2>(p, xa);
+    case 418: return launch_w4<0, 3>(p, xa);
+    case 518: return launch_w4<0, 4>(p, xa);    // no lgkmcnt waits in the rows (wrong results, timing only)
+    case 618: return launch_w4<0, 8>(p, xa);    // no vmcnt waits in the rows
+    case 718: return launch_w4<0, 12>(p, xa);   // neither
   }
+#endif
+  if (!cfg) { ovla_set_error("ovla_gemm_bf16: unknown tile id %d", tile); return OVLA_EINVAL; }
+  return cfg->launch(p, x);
 }
+
+}  // namespace
+
+extern "C" int ovla_gemm_plan(int32_t M, int32_t N, int32_t K, int32_t K2, int32_t k2_group_n, int64_t workspace_bytes, int32_t* tile,
+                              int32_t* full_tiles, int32_t* rem_tiles, int32_t* rem_splits, double* est_seconds) {
+  OVLA_REQUIRE(M > 0 && N > 0 && K > 0 && K2 >= 0 && tile, "ovla_gemm_plan: bad arguments");
+  HybridPlan pl{0, 0, 1, 0.0};
+  *tile = pick_tile(M, N, cdiv(K, BK) + (K2 > 0 ? cdiv(K2, BK) : 0), k2_group_n, workspace_bytes / 4, &pl);
+  if (full_tiles) *full_tiles = pl.full_tiles;
+  if (rem_tiles) *rem_tiles = pl.rem_tiles;
+  if (rem_splits) *rem_splits = pl.rem_splits;
+  if (est_seconds) *est_seconds = pl.est;
+  return OVLA_OK;
+}
+
+extern "C" int64_t ovla_gemm_workspace_bytes(int32_t M, int32_t N, int32_t split_k) {
+  return split_k > 1 ? (int64_t)split_k * M * N * 4 : 0;
+}
+
+extern "C" int ovla_gemm_resolved_tile(const ovla_gemm_args* a, int32_t* tile) {
+  OVLA_REQUIRE(tile != nullptr, "ovla_gemm_resolved_tile: null output");
+  *tile = -1;
+  return gemm_run(a, nullptr, tile, nullptr);
+}
+
+extern "C" int ovla_gemm_bf16(const ovla_gemm_args* a, void* stream) { return gemm_run(a, nullptr, nullptr, (hipStream_t)stream); }
 
 // ---- batch-invariant schedules (ovla.h: ovla_gemm_fixed_schedule / ovla_gemm_bf16_fixed) --------------------------------------------------
 namespace {
-struct FixedCand { int tile, BM, BN; bool w4; };
-const FixedCand kFixedCands[] = {{22, 128, 256, true}, {18, 256, 256, true}, {17, 256, 256, false}, {1, 128, 128, false}, {2, 64, 128, false}, {5, 128, 32, false}};
-const FixedCand* fixed_cand(int tile) {
-  for (const FixedCand& c : kFixedCands)
-    if (c.tile == tile) return &c;
-  return nullptr;
+const TileCfg* fixed_cfg(int tile) {
+  const TileCfg* c = find_cfg(tile);
+  return c && c->fixed_rank > 0 ? c : nullptr;
 }
 
-// Can tile configuration `c` run this problem class, split `splits` ways?  (The same rules ovla_gemm_bf16's launch paths enforce; splits keep
-// >= 4 K tiles per part, and a launch whose epilogue a configuration would run differently for other M -- RoPE fused or not on the 256x256
-// tile depends on M % 256 -- is not offered.)
-bool fixed_ok(const FixedCand& c, int N, int K, int K2, int k2_group_n, int flags, int splits) {
+// Can tile configuration `c` run this problem class, split `splits` ways?  What a configuration can run is asked of the predicates the launch
+// paths ask; what is written out here are the rules of a FIXED schedule only, each stricter than (or, marked, different from) the launch.
+bool fixed_ok(const TileCfg& c, int N, int K, int K2, int k2_group_n, int flags, int splits) {
   const int T1 = cdiv(K, BK);
-  if (splits < 1 || splits > 8 || (splits > 1 && splits * 4 > T1)) return false;
-  if (k2_group_n > 0 && k2_group_n % c.BN != 0) return false;
+  if (splits < 1 || splits > 8 || (splits > 1 && splits * 4 > T1)) return false;   // splits keep >= 4 K tiles per part
   const bool rope = flags & OVLA_EPI_ROPE, rowscale = flags & OVLA_EPI_ROWSCALE, rowsq = flags & OVLA_EPI_ROWSQ, swiglu = flags & OVLA_EPI_SWIGLU;
-  if (c.w4) {
-    if ((flags & OVLA_EPI_GENERAL) || K % BK != 0 || T1 < 8) return false;   // (the hand-scheduled loop is measured and tested on long K only)
-    if (c.tile == 22) {
-      if (!(K2 == 0 || (K2 == 32 && !rope && !swiglu))) return false;
-      if ((rope || swiglu) && N % 256 != 0) return false;
-      if (rowscale && K > 4096) return false;
-      if (rope && rowsq) return false;
-      return true;
-    }
-    if (rowscale || rowsq) return false;   // tile 18
-    if (swiglu) return (K2 == 0 || K2 == 32) && N % 256 == 0;
-    return K2 == 0 || K2 == 32 || K2 == 64 || K2 == 96;
+  if (!group_ok(c, k2_group_n) || !k_ok(c, K) || !kext_ok(c, K2, swiglu, rope) || !fold_ok(c, rowsq, rowscale, K, rope) || (swiglu && !swiglu_ok(c, N))) return false;
+  // The 4-wave configs: no general epilogue (the launch takes a forced tile = 18 with one, through epilogue_store), and long K only -- the
+  // hand-scheduled loop is measured and tested there; a forced tile = 18 with T1 < 8 launches.
+  if (c.fam == FAM_W4 && ((flags & OVLA_EPI_GENERAL) || T1 < 8)) return false;
+  if (rope) {
+    // A launch whose epilogue a configuration would run differently for other M is not offered: RoPE fused or not on the 256x256 8-wave tile
+    // depends on M % 256; the configurations that never fuse it would take a second launch.
+    if (c.rope != ROPE_HEAD_TILE && c.rope != ROPE_COLMAP) return false;
+    // (Differs from rope_fused: the 4-wave 256x256 config is offered whatever N; with N % 128 != 0 its launch rotates in a second pass, for every M alike.)
+    if (!(c.fam == FAM_W4 && c.rope == ROPE_HEAD_TILE) && !rope_n_ok(c, N)) return false;
   }
-  if (swiglu) return false;
-  if (rowscale || rowsq || rope) return c.tile == 1 && (!rope || N % 128 == 0);
   return true;
 }
 
-// Uniform-schedule time from the planner's cost model (plan_hybrid), on the MI355X's 256 CUs: ceil(units / slots) rounds of tk K tiles each,
+// Uniform-schedule time from the planner's cost model, on the MI355X's 256 CUs: ceil(units / slots) rounds of tk K tiles each,
 // plus the slab traffic and the reduce launch when split.
-double fixed_est(int M, int N, int T, const FixedCand& fc, int splits) {
-  static const TileCfg cfg128 = {22, 128, 256, 1, 1.2e15, 5e-6, 0.0};
-  const TileCfg& c = fc.tile == 22 ? cfg128 : tile_cfg(fc.BM, fc.BN);
-  const int C = 256, slots = C * c.bpc;
-  const double tkc = 2.0 * c.BM * c.BN * BK / (c.rate / C);
-  auto round_time = [&](int units, int tk) { return tk * std::max(c.tk1, std::min(c.bpc, cdiv(units, C)) * tkc) + c.t0; };
+double fixed_est(int M, int N, int T, const TileCfg& c, int splits) {
+  const CostModel cm{c, 256};
+  const int slots = cm.slots();
   const int units = cdiv(M, c.BM) * cdiv(N, c.BN) * splits, tk = cdiv(T, splits);
   const int rounds = cdiv(units, slots);
-  double t = (rounds - 1) * round_time(slots, tk) + round_time(units - (rounds - 1) * slots, tk);
-  if (splits > 1) t += 1.0 * units * (4.0 * c.BM * c.BN) / 5e12 + 5e-6;
+  double t = (rounds - 1) * cm.round_time(slots, tk) + cm.round_time(units - (rounds - 1) * slots, tk);
+  if (splits > 1) t += cm.slab_traffic(units) + 5e-6;
   return t;
 }
 }  // namespace
@@ -2318,50 +2376,48 @@ extern "C" int ovla_gemm_fixed_schedule(int32_t N, int32_t K, int32_t K2, int32_
   const int T = cdiv(K, BK) + (K2 > 0 ? cdiv(K2, BK) : 0);
   double best_at[sizeof(kRows) / sizeof(kRows[0])];
   for (double& b : best_at) b = 1e30;
-  for (const FixedCand& c : kFixedCands)
+  for (int r = 1; r <= kFixedRanks; ++r)
     for (int s : kSplits)
-      if (fixed_ok(c, N, K, K2, k2_group_n, epi_flags, s))
+      if (const TileCfg& c = by_rank(&TileCfg::fixed_rank, r); fixed_ok(c, N, K, K2, k2_group_n, epi_flags, s))
         for (size_t i = 0; i < sizeof(kRows) / sizeof(kRows[0]); ++i) best_at[i] = std::min(best_at[i], fixed_est(kRows[i], N, T, c, s));
   double best = 1e30;
   out->tile = 0; out->splits = 0;
-  for (const FixedCand& c : kFixedCands)
+  for (int r = 1; r <= kFixedRanks; ++r)
     for (int s : kSplits) {
+      const TileCfg& c = by_rank(&TileCfg::fixed_rank, r);
       if (!fixed_ok(c, N, K, K2, k2_group_n, epi_flags, s)) continue;
       double score = 0.0;   // summed slowdown against the best uniform schedule at each row count
       for (size_t i = 0; i < sizeof(kRows) / sizeof(kRows[0]); ++i) score += fixed_est(kRows[i], N, T, c, s) / best_at[i];
-      if (score < best - 1e-9) { best = score; out->tile = c.tile; out->splits = s; }
+      if (score < best - 1e-9) { best = score; out->tile = c.id; out->splits = s; }
     }
   OVLA_REQUIRE(out->tile != 0, "ovla_gemm_fixed_schedule: no tile configuration runs N=%d K=%d K2=%d k2_group_n=%d epilogue flags %d", N, K, K2, k2_group_n, epi_flags);
   return OVLA_OK;
 }
 
 extern "C" int64_t ovla_gemm_fixed_workspace_bytes(int32_t M, int32_t N, const ovla_gemm_schedule* s) {
-  const FixedCand* c = s ? fixed_cand(s->tile) : nullptr;
+  const TileCfg* c = s ? fixed_cfg(s->tile) : nullptr;
   if (!c || s->splits <= 1 || M <= 0 || N <= 0) return 0;
   return (int64_t)cdiv(M, c->BM) * cdiv(N, c->BN) * s->splits * c->BM * c->BN * 4;
 }
 
 extern "C" int ovla_gemm_bf16_fixed(const ovla_gemm_args* a, const ovla_gemm_schedule* s, void* stream) {
   OVLA_REQUIRE(a != nullptr && s != nullptr, "ovla_gemm_bf16_fixed: null argument");
-  const FixedCand* c = fixed_cand(s->tile);
+  const TileCfg* c = fixed_cfg(s->tile);
   OVLA_REQUIRE(c != nullptr && s->splits >= 1 && s->splits <= 8, "ovla_gemm_bf16_fixed: tile %d / splits %d is not a fixed schedule (tile 1, 2, 5, 17, 18 or 22; splits 1 .. 8)",
                s->tile, s->splits);
   OVLA_REQUIRE(a->tile == 0 && a->split_k <= 1 && a->a_group_n == 0 && !a->dact_src,
                "ovla_gemm_bf16_fixed: the schedule replaces tile / split_k; block-diagonal mode and the backward epilogues are not supported");
   OVLA_REQUIRE(a->K > 0 && (s->splits == 1 || s->splits * 4 <= cdiv(a->K, BK)), "ovla_gemm_bf16_fixed: %d splits need K >= %d (K=%d)", s->splits, s->splits * 4 * BK, a->K);
-  if (c->w4) {
+  if (c->fam == FAM_W4) {
     const bool fast_epi = !a->film_gamma && !a->C_pre && !a->colscale && (a->act == OVLA_ACT_NONE || a->act == OVLA_ACT_SWIGLU) &&
                           (!a->residual || ((((uintptr_t)a->residual) & 15) == 0 && (a->ldr % 8) == 0)) && (!a->bias || (((uintptr_t)a->bias) & 15) == 0);
     OVLA_REQUIRE(fast_epi, "ovla_gemm_bf16_fixed: the 4-wave configurations take alpha, 16-byte aligned bias / residual, RoPE, the RMSNorm fold and SwiGLU only");
   }
-  if (a->rope_cos) OVLA_REQUIRE(s->tile == 1 || s->tile == 18 || s->tile == 22, "ovla_gemm_bf16_fixed: RoPE runs fused on tiles 1, 18 and 22 only");
+  if (a->rope_cos) OVLA_REQUIRE(c->rope == ROPE_HEAD_TILE || c->rope == ROPE_COLMAP, "ovla_gemm_bf16_fixed: RoPE runs fused on tiles 1, 18 and 22 only");
   if (s->splits > 1)
     OVLA_REQUIRE(a->workspace && aligned16(a->workspace) && a->workspace_bytes >= ovla_gemm_fixed_workspace_bytes(a->M, a->N, s),
                  "ovla_gemm_bf16_fixed: needs a 16-byte aligned workspace of %lld bytes", (long long)ovla_gemm_fixed_workspace_bytes(a->M, a->N, s));
   ovla_gemm_args b = *a;
   b.tile = s->tile; b.split_k = 1; b.hybrid_counters = nullptr; b.n_hybrid_counters = 0;
-  g_fixed = s;
-  const int rc = ovla_gemm_bf16(&b, stream);
-  g_fixed = nullptr;
-  return rc;
+  return gemm_run(&b, s, nullptr, (hipStream_t)stream);
 }
