@@ -393,6 +393,13 @@ int ovla_masked_mean(const ovla_masked_mean_args* a, void* stream);
 typedef struct { const int64_t* ids; const int64_t* labels; const void* embed_table; void* out; int32_t B, L, D, vocab; int64_t action_token_begin; } ovla_language_average_args;
 int ovla_language_average(const ovla_language_average_args* a, void* stream);
 
+/* The same vector for a right-padded batch in ONE launch: row b averages the positions i < lens[b] only (lens int32 [B] on the device, each
+ * in [1, L]), otherwise the rule above.  out[b,:] is bit for bit what ovla_language_average returns for the single row ids[b, :lens[b]],
+ * labels[b, :lens[b]] (same fp32 summation order, one rounding), so pad tokens never enter a prompt's mean and the batched FiLM forward is
+ * capturable too (engine.ChunkGraph(film=True)). */
+typedef struct { const int64_t* ids; const int64_t* labels; const int32_t* lens; const void* embed_table; void* out; int32_t B, L, D, vocab; int64_t action_token_begin; } ovla_language_average_ragged_args;
+int ovla_language_average_ragged(const ovla_language_average_ragged_args* a, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Multimodal sequence assembly (modeling_prismatic.py:571-629): one pass writes
  *   out[b, 0]            = embed[ids[b,0]]
@@ -442,6 +449,15 @@ typedef struct {
   int32_t rows, vocab; float grad_scale;
 } ovla_token_ce_args;
 int ovla_token_ce(const ovla_token_ce_args* a, void* stream);
+
+/* Greedy decode of the discrete action tokens (modeling_prismatic.py:929-942: `logits.argmax(dim=2)`, then
+ * `np.clip(vocab_size - ids - 1, 0, bin_centers.shape[0] - 1)`), on the device so that it can sit inside a captured graph:
+ *   token[r] = lowest index of the maximum of logits[r, 0 .. vocab)          (the tie rule of ovla_token_ce's argmax)
+ *   bin[r]   = clip(n_tokens - token[r] - 1, 0, n_bins - 1)
+ * logits bf16 [rows, ld], ld >= vocab, values finite or -inf; columns [vocab, ld) are never read.  token / bin int32 [rows].  The float64
+ * bin-centre lookup and the un-normalisation stay on the host. */
+typedef struct { const void* logits; int64_t ld; int32_t* token; int32_t* bin; int32_t rows, vocab, n_tokens, n_bins; } ovla_argmax_bins_args;
+int ovla_argmax_bins(const ovla_argmax_bins_args* a, void* stream);
 
 typedef struct {
   const void* x; const void* W; const void* b; void* pred;   /* bf16 */

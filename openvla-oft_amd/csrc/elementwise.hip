@@ -445,6 +445,29 @@ __global__ __launch_bounds__(256) void language_average_kernel(const int64_t* __
   out[(int64_t)b * D + col] = f2bf(s / (float)(cnt > 0 ? cnt : 1));
 }
 
+// Ragged form of language_average_kernel for a right-padded batch: row b walks positions i < lens[b] only, in the same order and with the
+// same fp32 accumulation, so out[b] is bit for bit language_average_kernel's result on the single row ids[b, :lens[b]], labels[b, :lens[b]].
+__global__ __launch_bounds__(256) void language_average_ragged_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ labels,
+                                                                      const int32_t* __restrict__ lens, const bf16_bits* __restrict__ embed,
+                                                                      bf16_bits* __restrict__ out, int L, int D, int vocab, int64_t action_token_begin) {
+  const int b = blockIdx.y;
+  const int col = blockIdx.x * blockDim.x + threadIdx.x;
+  if (col >= D) return;
+  int n = lens[b];
+  n = n < 0 ? 0 : (n > L ? L : n);                            // a length outside [1, L] never reads outside the row
+  float s = 0.f;
+  int cnt = 0;
+  for (int i = 0; i < n; ++i) {
+    if (labels[(int64_t)b * L + i] <= action_token_begin) {
+      int64_t id = ids[(int64_t)b * L + i];
+      id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
+      s += bf2f(embed[id * D + col]);
+      ++cnt;
+    }
+  }
+  out[(int64_t)b * D + col] = f2bf(s / (float)(cnt > 0 ? cnt : 1));
+}
+
 // FiLM backward: one thread per (batch, column), walking the batch's rows (coalesced across the 256 columns of a block).
 __global__ __launch_bounds__(256) void film_bwd_kernel(bf16_bits* __restrict__ dy, const bf16_bits* __restrict__ x_pre,
                                                        const bf16_bits* __restrict__ gamma, float* __restrict__ dgamma,
@@ -1358,6 +1381,15 @@ extern "C" int ovla_language_average(const ovla_language_average_args* a, void* 
   hipLaunchKernelGGL(language_average_kernel, dim3(cdiv(a->D, 256), a->B), dim3(256), 0, stream, a->ids, a->labels, (const bf16_bits*)a->embed_table,
                      (bf16_bits*)a->out, a->L, a->D, a->vocab, a->action_token_begin);
   OVLA_CHECK_LAUNCH("ovla_language_average");
+  return OVLA_OK;
+}
+extern "C" int ovla_language_average_ragged(const ovla_language_average_ragged_args* a, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  OVLA_REQUIRE(a && a->ids && a->labels && a->lens && a->embed_table && a->out, "ovla_language_average_ragged: null pointer");
+  OVLA_REQUIRE(a->B > 0 && a->L > 0 && a->D > 0 && a->vocab > 0, "ovla_language_average_ragged: bad shape B=%d L=%d D=%d vocab=%d", a->B, a->L, a->D, a->vocab);
+  hipLaunchKernelGGL(language_average_ragged_kernel, dim3(cdiv(a->D, 256), a->B), dim3(256), 0, stream, a->ids, a->labels, a->lens,
+                     (const bf16_bits*)a->embed_table, (bf16_bits*)a->out, a->L, a->D, a->vocab, a->action_token_begin);
+  OVLA_CHECK_LAUNCH("ovla_language_average_ragged");
   return OVLA_OK;
 }
 extern "C" int ovla_assemble_multimodal(const ovla_assemble_args* a, void* stream_) {

@@ -471,7 +471,71 @@ __global__ __launch_bounds__(256) void token_ce_kernel(const bf16_bits* __restri
     }
   }
 }
+
+// Greedy decode of the discrete action tokens: one workgroup per row, token = lowest index of the row maximum over [0, vocab) (token_ce_kernel's
+// tie rule), bin = clip(n_tokens - token - 1, 0, n_bins - 1).  VEC: 16-byte loads of whole 8-column groups inside [0, vocab), the vocab % 8 tail
+// column by column; columns [vocab, ld) are never loaded.  `v == m && j < mi` also gives an all -inf row its column 0.
+template <bool VEC>
+__global__ __launch_bounds__(256) void argmax_bins_kernel(const bf16_bits* __restrict__ logits, int64_t ld, int* __restrict__ token_out,
+                                                          int* __restrict__ bin_out, int vocab, int n_tokens, int n_bins) {
+  __shared__ float red_f[4];
+  __shared__ int red_i[4];
+  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const bf16_bits* x = logits + (int64_t)row * ld;
+  float m = -INFINITY; int mi = 0x7fffffff;
+  int tail0 = 0;
+  if (VEC) {
+    const int ngroups = vocab >> 3;
+    const uint4* xv = reinterpret_cast<const uint4*>(x);
+    for (int g = tid; g < ngroups; g += 256) {
+      const uint4 q = xv[g];
+      const uint32_t w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const float v = bf2f((bf16_bits)((k & 1) ? (w[k >> 1] >> 16) : (w[k >> 1] & 0xffffu)));
+        const int j = g * 8 + k;
+        if (v > m || (v == m && j < mi)) { m = v; mi = j; }
+      }
+    }
+    tail0 = ngroups << 3;
+  }
+  for (int j = tail0 + tid; j < vocab; j += 256) {
+    const float v = bf2f(x[j]);
+    if (v > m || (v == m && j < mi)) { m = v; mi = j; }
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    const float om = __shfl_xor(m, off); const int oi = __shfl_xor(mi, off);
+    if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
+  }
+  if (lane == 0) { red_f[wave] = m; red_i[wave] = mi; }
+  __syncthreads();
+  if (tid == 0) {
+    float bm = red_f[0]; int bi = red_i[0];
+    for (int w = 1; w < 4; ++w) if (red_f[w] > bm || (red_f[w] == bm && red_i[w] < bi)) { bm = red_f[w]; bi = red_i[w]; }
+    bi = bi >= vocab ? 0 : bi;                 // (a row of NaNs: no column ever compared greater or equal)
+    int d = n_tokens - bi - 1;
+    d = d < 0 ? 0 : (d > n_bins - 1 ? n_bins - 1 : d);
+    token_out[row] = bi;
+    bin_out[row] = d;
+  }
+}
 }  // namespace
+
+extern "C" int ovla_argmax_bins(const ovla_argmax_bins_args* a, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  OVLA_REQUIRE(a && a->logits && a->token && a->bin, "ovla_argmax_bins: null pointer");
+  OVLA_REQUIRE(a->rows > 0 && a->vocab > 0 && a->ld >= a->vocab && a->n_tokens > 0 && a->n_bins > 0, "ovla_argmax_bins: rows=%d vocab=%d ld=%lld n_tokens=%d n_bins=%d",
+               a->rows, a->vocab, (long long)a->ld, a->n_tokens, a->n_bins);
+  const bool vec = aligned16(a->logits) && (a->ld % 8) == 0;   // every row then starts on a 16-byte boundary
+  if (vec)
+    hipLaunchKernelGGL(argmax_bins_kernel<true>, dim3(a->rows), dim3(256), 0, stream, (const bf16_bits*)a->logits, a->ld, a->token, a->bin, a->vocab,
+                       a->n_tokens, a->n_bins);
+  else
+    hipLaunchKernelGGL(argmax_bins_kernel<false>, dim3(a->rows), dim3(256), 0, stream, (const bf16_bits*)a->logits, a->ld, a->token, a->bin, a->vocab,
+                       a->n_tokens, a->n_bins);
+  OVLA_CHECK_LAUNCH("ovla_argmax_bins");
+  return OVLA_OK;
+}
 
 extern "C" int ovla_token_ce(const ovla_token_ce_args* a, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;

@@ -1379,13 +1379,26 @@ class ChunkGraph:
 
     Everything the capture allocates (activations, split-K workspaces) lives in the graph's private pool and stays valid as
     long as this object does.  Text length L is part of the captured shapes: callers pad the prompt to a bucket (right
-    padding is masked exactly: padded keys contribute exact zeros) or keep one ChunkGraph per L."""
+    padding is masked exactly: padded keys contribute exact zeros) or keep one ChunkGraph per L.
+
+    `film=True` (a FiLM engine, right-padded batch): the conditioning vectors come from ONE ragged launch over the static ids / labels / lengths
+    (ovla_language_average_ragged: row b averages its own lens[b] tokens, pad tokens never enter), inside the graph.  Without it a FiLM engine
+    averages over all L positions, which is the reference's rule for an unpadded prompt (predict_action).
+    `discrete=True` (no action head, engine.lm_head present): the graph goes on to the lm_head GEMM on the action rows and the greedy decode
+    (ovla_argmax_bins); replay() then returns (None, action hidden, token int32 [B*A], bin int32 [B*A])."""
 
     def __init__(self, engine: "VLAEngine", B: int, L: int, pixel_shape, *, head=None, use_proprio: bool = True, proprio_projector=None,
-                 invariant: bool = False):
+                 invariant: bool = False, film: bool = False, discrete: bool = False, n_tokens: Optional[int] = None, n_bins: Optional[int] = None):
         dev = engine.device
         self.engine, self.head, self.B, self.L = engine, head, B, L
         self.invariant = invariant   # capture every GEMM under its fixed schedule (ops.batch_invariant): the batched inference API
+        if film and not engine.use_film:
+            raise ValueError("ChunkGraph(film=True) needs an engine built with use_film=True")
+        if discrete and (head is not None or engine.lm_head is None):
+            raise ValueError("ChunkGraph(discrete=True) is the token path: no action head, and the checkpoint's lm_head must be loaded")
+        self.film, self.discrete = film, discrete
+        self.n_tokens = n_tokens if n_tokens is not None else engine.cfg.vocab - engine.cfg.pad_to_multiple_of   # modeling_prismatic.py:732
+        self.n_bins = n_bins if n_bins is not None else engine.cfg.n_action_bins - 1                              # bin_centers.shape[0]
         self.proprio_projector = proprio_projector
         self.ids = torch.zeros((B, L), dtype=torch.int64, device=dev)
         self.lab = torch.full((B, L), -100, dtype=torch.int64, device=dev)
@@ -1397,11 +1410,22 @@ class ChunkGraph:
 
     def _run(self):
         eng = self.engine
+        D = eng.cfg.llm_dim
         with ops.batch_invariant(self.invariant):
+            film_avg = None
+            if self.film:
+                film_avg = torch.zeros(((self.B + 7) // 8 * 8, D), dtype=BF16, device=eng.device)
+                ops.language_average_ragged(self.ids, self.lab, self.lens, eng.embed, film_avg)
             out = eng.forward_dev(self.ids, self.lab, self.lens, self.pixels, proprio=self.proprio, train=False,
-                                  proprio_projector=self.proprio_projector, sel="actions")
+                                  proprio_projector=self.proprio_projector, sel="actions", film_avg=film_avg)
             ah, _ = eng.action_hidden(out)
             pred = self.head.fwd(ah)[0] if self.head is not None else None
+            if self.discrete:   # modeling.logits_for's row padding and GEMM, then the decode on the bf16 logits
+                n = ah.shape[0]
+                rows = torch.zeros(((n + 7) // 8 * 8, D), dtype=BF16, device=eng.device)
+                rows[:n] = ah
+                tok, bins = ops.argmax_bins(ops.gemm(rows, eng.lm_head)[:n], n_tokens=self.n_tokens, n_bins=self.n_bins)
+                return pred, ah, tok, bins
         return pred, ah
 
     def load(self, input_ids, attention_mask, pixel_values, labels, proprio=None):

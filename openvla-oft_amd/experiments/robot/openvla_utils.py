@@ -222,10 +222,12 @@ def device_pixel_values_batch(per_obs: List[List[np.ndarray]], cfg: Any) -> torc
 
 
 def get_vla_action_batch(cfg: Any, vla, processor: Any, observations: List[Dict[str, Any]], task_labels: List[str], action_head=None,
-                         proprio_projector=None, noisy_action_projector=None, use_film: bool = False, noise=None) -> List[List[np.ndarray]]:
+                         proprio_projector=None, noisy_action_projector=None, use_film: bool = False, noise=None,
+                         pad_to: Optional[int] = None) -> List[List[np.ndarray]]:
     """get_vla_action for B observations in one batched forward (OpenVLAForActionPrediction.predict_action_batch): per observation the same
     semantics -- including the in-place normalisation of obs["state"] -- and one list of num_open_loop_steps actions per observation.  On the
-    device image path all B * I frames go through device_pixel_values together (one launch per stage)."""
+    device image path all B * I frames go through device_pixel_values together (one launch per stage).  `pad_to`: predict_action_batch's
+    (the forward runs at that batch size on a repeated observation 0; B results come back)."""
     if len(observations) != len(task_labels):
         raise ValueError(f"get_vla_action_batch: {len(observations)} observations but {len(task_labels)} task labels")
     if not observations:
@@ -261,8 +263,8 @@ def get_vla_action_batch(cfg: Any, vla, processor: Any, observations: List[Dict[
                 obs["state"] = normalize_proprio(obs["state"], vla.norm_stats[cfg.unnorm_key]["proprio"])
             proprio = np.stack([np.asarray(obs["state"]) for obs in observations])
         if action_head is None:
-            actions, _ = vla.predict_action_batch(batch, pixel_values, unnorm_key=cfg.unnorm_key)
+            actions, _ = vla.predict_action_batch(batch, pixel_values, unnorm_key=cfg.unnorm_key, pad_to=pad_to)
         else:
             actions, _ = vla.predict_action_batch(batch, pixel_values, unnorm_key=cfg.unnorm_key, proprio=proprio, proprio_projector=proprio_projector,
-                                                  noisy_action_projector=noisy_action_projector, action_head=action_head, use_film=use_film, noise=noise)
+                                                  noisy_action_projector=noisy_action_projector, action_head=action_head, use_film=use_film, noise=noise, pad_to=pad_to)
     return [[a[i] for i in range(min(len(a), cfg.num_open_loop_steps))] for a in actions]

@@ -386,7 +386,9 @@ class OpenVLAForActionPrediction(_StoreModule):
         # buffers it was captured with, so it is for deployment (weights frozen), not for evaluation inside a training loop.
         self.use_graph = os.environ.get("OVLA_INFER_GRAPH", "0") == "1"
         self._graphs: Dict[tuple, ChunkGraph] = {}
-        self.max_batch_graphs = 8   # predict_action_batch: captured graphs kept per (B, bucket, ...), least recently used evicted first
+        # predict_action_batch: captured graphs kept per (B, text bucket, ...), least recently used evicted first.  A coalescing server raises it to
+        # 4 text-length buckets per batch bucket (deploy.OpenVLAServer), so that prompts of varied length do not thrash captures.
+        self.max_batch_graphs = 8
 
     def merge_and_unload(self):
         """peft `merge_and_unload()` of merge_lora_weights_and_save.py:60-67 on device: W += (alpha/r) B A for every adapted
@@ -523,12 +525,15 @@ class OpenVLAForActionPrediction(_StoreModule):
     # -- batched inference (not in the reference: its predict_action asserts batch size 1) -----------------------------------------------
     @torch.no_grad()
     def predict_action_batch(self, prompts, pixel_values, unnorm_key=None, proprio=None, proprio_projector=None, action_head=None,
-                             noisy_action_projector=None, use_film: bool = False, noise=None):
+                             noisy_action_projector=None, use_film: bool = False, noise=None, pad_to: Optional[int] = None):
         """predict_action for B observations in one forward.  prompts: list of B (input_ids, attention_mask) pairs ([1, L_b] or [L_b], lengths may
         differ; masks right-padded), pixel_values [B, 6 I, H, W], proprio [B, proprio_dim], noise [B, chunk, action_dim] (diffusion: each sample's
         DDIM trajectory starts from its own noise).  Returns (actions [B, chunk, action_dim] unnormalised with `unnorm_key`, action hidden states
         [B, A, D]).  Every GEMM runs under its fixed schedule (ops.batch_invariant), so each observation's outputs are the same bits whatever else
-        is in the batch and in whatever order (OVLA_BATCH_INVARIANT=0: the planner's schedules, for A/B measurement only)."""
+        is in the batch and in whatever order (OVLA_BATCH_INVARIANT=0: the planner's schedules, for A/B measurement only).
+        `pad_to` > B: the batch is filled to `pad_to` observations by repeating observation 0 (valid data, never zeros) and the extra outputs are
+        dropped -- the same bits for the B real ones, and a caller with arbitrary arrival counts (the coalescing server) captures one graph per
+        bucket instead of one per count."""
         cfg = self.cfg
         if use_film != self.engine.use_film:
             raise ValueError(f"use_film={use_film} but the model was built with use_film={self.engine.use_film}")
@@ -537,6 +542,23 @@ class OpenVLAForActionPrediction(_StoreModule):
             raise ValueError("predict_action_batch: no observations")
         if pixel_values.shape[0] != B:
             raise ValueError(f"predict_action_batch: {B} prompts but pixel_values holds {pixel_values.shape[0]} observations")
+        if pad_to is not None and pad_to > B:
+            fill = [0] * (pad_to - B)
+
+            def rep(t):   # [B, ...] -> [pad_to, ...]: observation 0 repeated behind the real ones
+                if t is None:
+                    return None
+                t = t if torch.is_tensor(t) else torch.as_tensor(np.asarray(t))
+                if t.shape[0] != B:
+                    raise ValueError(f"predict_action_batch: a per-observation input holds {t.shape[0]} rows for {B} observations")
+                return torch.cat([t, t[fill]])
+
+            prop_p = rep(proprio)
+            actions, hidden = self.predict_action_batch(list(prompts) + [prompts[0]] * len(fill), rep(pixel_values), unnorm_key=unnorm_key,
+                                                        proprio=None if prop_p is None else prop_p.cpu().numpy(), proprio_projector=proprio_projector,
+                                                        action_head=action_head, noisy_action_projector=noisy_action_projector, use_film=use_film,
+                                                        noise=rep(noise))
+            return actions[:B], hidden[:B]
         use_proprio = proprio_projector is not None and proprio is not None
         prop = None
         if use_proprio:
@@ -566,13 +588,14 @@ class OpenVLAForActionPrediction(_StoreModule):
             ids[b, : len(r)], mask[b, : len(r)] = r, True
             labels[b, len(r) - A - 1: len(r)] = ACTION_TOKEN_BEGIN_IDX + 1
             labels[b, len(r) - 1] = STOP_INDEX
-        film_avg = None
-        if self.engine.use_film:   # FiLM's language average over each prompt's OWN tokens (padding would enter the mean: film_vit_wrapper.py:243)
+        film, film_avg = self.engine.use_film, None
+        graphed = self.use_graph and not use_diffusion
+        if film and not graphed:
+            # FiLM's language average over each prompt's OWN tokens (padding would enter the mean: film_vit_wrapper.py:243): one ragged launch
+            # for the batch, bit for bit ovla_language_average on each unpadded row.  (Under graph replay the launch is part of the graph.)
             film_avg = torch.zeros(((B + 7) // 8 * 8, D), dtype=BF16, device=self.device)
-            for b, r in enumerate(rows):
-                rid = r[None].to(self.device)
-                rlab = labels[b: b + 1, : len(r)].to(self.device)
-                ops.language_average(rid, rlab, self.engine.embed, film_avg[b: b + 1])
+            ops.language_average_ragged(ids.to(self.device), labels.to(self.device), torch.tensor([len(r) for r in rows], dtype=torch.int32).to(self.device),
+                                        self.engine.embed, film_avg)
         pp_comp = proprio_projector.comp if use_proprio else None
         with ops.batch_invariant(ops.BATCH_INVARIANT_DEFAULT):
             if use_diffusion:                                                                 # :793-877, per sample
@@ -595,18 +618,24 @@ class OpenVLAForActionPrediction(_StoreModule):
                 hidden = ah.view(B, A, D).clone()
             else:
                 head_comp = getattr(action_head, "comp", None) if action_head is not None else None
-                if self.use_graph and film_avg is None:
-                    key = ("batch", B, Lb, tuple(pixel_values.shape), id(head_comp), id(pp_comp), ops.BATCH_INVARIANT_DEFAULT)
+                discrete = action_head is None
+                bins = None
+                if graphed:
+                    key = ("batch", B, Lb, tuple(pixel_values.shape), id(head_comp), id(pp_comp), ops.BATCH_INVARIANT_DEFAULT, film, discrete)
                     g = self._graphs.pop(key, None)
                     if g is None:
                         batched = [k for k in self._graphs if k[0] == "batch"]
                         if len(batched) >= self.max_batch_graphs:   # B and the bucket come from callers (/act_batch): keep the most recent few
                             del self._graphs[batched[0]]
                         g = ChunkGraph(self.engine, B, Lb, pixel_values.shape, head=head_comp, use_proprio=use_proprio, proprio_projector=pp_comp,
-                                       invariant=ops.BATCH_INVARIANT_DEFAULT)
+                                       invariant=ops.BATCH_INVARIANT_DEFAULT, film=film, discrete=discrete, n_tokens=self.vocab_size,
+                                       n_bins=self.bin_centers.shape[0])
                         g._keep = (head_comp, pp_comp)
                     self._graphs[key] = g   # (re)inserted last: dict order is least recently used first
-                    pred, ah = g(ids, mask, pixel_values, labels, prop)
+                    res = g(ids, mask, pixel_values, labels, prop)
+                    pred, ah = res[0], res[1]
+                    if discrete:            # lm_head GEMM + ovla_argmax_bins ran inside the graph: only the bin indices come back
+                        bins = res[3].cpu().numpy().astype(np.int64)
                     hidden = ah.view(B, A, D).clone()
                     pred = pred.clone() if pred is not None else None
                 else:
@@ -617,6 +646,8 @@ class OpenVLAForActionPrediction(_StoreModule):
                     pred = action_head.predict_action(hidden) if action_head is not None else None
                 if action_head is not None:
                     normalized = pred.reshape(B, cfg.chunk, cfg.action_dim).float().cpu().numpy()
+                elif bins is not None:
+                    normalized = self.bin_centers[bins].reshape(B, cfg.chunk, cfg.action_dim)
                 else:
                     tok = self.logits_for(hidden.view(B * A, D)).argmax(dim=1).cpu().numpy()
                     d = np.clip(self.vocab_size - tok - 1, a_min=0, a_max=self.bin_centers.shape[0] - 1)

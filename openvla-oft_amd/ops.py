@@ -590,6 +590,20 @@ def language_average(ids, labels, table, out, *, action_token_begin=31743):
     return out
 
 
+def language_average_ragged(ids, labels, lens, table, out, *, action_token_begin=31743):
+    """language_average of a right-padded batch in one launch (ovla.h: ovla_language_average_ragged): row b averages positions i < lens[b]
+    only; out[b] is bit for bit language_average(ids[b:b+1, :lens[b]], labels[b:b+1, :lens[b]]).  lens int32 [B] on the device, each in [1, L]."""
+    B, L = ids.shape
+    assert ids.dtype == torch.int64 and labels.dtype == torch.int64 and ids.is_contiguous() and labels.is_contiguous() and ids.is_cuda and labels.is_cuda
+    assert labels.shape == ids.shape and lens.dtype == torch.int32 and lens.numel() == B and lens.is_contiguous() and lens.is_cuda
+    assert out.shape[0] >= B and out.shape[1] == table.shape[1] and out.is_contiguous()
+    g = STRUCTS["ovla_language_average_ragged_args"]()
+    g.ids, g.labels, g.lens, g.embed_table, g.out = ids.data_ptr(), labels.data_ptr(), lens.data_ptr(), table.data_ptr(), out.data_ptr()
+    g.B, g.L, g.D, g.vocab, g.action_token_begin = B, L, table.shape[1], table.shape[0], action_token_begin
+    _lib.call("ovla_language_average_ragged", g, _stream())
+    return out
+
+
 def image_prep(images_u8, *, crop: bool, crop_scale: float = 0.9, out_size: int = 224,
                mean=(0.485, 0.456, 0.406, 0.5, 0.5, 0.5), std=(0.229, 0.224, 0.225, 0.5, 0.5, 0.5)):
     """uint8 [n_img, H, W, 3] (device) -> bf16 [1, 6 * n_img, out, out] pixel_values: center crop (TF crop_and_resize rule) +
@@ -715,6 +729,23 @@ def token_ce(logits, targets, *, vocab=None, grad_scale=None, inplace_grad=True)
     g.rows, g.vocab, g.grad_scale = rows, vocab, float(grad_scale or 0.0)
     _lib.call("ovla_token_ce", g, _stream())
     return loss_rows, amax, d
+
+
+def argmax_bins(logits, *, n_tokens, n_bins, vocab=None, token=None, bins=None):
+    """Greedy action-token decode (ovla.h: ovla_argmax_bins): logits bf16 [rows, ld >= vocab] -> (token int32 [rows] = lowest index of the row
+    maximum over [0, vocab), bin int32 [rows] = clip(n_tokens - token - 1, 0, n_bins - 1))."""
+    _chk(logits, name="logits")
+    assert logits.dim() == 2 and logits.stride(1) == 1
+    rows = logits.shape[0]
+    vocab = logits.shape[1] if vocab is None else vocab
+    token = torch.empty(rows, dtype=torch.int32, device=logits.device) if token is None else token
+    bins = torch.empty(rows, dtype=torch.int32, device=logits.device) if bins is None else bins
+    assert token.dtype == torch.int32 and bins.dtype == torch.int32 and token.numel() == rows and bins.numel() == rows
+    g = STRUCTS["ovla_argmax_bins_args"]()
+    g.logits, g.ld, g.token, g.bin = logits.data_ptr(), logits.stride(0), token.data_ptr(), bins.data_ptr()
+    g.rows, g.vocab, g.n_tokens, g.n_bins = rows, vocab, n_tokens, n_bins
+    _lib.call("ovla_argmax_bins", g, _stream())
+    return token, bins
 
 
 def head_out_fwd(x, W, b, target=None, loss_sum=None, mse=False):

@@ -9,7 +9,12 @@ Differences, all deliberate:
     the "encoded" double-encoding of deploy.py:80-95 (whole payload as ONE json string under the key "encoded") is kept;
   * components can be handed in already built (tests; no checkpoint exists offline), otherwise they are loaded exactly like the
     reference does (get_vla / get_action_head / get_proprio_projector / get_processor);
-  * merged LoRA weights + hipGraph replay are switched on (`vla.enable_graph_replay()`): the deployment configuration of DESIGN.md §6.
+  * merged LoRA weights + hipGraph replay are switched on (`vla.enable_graph_replay()`): the deployment configuration of DESIGN.md §6;
+  * `coalesce_ms > 0` (not in the reference): independent `/act` callers that arrive within that window share ONE batched forward
+    (`RequestCoalescer` -> `get_vla_action_batch`, padded to a bucket of `batch_buckets`).  Batch invariance is what makes that safe: a
+    coalesced `/act` answer is bit-identical to `/act_batch([payload])` -- the fixed-schedule batch path at B = 1 -- whatever it was merged
+    with.  It is NOT promised identical to the uncoalesced `/act`, which runs `predict_action` on the planner's schedules and is
+    unchanged.  At `coalesce_ms == 0` (the default) no coalescer exists and both endpoints behave exactly as before.
 """
 from __future__ import annotations
 
@@ -26,6 +31,7 @@ import numpy as np
 
 from ..experiments.robot import openvla_utils as U
 from ..prismatic.vla import constants as C
+from .coalescer import RequestCoalescer
 
 
 def encode_ndarray(a: np.ndarray) -> Dict[str, Any]:
@@ -86,6 +92,9 @@ class DeployConfig:
     load_in_4bit: bool = False
     seed: int = 7
     graph_replay: bool = True           # hipGraph replay of predict_action (not in the reference)
+    coalesce_ms: float = 0.0            # > 0: merge /act requests that arrive within this window into one batched forward (not in the reference)
+    max_batch: int = 8                  # most requests merged into one forward
+    batch_buckets: tuple = (1, 2, 4, 8)  # a merged batch runs at the smallest of these that holds it: bounds the number of captured graphs
     # fmt: on
 
 
@@ -101,14 +110,66 @@ class OpenVLAServer:
             self.action_head = U.get_action_head(cfg, self.vla.llm_dim)
         assert cfg.unnorm_key in self.vla.norm_stats, f"Action un-norm key {cfg.unnorm_key} not found in VLA `norm_stats`!"
         self.processor = processor if processor is not None else U.get_processor(cfg)
-        if getattr(cfg, "graph_replay", True) and not cfg.use_diffusion and not cfg.use_film:
+        if getattr(cfg, "graph_replay", True) and not cfg.use_diffusion:   # (the diffusion sampler is a host loop: coalesced, but eager)
             self.vla.enable_graph_replay(True)
         self._lock = threading.Lock()
+        self._coalescer = None
+        if getattr(cfg, "coalesce_ms", 0.0) > 0:
+            buckets = tuple(getattr(cfg, "batch_buckets", (1, 2, 4, 8)))
+            # one captured graph per (batch bucket, 8-token text-length bucket): room for 4 text buckets per batch bucket before the least
+            # recently used graph is evicted and recaptured (task prompts of varied length would otherwise thrash captures)
+            self.vla.max_batch_graphs = max(getattr(self.vla, "max_batch_graphs", 8), 4 * len(buckets))
+            self._coalescer = RequestCoalescer(self._run_batch, coalesce_ms=cfg.coalesce_ms, max_batch=getattr(cfg, "max_batch", 8), buckets=buckets)
+
+    # -- coalescing mode: the worker thread of self._coalescer is the only thread that touches the engine ---------------------------------
+    def _proprio_dim(self) -> Optional[int]:
+        """Length of the state vector the un-normalisation statistics are for (None: the checkpoint carries none, nothing to compare with)."""
+        stats = self.vla.norm_stats.get(self.cfg.unnorm_key, {}).get("proprio")
+        for k in ("q01", "min", "q99", "max"):
+            if stats and k in stats:
+                return len(stats[k])
+        return None
+
+    def _decode_valid(self, payload):
+        """Decodes and validates one payload on the request thread, so that a malformed request never enters a batch.  The request contract
+        in coalescing mode (`/act` and every element of `/act_batch`): an 'instruction' string, a 'full_image' H x W x 3 array, and with
+        use_proprio a numeric 1-D 'state' of the length of the checkpoint's proprio statistics."""
+        observation, double = decode_payload(payload)
+        if not isinstance(observation, dict) or not isinstance(observation.get("instruction"), str):
+            raise ValueError("the payload needs an 'instruction' string")
+        image = observation.get("full_image")
+        if not isinstance(image, np.ndarray) or image.ndim != 3 or image.shape[-1] != 3:
+            raise ValueError("the payload needs a 'full_image' array of shape [H, W, 3]")
+        if self.cfg.use_proprio:
+            if "state" not in observation:
+                raise ValueError("the payload needs a 'state' array (use_proprio)")
+            state = np.asarray(observation["state"])
+            want = self._proprio_dim()
+            if state.ndim != 1 or state.dtype.kind not in "fiu" or (want is not None and state.shape[0] != want):
+                raise ValueError(f"'state' must be a numeric vector of length {want}, got dtype {state.dtype} shape {state.shape}")
+        return observation, double
+
+    def _run_batch(self, items, pad_to):
+        """RequestCoalescer's batch_fn: decoded (observation, double_encoded) pairs -> their encoded answers, from one forward at `pad_to`.
+        Idempotent: get_vla_action_batch normalises obs["state"] IN PLACE before the forward can fail, and the coalescer re-runs the members of
+        a failed batch one by one -- so it gets shallow copies, and a retried member starts from the state its caller sent."""
+        observations = [dict(o) for o, _ in items]
+        actions = U.get_vla_action_batch(self.cfg, self.vla, self.processor, observations, [o["instruction"] for o in observations],
+                                         action_head=self.action_head, proprio_projector=self.proprio_projector, use_film=self.cfg.use_film,
+                                         pad_to=pad_to)
+        return [json.dumps(_encode(a)) if double else _encode(a) for a, (_, double) in zip(actions, items)]
+
+    def close(self) -> None:
+        """Drains and stops the coalescer's worker (a no-op at coalesce_ms == 0)."""
+        if self._coalescer is not None:
+            self._coalescer.close()
 
     def act(self, payload: Dict[str, Any]):
         """The body of `/act` without the HTTP layer: returns a list of actions (ndarrays), or the json_numpy-encoded string
         for a double-encoded request, or "error" (deploy.py:78-107)."""
         try:
+            if self._coalescer is not None:
+                return self._coalescer.submit(self._decode_valid(payload))
             observation, double = decode_payload(payload)
             instruction = observation["instruction"]
             with self._lock:      # one engine, static graph buffers: serialise (the reference does not lock)
@@ -127,6 +188,8 @@ class OpenVLAServer:
         try:
             if not isinstance(payloads, list) or not payloads:
                 raise ValueError("/act_batch takes a non-empty list of observation payloads")
+            if self._coalescer is not None:   # through the same worker, as one pre-formed group
+                return self._coalescer.submit_group([self._decode_valid(p) for p in payloads])
             decoded = [decode_payload(p) for p in payloads]
             observations = [o for o, _ in decoded]
             instructions = [o["instruction"] for o in observations]
@@ -159,7 +222,10 @@ class OpenVLAServer:
     def run(self, host: str = "0.0.0.0", port: int = 8777) -> None:
         import uvicorn
 
-        uvicorn.run(self.build_app(), host=host, port=port)
+        try:
+            uvicorn.run(self.build_app(), host=host, port=port)
+        finally:
+            self.close()   # coalescing mode: requests still queued at shutdown are answered, then the worker is joined
 
 
 def deploy(cfg: DeployConfig) -> None:
