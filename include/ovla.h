@@ -523,6 +523,25 @@ typedef struct {
 } ovla_adamw_args;
 int ovla_adamw(const ovla_adamw_args* a, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * DDIM sampling on the device (prismatic/extern/hf/modeling_prismatic.py:793-877 `_run_diffusion_prediction`: per step, timestep
+ * embedding + noisy actions in, `noise_scheduler.step(noise_pred, t, curr_noisy_actions).prev_sample` out).  The loop's step index k is a
+ * DEVICE int32 that both kernels read and ovla_ddim_step advances, so one sampling step has no host-dependent argument and can be replayed
+ * from a captured graph; k outside [0, n_steps) makes either kernel a no-op.
+ *
+ * ovla_ddim_prepare, top of step k: temb[b, :] = temb_table[k, :] for b < B (the timestep token of each observation; temb_table bf16
+ * [n_steps, D] is the host's time_encoder(t_k) rounded to bf16) and noisy[i] = bf16(sample[i]), i < n (the noisy-action projector's input). */
+typedef struct { const int32_t* step; const void* temb_table; void* temb; const float* sample; void* noisy; int32_t n_steps, B, D, n; } ovla_ddim_prepare_args;
+int ovla_ddim_prepare(const ovla_ddim_prepare_args* a, void* stream);
+/* ovla_ddim_step, end of step k: diffusers' DDIMScheduler.step for epsilon prediction with clip_sample and eta = 0, then the sampler's
+ * bf16 round trip, in place on sample fp32 [n] with eps bf16 [n] (the head's output) and coef fp32 [n_steps, 4], row k =
+ * ((1 - a_t)^1/2, a_t^1/2, a_prev^1/2, (1 - a_prev)^1/2) built by the host with the scheduler's own expressions:
+ *     x0 = clamp((s - c0 e) / c1, -1, 1);   e' = (s - c1 x0) / c0;   s <- float(bf16(c2 x0 + c3 e'))
+ * Every multiply / subtract / divide / add is rounded on its own (no FMA contraction, correctly rounded division): bit-identical to the CPU
+ * torch expression.  One workgroup; *step becomes k + 1 once every element has been written. */
+typedef struct { float* sample; const void* eps; const float* coef; int32_t* step; int32_t n_steps, n; } ovla_ddim_step_args;
+int ovla_ddim_step(const ovla_ddim_step_args* a, void* stream);
+
 /* fp32 -> bf16 convert with scale (publishes .grad views), and fill */
 typedef struct { const float* src; void* dst; int64_t n; float scale; } ovla_cvt_args;
 int ovla_cvt_f32_to_bf16(const ovla_cvt_args* a, void* stream);

@@ -56,6 +56,19 @@ class DDIMScheduler:
         return SimpleNamespace(prev_sample=a_prev ** 0.5 * x0 + (1 - a_prev) ** 0.5 * eps)
 
 
+    def step_coefficients(self) -> torch.Tensor:
+        """fp32 [len(timesteps), 4]: per sampling step the four scalars `step` multiplies and divides by, ((1 - a_t)^1/2, a_t^1/2, a_prev^1/2,
+        (1 - a_prev)^1/2), from the very expressions of `step` -- the table ovla_ddim_step reads (ops.ddim_step)."""
+        rows = []
+        for t in self.timesteps:
+            t = int(t)
+            prev_t = t - self.config.num_train_timesteps // self.num_inference_steps
+            a_t = self.alphas_cumprod[t]
+            a_prev = self.alphas_cumprod[prev_t] if prev_t >= 0 else self.final_alpha_cumprod
+            rows.append(torch.stack([(1 - a_t) ** 0.5, a_t ** 0.5, a_prev ** 0.5, (1 - a_prev) ** 0.5]))
+        return torch.stack(rows).to(torch.float32).contiguous()
+
+
 class SinusoidalPositionalEncoding:
     def __init__(self, dim: int):
         self.dim = dim

@@ -1160,6 +1160,27 @@ class VLAEngine:
             raise ValueError("attention_mask must be right padding (a prefix of ones per row), as produced by the reference collator")
         return lens
 
+    def patches_dev(self, ids, lab, pixel_values, proprio, proprio_projector, film_avg, train):
+        """The step-independent front of forward_dev: FiLM average (unless given), both towers, the projector and the proprio token ->
+        (base bf16 [B, n_vis (+ 1), D], n_vis, vision saved, proprio saved).  (base, n_vis) is forward_dev's `cached_patches`: the DDIM
+        sampler computes it once per chunk (DiffusionGraph's prefix capture)."""
+        cfg, dev = self.cfg, self.device
+        B = ids.shape[0]
+        psaved = None
+        if self.use_film and film_avg is None:
+            film_avg = self.language_average(ids, lab)
+        patches, vsaved = self.vision_fwd(pixel_values.to(dev, BF16).contiguous(), train, film_avg)
+        n_vis = patches.shape[1]
+        base = patches
+        if proprio is not None and proprio_projector is not None:
+            pr = torch.zeros(((B + 7) // 8 * 8, cfg.proprio_dim), dtype=BF16, device=dev)
+            pr[:B] = proprio.reshape(B, -1).to(dev, BF16)
+            pf, psaved = proprio_projector.fwd(pr, train)
+            base = torch.empty((B, n_vis + 1, cfg.llm_dim), dtype=BF16, device=dev)   # token concat (pure data movement)
+            base[:, :n_vis] = patches
+            base[:, n_vis] = pf[:B]
+        return base, n_vis, vsaved, psaved
+
     def forward_dev(self, ids, lab, text_lens, pixel_values, proprio=None, noisy_actions=None, timestep_emb=None, train=False,
                     proprio_projector=None, noisy_action_projector=None, cached_patches=None, film_avg=None, sel=None):
         """Device-only part of forward(): ids / lab int64 [B, L] and text_lens int32 [B] already on the device; launches
@@ -1173,18 +1194,7 @@ class VLAEngine:
         if cached_patches is not None:
             base, n_vis = cached_patches
         else:
-            if self.use_film and film_avg is None:
-                film_avg = self.language_average(ids, lab)
-            patches, vsaved = self.vision_fwd(pixel_values.to(dev, BF16).contiguous(), train, film_avg)
-            n_vis = patches.shape[1]
-            base = patches
-            if proprio is not None and proprio_projector is not None:
-                pr = torch.zeros(((B + 7) // 8 * 8, cfg.proprio_dim), dtype=BF16, device=dev)
-                pr[:B] = proprio.reshape(B, -1).to(dev, BF16)
-                pf, psaved = proprio_projector.fwd(pr, train)
-                base = torch.empty((B, n_vis + 1, cfg.llm_dim), dtype=BF16, device=dev)   # token concat (pure data movement)
-                base[:, :n_vis] = patches
-                base[:, n_vis] = pf[:B]
+            base, n_vis, vsaved, psaved = self.patches_dev(ids, lab, pixel_values, proprio, proprio_projector, film_avg, train)
         allp = base
         if timestep_emb is not None:
             allp = torch.empty((B, base.shape[1] + 1, cfg.llm_dim), dtype=BF16, device=dev)
@@ -1459,5 +1469,123 @@ class ChunkGraph:
     def __call__(self, input_ids, attention_mask, pixel_values, labels, proprio=None):
         self.load(input_ids, attention_mask, pixel_values, labels, proprio)
         if self.graph is None:
+            self.capture()
+        return self.replay()
+
+
+# ======================================================================================================================
+# hipGraph replay of the DDIM sampler (BASELINE.json configs[5]: FiLM + diffusion head)
+# ======================================================================================================================
+class DiffusionGraph:
+    """The diffusion head's sampling loop (modeling_prismatic.py:793-877) as TWO captures over static buffers, with no host work between the
+    steps:
+
+      prefix  once per chunk: the optional ragged FiLM average, both towers on their two streams, the projector and the proprio token
+              (VLAEngine.patches_dev) -> the static `patches` every step reuses (the reference caches them too, :810);
+      step    replayed n_steps times back to back: ovla_ddim_prepare (timestep token + bf16(sample) from the device step index) -> noisy-action
+              projector, assembly, Llama stack on the cached patches (forward_dev) -> action rows -> noise-predicting head -> ovla_ddim_step
+              (sample updated in place, step index advanced).
+
+    The host loop it replaces (OpenVLAForActionPrediction.predict_action / predict_action_batch with graph replay off) enqueues ~1.3 k
+    launches per step, then synchronises, steps the scheduler in CPU torch and uploads the sample again; both compute the same bits.
+    `coef` / `temb_table`: DDIMScheduler.step_coefficients() and the bf16 time_encoder rows of the scheduler's timesteps, one row per step.
+    `invariant` and `film` as in ChunkGraph.  `step_replays` counts the step graph's replays over the object's life."""
+
+    def __init__(self, engine: "VLAEngine", B: int, L: int, pixel_shape, *, head, noisy_action_projector, coef, temb_table,
+                 use_proprio: bool = True, proprio_projector=None, invariant: bool = False, film: bool = False):
+        dev, cfg = engine.device, engine.cfg
+        if film and not engine.use_film:
+            raise ValueError("DiffusionGraph(film=True) needs an engine built with use_film=True")
+        if head is None or noisy_action_projector is None:
+            raise ValueError("DiffusionGraph needs the noise-predicting head and the noisy-action projector")
+        self.engine, self.head, self.noisy_action_projector, self.proprio_projector = engine, head, noisy_action_projector, proprio_projector
+        self.B, self.L, self.invariant, self.film = B, L, invariant, film
+        self.n_steps = int(coef.shape[0])
+        if tuple(coef.shape) != (self.n_steps, 4) or tuple(temb_table.shape) != (self.n_steps, cfg.llm_dim):
+            raise ValueError(f"DiffusionGraph: coef {tuple(coef.shape)} / temb_table {tuple(temb_table.shape)} for {self.n_steps} steps, D = {cfg.llm_dim}")
+        self.coef = coef.to(dev, F32).contiguous()
+        self.temb_table = temb_table.to(dev, BF16).contiguous()
+        n = B * cfg.chunk * cfg.action_dim
+        self.ids = torch.zeros((B, L), dtype=torch.int64, device=dev)
+        self.lab = torch.full((B, L), -100, dtype=torch.int64, device=dev)
+        self.lens = torch.full((B,), L, dtype=torch.int32, device=dev)
+        self.pixels = torch.zeros(tuple(pixel_shape), dtype=BF16, device=dev)
+        self.proprio = torch.zeros((B, cfg.proprio_dim), dtype=BF16, device=dev) if use_proprio else None
+        self.sample = torch.zeros(n, dtype=F32, device=dev)           # the trajectory, bf16-rounded values held in fp32 (as the host loop holds them)
+        self.step = torch.zeros(1, dtype=torch.int32, device=dev)     # index into the scheduler's timesteps; n_steps = sampling finished
+        self.temb = torch.zeros((B, cfg.llm_dim), dtype=BF16, device=dev)
+        self.noisy = torch.zeros(n, dtype=BF16, device=dev)
+        self.prefix_graph = self.step_graph = None
+        self.patches = self.ah = None
+        self.step_replays = 0
+
+    def _run_prefix(self):
+        eng = self.engine
+        with ops.batch_invariant(self.invariant):
+            film_avg = None
+            if self.film:
+                film_avg = torch.zeros(((self.B + 7) // 8 * 8, eng.cfg.llm_dim), dtype=BF16, device=eng.device)
+                ops.language_average_ragged(self.ids, self.lab, self.lens, eng.embed, film_avg)
+            pp = self.proprio_projector if self.proprio_projector is not None else eng.proprio
+            base, n_vis, _, _ = eng.patches_dev(self.ids, self.lab, self.pixels, self.proprio, pp, film_avg, False)
+        return base, n_vis
+
+    def _run_step(self, patches):
+        eng = self.engine
+        with ops.batch_invariant(self.invariant):
+            ops.ddim_prepare(self.step, self.temb_table, self.temb, self.sample, self.noisy)
+            out = eng.forward_dev(self.ids, self.lab, self.lens, self.pixels, train=False, noisy_actions=self.noisy, timestep_emb=self.temb,
+                                  noisy_action_projector=self.noisy_action_projector, cached_patches=patches, sel="actions")
+            ah, _ = eng.action_hidden(out)
+            eps = self.head.fwd(ah)[0]
+            ops.ddim_step(self.sample, eps, self.coef, self.step)
+        return ah
+
+    def load(self, input_ids, attention_mask, pixel_values, labels, proprio, noise):
+        """noise: the start of the trajectory, fp32 [B, chunk, action_dim] already rounded through bf16."""
+        lens = VLAEngine.check_right_padding(attention_mask)
+        assert tuple(input_ids.shape) == (self.B, self.L), f"DiffusionGraph captured for ids {(self.B, self.L)}, got {tuple(input_ids.shape)}"
+        self.ids.copy_(input_ids.to(torch.int64), non_blocking=True)
+        self.lab.copy_(labels.to(torch.int64), non_blocking=True)
+        self.lens.copy_(lens.to(torch.int32), non_blocking=True)
+        self.pixels.copy_(pixel_values.reshape(self.pixels.shape), non_blocking=True)
+        if self.proprio is not None:
+            self.proprio.copy_(proprio.reshape(self.proprio.shape), non_blocking=True)
+        self.sample.copy_(noise.reshape(-1).to(F32), non_blocking=True)
+        self.step.zero_()
+
+    def capture(self):
+        """Call after load() of a representative input: one eager prefix + step as warm-up (lazy tables, kernel attributes), the loaded sample
+        and step index put back, then the two captures."""
+        assert ops.PROFILE is None, "no per-launch event timing inside a graph capture"
+        start = self.sample.clone()
+        self._run_step(self._run_prefix())
+        self.sample.copy_(start)
+        self.step.zero_()
+        torch.cuda.synchronize(self.engine.device)
+        outer_ws, ops._ws_cache = ops._ws_cache, {}          # workspaces allocated while capturing belong to the graphs' pools
+        try:
+            self.prefix_graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.prefix_graph):
+                self.patches = self._run_prefix()
+            self.step_graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.step_graph):
+                self.ah = self._run_step(self.patches)
+        finally:
+            self._ws, ops._ws_cache = ops._ws_cache, outer_ws
+        return self
+
+    def replay(self):
+        """-> (sample fp32 [B * chunk * action_dim] on the HOST, the last step's action hidden states bf16 [B * A, D] in a static device buffer).
+        The copy of the sample is the loop's only synchronisation."""
+        self.prefix_graph.replay()
+        for _ in range(self.n_steps):
+            self.step_graph.replay()
+        self.step_replays += self.n_steps
+        return self.sample.cpu(), self.ah
+
+    def __call__(self, input_ids, attention_mask, pixel_values, labels, proprio=None, noise=None):
+        self.load(input_ids, attention_mask, pixel_values, labels, proprio, noise)
+        if self.step_graph is None:
             self.capture()
         return self.replay()

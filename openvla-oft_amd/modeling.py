@@ -22,7 +22,7 @@ import torch.nn as nn
 from . import ops
 from .config import VLAConfig
 from .diffusion import DDIMScheduler, SinusoidalPositionalEncoding
-from .engine import ChunkGraph, ActionHead, MlpProjector, ParamStore, VLAEngine, build_component
+from .engine import ChunkGraph, DiffusionGraph, ActionHead, MlpProjector, ParamStore, VLAEngine, build_component
 from .weights import make_getter
 
 BF16 = torch.bfloat16
@@ -382,10 +382,10 @@ class OpenVLAForActionPrediction(_StoreModule):
         self.config = type("Cfg", (), {"image_sizes": [cfg.dino.image_size, cfg.siglip.image_size], "pad_token_id": cfg.pad_token_id})()
         self.training = False
         self._anchor = torch.zeros((), device=self.device, requires_grad=True)
-        # hipGraph replay of predict_action (L1 / discrete paths).  Off by default: a captured graph pins the parameter
-        # buffers it was captured with, so it is for deployment (weights frozen), not for evaluation inside a training loop.
+        # hipGraph replay of predict_action (L1 / discrete paths: ChunkGraph; diffusion head: DiffusionGraph).  Off by default: a captured graph
+        # pins the parameter buffers it was captured with, so it is for deployment (weights frozen), not for evaluation inside a training loop.
         self.use_graph = os.environ.get("OVLA_INFER_GRAPH", "0") == "1"
-        self._graphs: Dict[tuple, ChunkGraph] = {}
+        self._graphs: Dict[tuple, Any] = {}
         # predict_action_batch: captured graphs kept per (B, text bucket, ...), least recently used evicted first.  A coalescing server raises it to
         # 4 text-length buckets per batch bucket (deploy.OpenVLAServer), so that prompts of varied length do not thrash captures.
         self.max_batch_graphs = 8
@@ -451,6 +451,33 @@ class OpenVLAForActionPrediction(_StoreModule):
         rows[:n] = hidden_rows
         return ops.cvt_bf16_to_f32(ops.gemm(rows, self.engine.lm_head))[:n]
 
+    # -- graph replay of the DDIM sampler ---------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _ddim_tables(action_head):
+        """(coef fp32 [n_steps, 4], timestep embeddings bf16 [n_steps, D]) of the head's scheduler after set_timesteps: what the host loop
+        computes step by step (sched.step's scalars, time_encoder(float(t)).to(bf16)), as DiffusionGraph's two device tables."""
+        sched = action_head.noise_scheduler
+        temb = torch.cat([action_head.time_encoder(torch.tensor([float(t)])).to(BF16).reshape(1, -1) for t in sched.timesteps])
+        return sched.step_coefficients(), temb
+
+    def _diffusion_graph(self, key, B, L, pixel_shape, action_head, noisy_action_projector, pp_comp, use_proprio, *, invariant=False, film=False):
+        """The DiffusionGraph under `key` in self._graphs (captured on first use).  Batch keys follow predict_action_batch's LRU rule."""
+        g = self._graphs.pop(key, None)
+        if g is None:
+            if key[0] == "batch":
+                self._evict_batch_graph()
+            coef, temb = self._ddim_tables(action_head)
+            g = DiffusionGraph(self.engine, B, L, pixel_shape, head=action_head.comp, noisy_action_projector=noisy_action_projector.comp, coef=coef,
+                               temb_table=temb, use_proprio=use_proprio, proprio_projector=pp_comp, invariant=invariant, film=film)
+            g._keep = (action_head.comp, pp_comp, noisy_action_projector.comp)   # the captured kernels read these parameter buffers: keep them alive
+        self._graphs[key] = g   # (re)inserted last: dict order is least recently used first
+        return g
+
+    def _evict_batch_graph(self):
+        batched = [k for k in self._graphs if k[0] == "batch"]
+        if len(batched) >= self.max_batch_graphs:   # B and the bucket come from callers (/act_batch): keep the most recent few
+            del self._graphs[batched[0]]
+
     # -- predict_action (:946-1060) -------------------------------------------------------------------------------------
     @torch.no_grad()
     def predict_action(self, input_ids=None, unnorm_key=None, proprio=None, proprio_projector=None, action_head=None,
@@ -481,6 +508,15 @@ class OpenVLAForActionPrediction(_StoreModule):
             if cur is None:
                 cur = torch.randn((1, cfg.chunk, cfg.action_dim))
             cur = cur.to("cpu", torch.float32).to(BF16).float()
+            if self.use_graph:
+                # the whole loop from two captured graphs, no host work between the steps (engine.DiffusionGraph): same bits as the loop below
+                pp_comp = proprio_projector.comp if use_proprio else None
+                key = ("ddim", ids.shape[1], tuple(pixel_values.shape), id(action_head.comp), id(pp_comp), id(noisy_action_projector.comp),
+                       len(sched.timesteps), sched.config.num_train_timesteps)
+                g = self._diffusion_graph(key, 1, ids.shape[1], pixel_values.shape, action_head, noisy_action_projector, pp_comp, use_proprio)
+                sample, ah = g(ids, mask, pixel_values, labels, prop, cur)
+                normalized = sample.reshape(cfg.chunk, cfg.action_dim).numpy()
+                return self._unnormalize_actions(normalized, unnorm_key), ah.view(1, A, cfg.llm_dim).clone()
             cached, ah = None, None
             for t in sched.timesteps:
                 temb = action_head.time_encoder(torch.tensor([float(t)])).to(BF16)
@@ -589,7 +625,7 @@ class OpenVLAForActionPrediction(_StoreModule):
             labels[b, len(r) - A - 1: len(r)] = ACTION_TOKEN_BEGIN_IDX + 1
             labels[b, len(r) - 1] = STOP_INDEX
         film, film_avg = self.engine.use_film, None
-        graphed = self.use_graph and not use_diffusion
+        graphed = self.use_graph
         if film and not graphed:
             # FiLM's language average over each prompt's OWN tokens (padding would enter the mean: film_vit_wrapper.py:243): one ragged launch
             # for the batch, bit for bit ovla_language_average on each unpadded row.  (Under graph replay the launch is part of the graph.)
@@ -604,16 +640,24 @@ class OpenVLAForActionPrediction(_StoreModule):
                 if noise is None:
                     noise = torch.randn((B, cfg.chunk, cfg.action_dim))
                 cur = torch.as_tensor(noise).to("cpu", torch.float32).reshape(B, cfg.chunk, cfg.action_dim).to(BF16).float()
-                cached, ah = None, None
-                for t in sched.timesteps:
-                    temb = action_head.time_encoder(torch.tensor([float(t)])).to(BF16).reshape(1, D).expand(B, D)
-                    out = self.engine.forward(ids, mask, pixel_values, labels, proprio=prop, train=False, noisy_actions=cur.to(BF16),
-                                              timestep_emb=temb, proprio_projector=pp_comp, noisy_action_projector=noisy_action_projector.comp,
-                                              cached_patches=cached, sel="actions", film_avg=film_avg)
-                    cached = out["patches"]
-                    ah, _ = self.engine.action_hidden(out)
-                    eps = action_head.predict_noise(ah.view(B, A, D)).reshape(cur.shape).float().cpu()
-                    cur = sched.step(eps, int(t), cur).prev_sample.to(BF16).float()
+                if graphed:   # engine.DiffusionGraph: the ragged FiLM average, the towers and every sampling step replayed from captured graphs
+                    key = ("batch", B, Lb, tuple(pixel_values.shape), id(action_head.comp), id(pp_comp), ops.BATCH_INVARIANT_DEFAULT, film, "ddim",
+                           id(noisy_action_projector.comp), len(sched.timesteps), sched.config.num_train_timesteps)
+                    g = self._diffusion_graph(key, B, Lb, pixel_values.shape, action_head, noisy_action_projector, pp_comp, use_proprio,
+                                              invariant=ops.BATCH_INVARIANT_DEFAULT, film=film)
+                    sample, ah = g(ids, mask, pixel_values, labels, prop, cur)
+                    cur = sample.reshape(B, cfg.chunk, cfg.action_dim)
+                else:
+                    cached, ah = None, None
+                    for t in sched.timesteps:
+                        temb = action_head.time_encoder(torch.tensor([float(t)])).to(BF16).reshape(1, D).expand(B, D)
+                        out = self.engine.forward(ids, mask, pixel_values, labels, proprio=prop, train=False, noisy_actions=cur.to(BF16),
+                                                  timestep_emb=temb, proprio_projector=pp_comp, noisy_action_projector=noisy_action_projector.comp,
+                                                  cached_patches=cached, sel="actions", film_avg=film_avg)
+                        cached = out["patches"]
+                        ah, _ = self.engine.action_hidden(out)
+                        eps = action_head.predict_noise(ah.view(B, A, D)).reshape(cur.shape).float().cpu()
+                        cur = sched.step(eps, int(t), cur).prev_sample.to(BF16).float()
                 normalized = cur.numpy()
                 hidden = ah.view(B, A, D).clone()
             else:
@@ -624,9 +668,7 @@ class OpenVLAForActionPrediction(_StoreModule):
                     key = ("batch", B, Lb, tuple(pixel_values.shape), id(head_comp), id(pp_comp), ops.BATCH_INVARIANT_DEFAULT, film, discrete)
                     g = self._graphs.pop(key, None)
                     if g is None:
-                        batched = [k for k in self._graphs if k[0] == "batch"]
-                        if len(batched) >= self.max_batch_graphs:   # B and the bucket come from callers (/act_batch): keep the most recent few
-                            del self._graphs[batched[0]]
+                        self._evict_batch_graph()
                         g = ChunkGraph(self.engine, B, Lb, pixel_values.shape, head=head_comp, use_proprio=use_proprio, proprio_projector=pp_comp,
                                        invariant=ops.BATCH_INVARIANT_DEFAULT, film=film, discrete=discrete, n_tokens=self.vocab_size,
                                        n_bins=self.bin_centers.shape[0])

@@ -748,6 +748,38 @@ def argmax_bins(logits, *, n_tokens, n_bins, vocab=None, token=None, bins=None):
     return token, bins
 
 
+def _chk_step(step):
+    assert step.dtype == torch.int32 and step.numel() == 1 and step.is_cuda, "the DDIM step index is one int32 on the device"
+
+
+def ddim_prepare(step, temb_table, temb, sample, noisy):
+    """Top of DDIM step k = *step (ovla.h: ovla_ddim_prepare): temb[b] = temb_table[k] for every row of temb bf16 [B, D], noisy = bf16(sample)
+    (sample fp32, noisy bf16, n elements each).  k outside [0, n_steps): nothing is written."""
+    _chk_step(step)
+    _chk(temb_table, name="temb_table"), _chk(temb, name="temb"), _chk(noisy, name="noisy"), _chk(sample, torch.float32, "sample")
+    assert temb_table.dim() == 2 and temb.dim() == 2 and temb.shape[1] == temb_table.shape[1]
+    assert temb_table.is_contiguous() and temb.is_contiguous() and sample.is_contiguous() and noisy.is_contiguous() and noisy.numel() == sample.numel()
+    g = STRUCTS["ovla_ddim_prepare_args"]()
+    g.step, g.temb_table, g.temb, g.sample, g.noisy = step.data_ptr(), temb_table.data_ptr(), temb.data_ptr(), sample.data_ptr(), noisy.data_ptr()
+    g.n_steps, g.B, g.D, g.n = temb_table.shape[0], temb.shape[0], temb.shape[1], sample.numel()
+    _lib.call("ovla_ddim_prepare", g, _stream())
+
+
+def ddim_step(sample, eps, coef, step):
+    """End of DDIM step k = *step (ovla.h: ovla_ddim_step): sample (fp32, in place) <- DDIMScheduler.step(eps, t_k, sample).prev_sample rounded
+    through bf16, with eps the head's bf16 output and coef fp32 [n_steps, 4] from DDIMScheduler.step_coefficients(); then *step = k + 1.
+    k outside [0, n_steps): nothing is written."""
+    _chk_step(step)
+    _chk(sample, torch.float32, "sample"), _chk(eps, name="eps"), _chk(coef, torch.float32, "coef")
+    assert coef.dim() == 2 and coef.shape[1] == 4 and coef.is_contiguous() and sample.is_contiguous() and eps.is_contiguous()
+    assert eps.numel() == sample.numel()
+    g = STRUCTS["ovla_ddim_step_args"]()
+    g.sample, g.eps, g.coef, g.step = sample.data_ptr(), eps.data_ptr(), coef.data_ptr(), step.data_ptr()
+    g.n_steps, g.n = coef.shape[0], sample.numel()
+    _lib.call("ovla_ddim_step", g, _stream())
+    return sample
+
+
 def head_out_fwd(x, W, b, target=None, loss_sum=None, mse=False):
     rows, dim = x.shape
     adim = W.shape[0]

@@ -9,7 +9,10 @@ Differences, all deliberate:
     the "encoded" double-encoding of deploy.py:80-95 (whole payload as ONE json string under the key "encoded") is kept;
   * components can be handed in already built (tests; no checkpoint exists offline), otherwise they are loaded exactly like the
     reference does (get_vla / get_action_head / get_proprio_projector / get_processor);
-  * merged LoRA weights + hipGraph replay are switched on (`vla.enable_graph_replay()`): the deployment configuration of DESIGN.md §6;
+  * merged LoRA weights + hipGraph replay are switched on (`vla.enable_graph_replay()`): the deployment configuration of DESIGN.md §6,
+    for the diffusion head too (its DDIM loop replays from engine.DiffusionGraph);
+  * the reference's server never hands the noisy-action projector to `get_vla_action`, so its diffusion configuration cannot sample; here
+    the projector is a component like the action head (handed in, or loaded with get_noisy_action_projector) and is passed on;
   * `coalesce_ms > 0` (not in the reference): independent `/act` callers that arrive within that window share ONE batched forward
     (`RequestCoalescer` -> `get_vla_action_batch`, padded to a bucket of `batch_buckets`).  Batch invariance is what makes that safe: a
     coalesced `/act` answer is bit-identical to `/act_batch([payload])` -- the fixed-schedule batch path at B = 1 -- whatever it was merged
@@ -99,7 +102,7 @@ class DeployConfig:
 
 
 class OpenVLAServer:
-    def __init__(self, cfg, *, vla=None, processor=None, action_head=None, proprio_projector=None):
+    def __init__(self, cfg, *, vla=None, processor=None, action_head=None, proprio_projector=None, noisy_action_projector=None):
         self.cfg = cfg
         self.vla = vla if vla is not None else U.get_vla(cfg)
         self.proprio_projector = proprio_projector
@@ -108,9 +111,12 @@ class OpenVLAServer:
         self.action_head = action_head
         if self.action_head is None and (cfg.use_l1_regression or cfg.use_diffusion):
             self.action_head = U.get_action_head(cfg, self.vla.llm_dim)
+        self.noisy_action_projector = noisy_action_projector
+        if self.noisy_action_projector is None and cfg.use_diffusion:
+            self.noisy_action_projector = U.get_noisy_action_projector(cfg, self.vla.llm_dim)
         assert cfg.unnorm_key in self.vla.norm_stats, f"Action un-norm key {cfg.unnorm_key} not found in VLA `norm_stats`!"
         self.processor = processor if processor is not None else U.get_processor(cfg)
-        if getattr(cfg, "graph_replay", True) and not cfg.use_diffusion:   # (the diffusion sampler is a host loop: coalesced, but eager)
+        if getattr(cfg, "graph_replay", True):   # every head, the diffusion sampler included (engine.DiffusionGraph)
             self.vla.enable_graph_replay(True)
         self._lock = threading.Lock()
         self._coalescer = None
@@ -155,8 +161,8 @@ class OpenVLAServer:
         a failed batch one by one -- so it gets shallow copies, and a retried member starts from the state its caller sent."""
         observations = [dict(o) for o, _ in items]
         actions = U.get_vla_action_batch(self.cfg, self.vla, self.processor, observations, [o["instruction"] for o in observations],
-                                         action_head=self.action_head, proprio_projector=self.proprio_projector, use_film=self.cfg.use_film,
-                                         pad_to=pad_to)
+                                         action_head=self.action_head, proprio_projector=self.proprio_projector,
+                                         noisy_action_projector=self.noisy_action_projector, use_film=self.cfg.use_film, pad_to=pad_to)
         return [json.dumps(_encode(a)) if double else _encode(a) for a, (_, double) in zip(actions, items)]
 
     def close(self) -> None:
@@ -174,7 +180,8 @@ class OpenVLAServer:
             instruction = observation["instruction"]
             with self._lock:      # one engine, static graph buffers: serialise (the reference does not lock)
                 action = U.get_vla_action(self.cfg, self.vla, self.processor, observation, instruction, action_head=self.action_head,
-                                          proprio_projector=self.proprio_projector, use_film=self.cfg.use_film)
+                                          proprio_projector=self.proprio_projector, noisy_action_projector=self.noisy_action_projector,
+                                          use_film=self.cfg.use_film)
             return json.dumps(_encode(action)) if double else _encode(action)
         except Exception:  # noqa: BLE001 -- the reference answers "error" to any malformed request
             logging.error(traceback.format_exc())
@@ -195,7 +202,8 @@ class OpenVLAServer:
             instructions = [o["instruction"] for o in observations]
             with self._lock:
                 actions = U.get_vla_action_batch(self.cfg, self.vla, self.processor, observations, instructions, action_head=self.action_head,
-                                                 proprio_projector=self.proprio_projector, use_film=self.cfg.use_film)
+                                                 proprio_projector=self.proprio_projector, noisy_action_projector=self.noisy_action_projector,
+                                                 use_film=self.cfg.use_film)
             return [json.dumps(_encode(a)) if double else _encode(a) for a, (_, double) in zip(actions, decoded)]
         except Exception:  # noqa: BLE001 -- like /act
             logging.error(traceback.format_exc())
