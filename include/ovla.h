@@ -203,6 +203,38 @@ typedef struct {
 int64_t ovla_lora_bwd_workspace_bytes(int32_t M, int32_t gn, int32_t G);
 int ovla_lora_bwd(const ovla_lora_bwd_args* a, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Multi-adapter serving: n LoRA adapters ("slots", one per fine-tuned policy) in ONE K-extended GEMM launch.  peft applies one adapter per
+ * model, `result + lora_B(lora_A(x)) * scaling` (finetune.py:862-871); here the projection GEMM runs against the n adapters' stacked A
+ * (t [M, G*n*r], group-major: group g owns columns [g n r, (g+1) n r), slot s inside it [s r, (s+1) r)) and ovla_lora_route then stores bf16 +0
+ * over every column block of a slot other than the row's own, so the K-extension (K2 = n r, k2_group_n as before) adds exactly the row's own
+ * adapter: zeros contribute nothing to the fp32 accumulator.  Row m belongs to observation m / rows_per_obs, whose slot is obs_slot[obs]
+ * (DEVICE int32 [n_obs]: a captured graph serves any assignment).  Zeros are STORED, never multiplied in: a non-finite value in a foreign
+ * adapter's projection does not reach the row.  The row's own columns and the columns >= G*n*r (ld padding) are left untouched.  16-byte
+ * vector stores, no atomics, stream-ordered and capturable; r % 8 == 0, ld % 8 == 0, ld >= G*n*r, 16-byte aligned t, n_obs * rows_per_obs >= M.
+ * obs_slot_host (optional): the same n_obs values in HOST memory; an entry outside [0, n) is OVLA_EINVAL before anything is launched.  The
+ * kernel itself clamps what it reads from the device array to [0, n): it never reads or writes out of range.  n == 1 launches nothing. */
+typedef struct {
+  void* t; int64_t ld;               /* bf16 [M, ld], routed in place */
+  const int32_t* obs_slot;           /* device int32 [n_obs] */
+  const int32_t* obs_slot_host;      /* optional host copy, validated */
+  int32_t M, G, n, r, rows_per_obs, n_obs;
+} ovla_lora_route_args;
+int ovla_lora_route(const ovla_lora_route_args* a, void* stream);
+
+/* dst[m, :] = src[slot(m), m, :]: each observation's own policy's output out of n stacked candidates -- the per-policy L1 action heads'
+ * predictions (prismatic/models/action_heads.py:84-107; a fine-tune saves its own `action_head--*.pt`, finetune.py:584-675) and proprio
+ * projectors' tokens (prismatic/models/projectors.py:6-24), computed for all observations by every registered policy and picked here.
+ * src [n, rows, dim] with src_slot_stride elements between slots (0: rows * dim), dst [rows, dim] contiguous, elem_bytes 2 (bf16) or 4 (fp32);
+ * slot(m) = obs_slot[m / rows_per_obs] with ovla_lora_route's addressing, host validation (obs_slot_host) and device-side clamp. */
+typedef struct {
+  const void* src; void* dst;
+  const int32_t* obs_slot; const int32_t* obs_slot_host;
+  int64_t src_slot_stride;
+  int32_t n, rows, dim, rows_per_obs, n_obs, elem_bytes;
+} ovla_select_by_slot_args;
+int ovla_select_by_slot(const ovla_select_by_slot_args* a, void* stream);
+
 /* column sums  out[n] (+)= sum_m X[m,n]   (bias gradients).  out fp32, atomic accumulate. */
 typedef struct { const void* X; int64_t ldx; float* out; int32_t M, N; } ovla_colsum_args;
 int ovla_colsum_bf16(const ovla_colsum_args* a, void* stream);

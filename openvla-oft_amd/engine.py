@@ -15,6 +15,7 @@ HBM layout (sized for 288 GB):
 """
 from __future__ import annotations
 
+import contextlib
 import math
 from typing import Dict, List, Optional
 
@@ -153,6 +154,53 @@ class ParamStore:
 # ======================================================================================================================
 # linears
 # ======================================================================================================================
+MAX_SLOTS = 4   # adapters that ride in one launch (K2 = n * r <= 128 at r = 32)
+
+
+def slot_a_rows(g: int, s: int, n: int, r: int) -> slice:
+    """Rows of A_slots (= columns of t) that hold group g of adapter slot s: group-major, [(g n + s) r, (g n + s + 1) r)."""
+    return slice((g * n + s) * r, (g * n + s + 1) * r)
+
+
+def fill_slot(A_slots, B_slots, s: int, lora_A, lora_B, groups: int):
+    """Writes adapter s into the slot storage of one (fused) linear: A_slots [G*n*r, in], B_slots [out, n*r]; lora_A is [G*r, in] (the groups'
+    lora_A stacked), lora_B is [out, r].  THE layout (LoraLinear.set_slot goes through here): with t = s * x . A_slots^T and every column block
+    of a foreign slot zeroed per row, the K-extended GEMM  y = x W^T + t_g . B_slots[group g rows]^T  gives each row  x W^T + t_own B_own^T."""
+    r = lora_B.shape[1]
+    n = B_slots.shape[1] // r
+    for g in range(groups):
+        A_slots[slot_a_rows(g, s, n, r)] = lora_A[g * r:(g + 1) * r].to(A_slots.device, A_slots.dtype)
+    B_slots[:, s * r:(s + 1) * r] = lora_B.to(B_slots.device, B_slots.dtype)
+
+
+class SlotRoute:
+    """The engine-level routing context of multi-policy serving: which adapter slot each observation of the running forward takes, as a DEVICE
+    int32 buffer (so a captured graph serves any assignment), and how many observations there are.  Every slotted LoraLinear holds the engine's
+    one instance and derives rows_per_obs from its own row count (rows are ordered by observation everywhere: towers (b, img, token),
+    projector (b, patch), decoder (b, s), selected action rows (b, a))."""
+
+    def __init__(self):
+        self.obs_slot: Optional[torch.Tensor] = None
+        self.n_obs = 0
+        self.host_slots: Optional[List[int]] = None   # the same values on the host where the caller has them: the library validates them
+
+
+class SlotProjectors:
+    """Every registered policy's proprio projector on all B observations, then each observation's own row (ovla_select_by_slot): n small
+    forwards instead of data-dependent grouping, which a captured graph could not hold.  Quacks like MlpProjector.fwd for patches_dev."""
+
+    def __init__(self, comps, route: SlotRoute):
+        self.comps, self.route = list(comps), route
+
+    def fwd(self, x, train: bool):
+        assert not train, "multi-policy serving is inference-only"
+        ys = torch.stack([c.fwd(x, False)[0] for c in self.comps])          # [n, rows padded to 8, D]
+        out = torch.zeros_like(ys[0])
+        B = self.route.n_obs
+        ops.select_by_slot(ys, self.route.obs_slot, rows_per_obs=1, rows=B, out=out[:B], host_slots=self.route.host_slots)
+        return out, None
+
+
 class LoraLinear:
     """Frozen nn.Linear (+ optional bias) with peft-style LoRA adapters; `groups` fused sub-linears share the input.
 
@@ -220,9 +268,52 @@ class LoraLinear:
             ops.transpose(self.W, self.WT)
         self.merged = True
 
+    # -- adapter slots (multi-policy serving; inference only) -------------------------------------------------------------------------------
+    def init_slots(self, n: int, r: int, route: "SlotRoute"):
+        """Frozen storage for n adapters of rank r in the layout of fill_slot (zero until set_slot fills it): A_slots [G*n*r, in] makes the
+        ordinary projection GEMM produce t [M, G*n*r] directly, B_slots [out, n*r] is the K-extension's B2.  Only on a linear without adapters of
+        its own; `route` is the engine's SlotRoute, whose device obs_slot buffer says which slot each observation takes."""
+        if self.has_lora:
+            raise ValueError(f"{self.name}: adapter slots need a linear without merged or trainable adapters")
+        if not 1 <= n <= MAX_SLOTS:
+            raise ValueError(f"{self.name}: {n} adapter slots (1 .. {MAX_SLOTS} supported)")
+        if r % 8:
+            raise ValueError(f"{self.name}: slot rank {r} must be a multiple of 8")
+        dev = self.W.device
+        self.n_slots, self.slot_r, self.route = n, r, route
+        self.A_slots = torch.zeros((self.groups * n * r, self.in_f), dtype=BF16, device=dev)
+        self.B_slots = torch.zeros((self.out_f, n * r), dtype=BF16, device=dev)
+
+    def clear_slots(self):
+        self.n_slots, self.A_slots, self.B_slots = 0, None, None
+
+    def set_slot(self, s: int, lora_A: torch.Tensor, lora_B: torch.Tensor):
+        """Adapter s: lora_A [G*r, in] (the fused groups' A stacked as in __init__), lora_B [out, r]."""
+        n, r, G = self.n_slots, self.slot_r, self.groups
+        if not 0 <= s < n:
+            raise ValueError(f"{self.name}: slot {s} of {n}")
+        if tuple(lora_A.shape) != (G * r, self.in_f) or tuple(lora_B.shape) != (self.out_f, r):
+            raise ValueError(f"{self.name}: adapter shapes {tuple(lora_A.shape)} / {tuple(lora_B.shape)} do not fit rank {r} "
+                             f"(want {(G * r, self.in_f)} / {(self.out_f, r)})")
+        fill_slot(self.A_slots, self.B_slots, s, lora_A, lora_B, G)
+
+    def slots_active(self) -> bool:
+        return bool(getattr(self, "n_slots", 0)) and self.route.obs_slot is not None
+
     def fwd(self, x, *, act=0, residual=None, colscale=None, c_pre=None, film=None, out=None, rope=None):
         """x [M, in] -> (y [M, out], saved).  `rope` = (cos, sin, S, cols): RoPE on the first `cols` output columns in the GEMM epilogue."""
         t_s = None
+        if self.slots_active():
+            # n adapters in one launch: project against all of them, zero every foreign slot's columns per row (ovla_lora_route: the assignment is
+            # device data), then the usual K-extended GEMM with K2 = n * r.  Zeros add nothing to the fp32 accumulator: a row sees its own adapter.
+            rt, n, r, M = self.route, self.n_slots, self.slot_r, x.shape[0]
+            if M % rt.n_obs:
+                raise RuntimeError(f"{self.name}: {M} rows do not divide over {rt.n_obs} observations")
+            t_s = ops.gemm(x, self.A_slots, alpha=self.scale)
+            ops.lora_route(t_s, rt.obs_slot, G=self.groups, n=n, r=r, rows_per_obs=M // rt.n_obs, host_slots=rt.host_slots)
+            y = ops.gemm(x, self.W, out=out, bias=self.bias, act=act, residual=residual, colscale=colscale, c_pre=c_pre, film=film,
+                         a2=t_s, b2=self.B_slots, k2_group_n=self.group_n if self.groups > 1 else 0, rope=rope)
+            return y, None
         if self.has_lora and not getattr(self, "merged", False):
             t_s = ops.gemm(x, self.A.data, alpha=self.scale)
             y = ops.gemm(x, self.W, out=out, bias=self.bias, act=act, residual=residual, colscale=colscale, c_pre=c_pre, film=film,
@@ -237,6 +328,8 @@ class LoraLinear:
         activation that PRODUCED this linear's input (returns dz / d(gate|up) instead of dx: ovla.h backward epilogues).
         `tn_queue`: a list that collects this linear's weight-gradient TN problems instead of launching them; the caller launches the
         list (ops.gemm_tn_grouped) BEFORE anything overwrites `dy` -- two neighbouring linears' four small problems share one launch."""
+        if getattr(self, "n_slots", 0):
+            raise RuntimeError(f"{self.name}: this linear carries adapter slots (multi-policy serving); that path is inference-only")
         x, t_s = saved
         dx = None
         if getattr(self, "merged", False):
@@ -595,7 +688,10 @@ class LlamaStack:
             raise ValueError("LlamaStack.fwd: the number of selected rows must be a positive multiple of 8")
         M = x.shape[0]
         invariant = ops.batch_invariant_enabled()
-        fold = (not train) and getattr(self, "folded", False) and _FOLD_RMSNORM and (self._fold_fixed_ok() if invariant else self._fold_ok(M))
+        # (live adapter slots: the unfolded path, as for any adapter-carrying decoder -- the folded launches bypass LoraLinear.fwd)
+        rt = getattr(self, "slot_route", None)   # set by VLAEngine.set_adapter_slots when a decoder linear carries slots
+        slotted = rt is not None and rt.obs_slot is not None
+        fold = (not train) and getattr(self, "folded", False) and _FOLD_RMSNORM and not slotted and (self._fold_fixed_ok() if invariant else self._fold_ok(M))
         part = rbuf = None
         itile = 0
         if fold:   # sums of squares of the first layer's input rows; every later layer's come out of the down projection's epilogue
@@ -853,6 +949,7 @@ class VLAEngine:
             raise ValueError(head)
         ops.check_device(device.index or 0)
         self.cfg, self.device, self.lora = cfg, device, lora
+        self.route, self.n_slots = SlotRoute(), 0   # multi-policy serving (set_adapter_slots / routing)
         lora = lora_predicate(lora, has)
         st = self.store = ParamStore(device)
         # registration order = forward order (the store reverses it into backward order)
@@ -922,6 +1019,68 @@ class VLAEngine:
         self.lora_merged = True
         if _FOLD_RMSNORM:
             self.llm.fold_norms()       # adapter-free decoder: RMSNorm + RoPE + q|k|v (and RMSNorm + gate|up) become one launch each at inference
+
+    # -- adapter slots: several fine-tuned policies on one base model (inference only) ---------------------------------------------------------
+    def set_adapter_slots(self, adapters: List[Dict[str, torch.Tensor]], *, lora_alpha: Optional[List[Optional[float]]] = None):
+        """adapters[s]: policy s's LoRA tensors under the names lora_state_dict() / weights.load_lora_adapter use (`<linear>.lora_A.weight`,
+        `.lora_B.weight`, un-fused per q/k/v and gate/up).  Allocates n = len(adapters) slots on every adapted linear and fills them; an empty
+        list removes the slots.  The model must carry no merged or trainable adapters of its own; all policies must adapt the same linears with
+        one rank and one lora_alpha -- the model configuration's, whose alpha / r scales every slot's projection."""
+        if getattr(self, "lora_merged", False) or any(isinstance(l, LoraLinear) and l.has_lora for l in self.vlm_linears()):
+            raise ValueError("adapter slots need a base model built without merged or trainable LoRA adapters")
+        n = len(adapters)
+        if n > MAX_SLOTS:
+            raise ValueError(f"{n} policies: at most {MAX_SLOTS} adapter slots ride in one launch")
+        cfg = self.cfg
+        for s, a in enumerate(lora_alpha or []):
+            if a is not None and float(a) != float(cfg.lora_alpha):
+                raise ValueError(f"policy {s}: lora_alpha {a} differs from the model configuration's {cfg.lora_alpha} (one alpha / r scales every slot)")
+        linears = [l for l in self.vlm_linears() if isinstance(l, LoraLinear)]
+        known = {rn + suffix for l in linears for rn in l.ref_names for suffix in (".lora_A.weight", ".lora_B.weight")}
+        unused = tuple(f"{t.prefix}blocks.{t.vc.depth - 1}." for t in (self.dino, self.siglip))   # each tower's last block is never run (VitTower)
+        plans = []
+        for s, sd in enumerate(adapters):
+            stray = [k for k in sd if k not in known and not k.startswith(unused)]
+            if stray:
+                raise ValueError(f"policy {s}: {len(stray)} tensors name no adapted linear of this model, e.g. {stray[:2]}")
+            adapted = frozenset(l.name for l in linears if any(rn + ".lora_A.weight" in sd for rn in l.ref_names))
+            plans.append(adapted)
+            for l in linears:
+                if l.name in adapted and not all(rn + sfx in sd for rn in l.ref_names for sfx in (".lora_A.weight", ".lora_B.weight")):
+                    raise ValueError(f"policy {s}: adapters present for only some of the fused linears {l.ref_names}")
+                for rn in l.ref_names:
+                    if l.name in adapted and sd[rn + ".lora_A.weight"].shape[0] != cfg.lora_rank:
+                        raise ValueError(f"policy {s}: {rn} has rank {sd[rn + '.lora_A.weight'].shape[0]}, the model configuration's is {cfg.lora_rank} "
+                                         "(mixed ranks are not supported)")
+        if any(p != plans[0] for p in plans):
+            raise ValueError("the policies adapt different sets of linears")
+        for l in linears:
+            l.clear_slots()
+            if n and l.name in plans[0]:
+                l.init_slots(n, cfg.lora_rank, self.route)
+                for s, sd in enumerate(adapters):
+                    l.set_slot(s, torch.cat([sd[rn + ".lora_A.weight"] for rn in l.ref_names], 0), torch.cat([sd[rn + ".lora_B.weight"] for rn in l.ref_names], 0))
+        self.n_slots = n
+        self.llm.slot_route = self.route if any(getattr(l, "n_slots", 0) for l in self.llm.linears()) else None
+
+    @contextlib.contextmanager
+    def routing(self, obs_slot: torch.Tensor, host_slots=None):
+        """Inside: every slotted linear of this engine routes by `obs_slot` (device int32 [B], one adapter slot per observation of the forward).
+        `host_slots`: the same values on the host, when the caller has them and they will not change under the launches (an eager forward; not a
+        graph capture, whose buffer is rewritten before every replay): every routed launch then validates them (OVLA_EINVAL)."""
+        assert obs_slot.dtype == torch.int32 and obs_slot.is_cuda and obs_slot.dim() == 1
+        rt = self.route
+        prev = (rt.obs_slot, rt.n_obs, rt.host_slots)
+        rt.obs_slot, rt.n_obs, rt.host_slots = obs_slot, obs_slot.numel(), None if host_slots is None else [int(v) for v in host_slots]
+        try:
+            yield rt
+        finally:
+            rt.obs_slot, rt.n_obs, rt.host_slots = prev
+
+    def policy_heads_fwd(self, ah, heads):
+        """Every policy's L1 head on all B observations' action rows, then each observation's own prediction (ovla_select_by_slot) -> [B*chunk, action_dim]."""
+        preds = torch.stack([h.fwd(ah)[0] for h in heads])                   # [n, B * chunk, action_dim]
+        return ops.select_by_slot(preds, self.route.obs_slot, rows_per_obs=self.cfg.chunk, host_slots=self.route.host_slots)
 
     def merged_state_dict(self) -> Dict[str, torch.Tensor]:
         """Base VLM weights under the reference's HF key layout (un-fused q/k/v, gate/up), after merge_lora(): what
@@ -1395,11 +1554,27 @@ class ChunkGraph:
     (ovla_language_average_ragged: row b averages its own lens[b] tokens, pad tokens never enter), inside the graph.  Without it a FiLM engine
     averages over all L positions, which is the reference's rule for an unpadded prompt (predict_action).
     `discrete=True` (no action head, engine.lm_head present): the graph goes on to the lm_head GEMM on the action rows and the greedy decode
-    (ovla_argmax_bins); replay() then returns (None, action hidden, token int32 [B*A], bin int32 [B*A])."""
+    (ovla_argmax_bins); replay() then returns (None, action hidden, token int32 [B*A], bin int32 [B*A]).
+    `policies` (multi-policy serving, an engine with adapter slots): [(L1 head component or None, proprio projector component or None)] in slot
+    order.  The graph then routes every slotted linear by the static `obs_slot` buffer that load(slots=...) writes, runs EVERY policy's head and
+    proprio projector on all B observations and picks each observation's own with one ovla_select_by_slot each: the assignment is data, so one
+    capture serves every assignment of the same policy set."""
 
     def __init__(self, engine: "VLAEngine", B: int, L: int, pixel_shape, *, head=None, use_proprio: bool = True, proprio_projector=None,
-                 invariant: bool = False, film: bool = False, discrete: bool = False, n_tokens: Optional[int] = None, n_bins: Optional[int] = None):
+                 invariant: bool = False, film: bool = False, discrete: bool = False, n_tokens: Optional[int] = None, n_bins: Optional[int] = None,
+                 policies=None):
         dev = engine.device
+        self.policies = policies
+        self.obs_slot = None
+        if policies is not None:
+            if len(policies) != engine.n_slots or not policies:
+                raise ValueError(f"ChunkGraph: {len(policies)} policies for an engine with {engine.n_slots} adapter slots")
+            if film or head is not None or proprio_projector is not None:
+                raise ValueError("ChunkGraph(policies=...): heads and proprio projectors come per policy; FiLM is not supported")
+            self.slot_heads = [h for h, _ in policies] if all(h is not None for h, _ in policies) else None
+            self.obs_slot = torch.zeros(B, dtype=torch.int32, device=dev)
+            if use_proprio:
+                proprio_projector = SlotProjectors([p for _, p in policies], engine.route)
         self.engine, self.head, self.B, self.L = engine, head, B, L
         self.invariant = invariant   # capture every GEMM under its fixed schedule (ops.batch_invariant): the batched inference API
         if film and not engine.use_film:
@@ -1417,8 +1592,15 @@ class ChunkGraph:
         self.proprio = torch.zeros((B, engine.cfg.proprio_dim), dtype=BF16, device=dev) if use_proprio else None
         self.graph = None
         self.out = None
+        self.captures = 0
 
     def _run(self):
+        if self.policies is not None:
+            with self.engine.routing(self.obs_slot):
+                return self._run_routed()
+        return self._run_routed()
+
+    def _run_routed(self):
         eng = self.engine
         D = eng.cfg.llm_dim
         with ops.batch_invariant(self.invariant):
@@ -1430,6 +1612,8 @@ class ChunkGraph:
                                   proprio_projector=self.proprio_projector, sel="actions", film_avg=film_avg)
             ah, _ = eng.action_hidden(out)
             pred = self.head.fwd(ah)[0] if self.head is not None else None
+            if self.policies is not None and self.slot_heads is not None:
+                pred = eng.policy_heads_fwd(ah, self.slot_heads)
             if self.discrete:   # modeling.logits_for's row padding and GEMM, then the decode on the bf16 logits
                 n = ah.shape[0]
                 rows = torch.zeros(((n + 7) // 8 * 8, D), dtype=BF16, device=eng.device)
@@ -1438,9 +1622,16 @@ class ChunkGraph:
                 return pred, ah, tok, bins
         return pred, ah
 
-    def load(self, input_ids, attention_mask, pixel_values, labels, proprio=None):
+    def load(self, input_ids, attention_mask, pixel_values, labels, proprio=None, slots=None):
         lens = VLAEngine.check_right_padding(attention_mask)
         assert tuple(input_ids.shape) == (self.B, self.L), f"ChunkGraph captured for ids {(self.B, self.L)}, got {tuple(input_ids.shape)}"
+        if (slots is None) != (self.obs_slot is None):
+            raise ValueError("ChunkGraph.load: `slots` goes with a graph built with policies=")
+        if slots is not None:   # the host sees the values here: an out-of-range slot never reaches a kernel
+            slots = [int(v) for v in slots]
+            if len(slots) != self.B or any(not 0 <= v < len(self.policies) for v in slots):
+                raise ValueError(f"ChunkGraph.load: slots {slots} for {self.B} observations and {len(self.policies)} policies")
+            self.obs_slot.copy_(torch.tensor(slots, dtype=torch.int32), non_blocking=True)
         self.ids.copy_(input_ids.to(torch.int64), non_blocking=True)
         self.lab.copy_(labels.to(torch.int64), non_blocking=True)
         self.lens.copy_(lens.to(torch.int32), non_blocking=True)
@@ -1458,6 +1649,7 @@ class ChunkGraph:
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph):
                 self.out = self._run()
+            self.captures += 1
         finally:
             self._ws, ops._ws_cache = ops._ws_cache, outer_ws
         return self
@@ -1466,8 +1658,8 @@ class ChunkGraph:
         self.graph.replay()
         return self.out
 
-    def __call__(self, input_ids, attention_mask, pixel_values, labels, proprio=None):
-        self.load(input_ids, attention_mask, pixel_values, labels, proprio)
+    def __call__(self, input_ids, attention_mask, pixel_values, labels, proprio=None, slots=None):
+        self.load(input_ids, attention_mask, pixel_values, labels, proprio, slots)
         if self.graph is None:
             self.capture()
         return self.replay()

@@ -8,6 +8,7 @@ Differences forced by the offline MI355X environment, all explicit:
 """
 from __future__ import annotations
 
+import copy
 import json
 import os
 from pathlib import Path
@@ -122,6 +123,30 @@ def get_action_head(cfg: Any, llm_dim: int):
     return L1RegressionActionHead(llm_dim, llm_dim, C.ACTION_DIM, num_actions_chunk=C.NUM_ACTIONS_CHUNK, device=DEVICE, state_dict=sd).eval()
 
 
+def get_policy(cfg: Any, vla: OpenVLAForActionPrediction, name: str, checkpoint_dir) -> OpenVLAForActionPrediction:
+    """Registers the fine-tune output directory `checkpoint_dir` (finetune.py:584-675: `lora_adapter/`, `action_head--*_checkpoint.pt`,
+    `proprio_projector--*_checkpoint.pt`, `dataset_statistics.json`) as policy `name` of the base model `vla` (vla.add_policy), read with the
+    loaders above.  The head is loaded when cfg.use_l1_regression, the proprio projector when cfg.use_proprio; without a head the policy uses
+    the discrete token path.  Returns vla."""
+    from ...weights import load_lora_adapter
+
+    d = Path(checkpoint_dir)
+    if not d.is_dir():
+        raise ValueError(f"`{d}` is not a fine-tune output directory")
+    if getattr(cfg, "use_diffusion", False) or getattr(cfg, "use_film", False):
+        raise ValueError("get_policy: diffusion heads and FiLM are not supported for per-request policies")
+    lora, acfg = load_lora_adapter(d / "lora_adapter")
+    if acfg.get("r") is not None and int(acfg["r"]) != vla.cfg.lora_rank:
+        raise ValueError(f"policy {name!r}: adapter rank {acfg['r']} differs from the model configuration's {vla.cfg.lora_rank}")
+    sub = copy.copy(cfg)                       # the component loaders read cfg.pretrained_checkpoint
+    sub.pretrained_checkpoint = str(d)
+    head = get_action_head(sub, vla.llm_dim) if getattr(cfg, "use_l1_regression", False) else None
+    pp = get_proprio_projector(sub, vla.llm_dim, C.PROPRIO_DIM) if getattr(cfg, "use_proprio", False) else None
+    stats = d / "dataset_statistics.json"
+    norm_stats = json.loads(stats.read_text()) if stats.is_file() else None
+    return vla.add_policy(name, lora, action_head=head, proprio_projector=pp, norm_stats=norm_stats, lora_alpha=acfg.get("lora_alpha"))
+
+
 class PrismaticProcessor:
     """processor(prompt, image) -> {"input_ids", "attention_mask", "pixel_values"} (processing_prismatic.py:175-252)."""
 
@@ -223,13 +248,17 @@ def device_pixel_values_batch(per_obs: List[List[np.ndarray]], cfg: Any) -> torc
 
 def get_vla_action_batch(cfg: Any, vla, processor: Any, observations: List[Dict[str, Any]], task_labels: List[str], action_head=None,
                          proprio_projector=None, noisy_action_projector=None, use_film: bool = False, noise=None,
-                         pad_to: Optional[int] = None) -> List[List[np.ndarray]]:
+                         pad_to: Optional[int] = None, policies: Optional[List[str]] = None) -> List[List[np.ndarray]]:
     """get_vla_action for B observations in one batched forward (OpenVLAForActionPrediction.predict_action_batch): per observation the same
     semantics -- including the in-place normalisation of obs["state"] -- and one list of num_open_loop_steps actions per observation.  On the
     device image path all B * I frames go through device_pixel_values together (one launch per stage).  `pad_to`: predict_action_batch's
-    (the forward runs at that batch size on a repeated observation 0; B results come back)."""
+    (the forward runs at that batch size on a repeated observation 0; B results come back).  `policies`: one registered policy name per
+    observation (vla.add_policy / get_policy): head, proprio projector, proprio and action statistics are then each observation's policy's,
+    and `action_head` / `proprio_projector` must not be given."""
     if len(observations) != len(task_labels):
         raise ValueError(f"get_vla_action_batch: {len(observations)} observations but {len(task_labels)} task labels")
+    if policies is not None and len(policies) != len(observations):
+        raise ValueError(f"get_vla_action_batch: {len(policies)} policy names for {len(observations)} observations")
     if not observations:
         raise ValueError("get_vla_action_batch: no observations")
     with torch.inference_mode():
@@ -259,10 +288,19 @@ def get_vla_action_batch(cfg: Any, vla, processor: Any, observations: List[Dict[
         batch = [(t["input_ids"], t.get("attention_mask")) for t in toks]
         proprio = None
         if cfg.use_proprio:
-            for obs in observations:
-                obs["state"] = normalize_proprio(obs["state"], vla.norm_stats[cfg.unnorm_key]["proprio"])
+            for b, obs in enumerate(observations):
+                stats = vla.norm_stats
+                if policies is not None:
+                    if policies[b] not in vla.policies:
+                        raise ValueError(f"get_vla_action_batch: unknown policy {policies[b]!r}")
+                    stats = vla.policy_norm_stats(policies[b])
+                obs["state"] = normalize_proprio(obs["state"], stats[cfg.unnorm_key]["proprio"])
             proprio = np.stack([np.asarray(obs["state"]) for obs in observations])
-        if action_head is None:
+        if policies is not None:
+            actions, _ = vla.predict_action_batch(batch, pixel_values, unnorm_key=cfg.unnorm_key, proprio=proprio, action_head=action_head,
+                                                  proprio_projector=proprio_projector, noisy_action_projector=noisy_action_projector, use_film=use_film,
+                                                  pad_to=pad_to, policy=list(policies))
+        elif action_head is None:
             actions, _ = vla.predict_action_batch(batch, pixel_values, unnorm_key=cfg.unnorm_key, pad_to=pad_to)
         else:
             actions, _ = vla.predict_action_batch(batch, pixel_values, unnorm_key=cfg.unnorm_key, proprio=proprio, proprio_projector=proprio_projector,

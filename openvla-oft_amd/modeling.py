@@ -22,7 +22,7 @@ import torch.nn as nn
 from . import ops
 from .config import VLAConfig
 from .diffusion import DDIMScheduler, SinusoidalPositionalEncoding
-from .engine import ChunkGraph, DiffusionGraph, ActionHead, MlpProjector, ParamStore, VLAEngine, build_component
+from .engine import ChunkGraph, DiffusionGraph, ActionHead, MlpProjector, ParamStore, SlotProjectors, VLAEngine, build_component
 from .weights import make_getter
 
 BF16 = torch.bfloat16
@@ -389,6 +389,93 @@ class OpenVLAForActionPrediction(_StoreModule):
         # predict_action_batch: captured graphs kept per (B, text bucket, ...), least recently used evicted first.  A coalescing server raises it to
         # 4 text-length buckets per batch bucket (deploy.OpenVLAServer), so that prompts of varied length do not thrash captures.
         self.max_batch_graphs = 8
+        # multi-policy serving (add_policy): name -> dict(lora, head, pp, norm_stats), in adapter-slot order
+        self._policies: Dict[str, dict] = {}
+        self._policy_gen = 0
+
+    # -- several fine-tuned policies on one base model ------------------------------------------------------------------------------------
+    @property
+    def policies(self) -> Tuple[str, ...]:
+        """Names of the registered policies, in adapter-slot order."""
+        return tuple(self._policies)
+
+    def add_policy(self, name: str, lora_state_dict: Dict[str, torch.Tensor], *, action_head=None, proprio_projector=None,
+                   norm_stats: Optional[dict] = None, lora_alpha: Optional[float] = None):
+        """Registers one fine-tune's outputs (finetune.py:584-675: `lora_adapter/`, `action_head--*.pt`, `proprio_projector--*.pt`,
+        `dataset_statistics.json`) as a policy of this BASE model: its adapters go into the next adapter slot of every adapted linear
+        (engine.set_adapter_slots; tensor names as lora_state_dict() emits and weights.load_lora_adapter returns), its L1 head, proprio projector
+        and un-normalisation statistics are kept for predict_action_batch(policy=[...]).  At most engine.MAX_SLOTS policies; all with the
+        model configuration's rank and lora_alpha (`lora_alpha`: the adapter_config.json value, checked when given), the same adapted linears,
+        and alike in having a head / a proprio projector or not.  The model must carry no merged or trainable adapters.  Adding a policy changes
+        the slot count n and with it the K-extension width: outputs of earlier policies are reproducible per (policy, n), not across n.
+        Every policy's adapter tensors stay referenced on the host and each call refills all slots of all linears (the slot count changed): with
+        at most 4 policies that is a handful of copies per linear, done once at registration."""
+        if not isinstance(name, str) or not name:
+            raise ValueError("add_policy: the policy name must be a non-empty string")
+        if name in self._policies:
+            raise ValueError(f"add_policy: a policy named {name!r} is already registered")
+        if action_head is not None and hasattr(action_head, "noise_scheduler"):
+            raise ValueError("add_policy: per-policy diffusion heads are not supported (L1 head, or none for the discrete token path)")
+        pol = dict(lora=dict(lora_state_dict), head=action_head, pp=proprio_projector, norm_stats=norm_stats, lora_alpha=lora_alpha)
+        pols = list(self._policies.values()) + [pol]
+        for what in ("head", "pp"):
+            if len({p[what] is None for p in pols}) > 1:
+                raise ValueError(f"add_policy: either every policy brings its own {'action head' if what == 'head' else 'proprio projector'} or none does")
+        self.engine.set_adapter_slots([p["lora"] for p in pols], lora_alpha=[p["lora_alpha"] for p in pols])   # validates before it changes anything
+        self._policies[name] = pol
+        self._policy_gen += 1
+        for k in [k for k in self._graphs if "policies" in k]:   # captured against the previous slot storage
+            del self._graphs[k]
+        return self
+
+    def policy_norm_stats(self, name: Optional[str] = None) -> dict:
+        """The statistics a policy un-normalises with: its own `norm_stats` when add_policy was given some, otherwise the model's (also for None)."""
+        own = self._policies[name]["norm_stats"] if name is not None else None
+        return own if own is not None else self.norm_stats
+
+    def _predict_batch_policies(self, policy, ids, mask, labels, pixel_values, prop, use_proprio, Lb):
+        """predict_action_batch's forward for a mixed-policy batch -> (normalised actions [B, chunk, action_dim], hidden [B, A, D])."""
+        cfg, eng = self.cfg, self.engine
+        B, A, D = ids.shape[0], cfg.num_action_tokens, cfg.llm_dim
+        names = list(self._policies)
+        slots = [names.index(p) for p in policy]
+        pols = [self._policies[n] for n in names]
+        heads = [p["head"].comp for p in pols] if pols[0]["head"] is not None else None
+        pps = [p["pp"].comp for p in pols] if use_proprio else None
+        discrete, bins = heads is None, None
+        with ops.batch_invariant(ops.BATCH_INVARIANT_DEFAULT):
+            if self.use_graph:   # the key holds the policy set's identity and n, never the assignment: one capture serves every assignment
+                key = ("batch", B, Lb, tuple(pixel_values.shape), use_proprio, ops.BATCH_INVARIANT_DEFAULT, "policies", self._policy_gen, len(names),
+                       "discrete" if discrete else "l1")
+                g = self._graphs.pop(key, None)
+                if g is None:
+                    self._evict_batch_graph()
+                    g = ChunkGraph(eng, B, Lb, pixel_values.shape, use_proprio=use_proprio, invariant=ops.BATCH_INVARIANT_DEFAULT, discrete=discrete,
+                                   n_tokens=self.vocab_size, n_bins=self.bin_centers.shape[0],
+                                   policies=[(None if heads is None else heads[s], None if pps is None else pps[s]) for s in range(len(names))])
+                    g._keep = (heads, pps)
+                self._graphs[key] = g
+                res = g(ids, mask, pixel_values, labels, prop, slots=slots)
+                pred, hidden = res[0], res[1].view(B, A, D).clone()
+                if discrete:
+                    bins = res[3].cpu().numpy().astype(np.int64)
+                pred = pred.clone() if pred is not None else None
+            else:
+                with eng.routing(torch.tensor(slots, dtype=torch.int32).to(self.device), host_slots=slots):
+                    out = eng.forward(ids, mask, pixel_values, labels, proprio=prop, train=False,
+                                      proprio_projector=SlotProjectors(pps, eng.route) if use_proprio else None, sel="actions")
+                    ah, _ = eng.action_hidden(out)
+                    hidden = ah.view(B, A, D).clone()
+                    pred = eng.policy_heads_fwd(ah, heads) if heads is not None else None
+            if pred is not None:
+                normalized = pred.reshape(B, cfg.chunk, cfg.action_dim).float().cpu().numpy()
+            elif bins is not None:
+                normalized = self.bin_centers[bins].reshape(B, cfg.chunk, cfg.action_dim)
+            else:
+                tok = self.logits_for(hidden.view(B * A, D)).argmax(dim=1).cpu().numpy()
+                d = np.clip(self.vocab_size - tok - 1, a_min=0, a_max=self.bin_centers.shape[0] - 1)
+                normalized = self.bin_centers[d].reshape(B, cfg.chunk, cfg.action_dim)
+        return normalized, hidden
 
     def merge_and_unload(self):
         """peft `merge_and_unload()` of merge_lora_weights_and_save.py:60-67 on device: W += (alpha/r) B A for every adapted
@@ -561,7 +648,7 @@ class OpenVLAForActionPrediction(_StoreModule):
     # -- batched inference (not in the reference: its predict_action asserts batch size 1) -----------------------------------------------
     @torch.no_grad()
     def predict_action_batch(self, prompts, pixel_values, unnorm_key=None, proprio=None, proprio_projector=None, action_head=None,
-                             noisy_action_projector=None, use_film: bool = False, noise=None, pad_to: Optional[int] = None):
+                             noisy_action_projector=None, use_film: bool = False, noise=None, pad_to: Optional[int] = None, policy=None):
         """predict_action for B observations in one forward.  prompts: list of B (input_ids, attention_mask) pairs ([1, L_b] or [L_b], lengths may
         differ; masks right-padded), pixel_values [B, 6 I, H, W], proprio [B, proprio_dim], noise [B, chunk, action_dim] (diffusion: each sample's
         DDIM trajectory starts from its own noise).  Returns (actions [B, chunk, action_dim] unnormalised with `unnorm_key`, action hidden states
@@ -569,7 +656,11 @@ class OpenVLAForActionPrediction(_StoreModule):
         is in the batch and in whatever order (OVLA_BATCH_INVARIANT=0: the planner's schedules, for A/B measurement only).
         `pad_to` > B: the batch is filled to `pad_to` observations by repeating observation 0 (valid data, never zeros) and the extra outputs are
         dropped -- the same bits for the B real ones, and a caller with arbitrary arrival counts (the coalescing server) captures one graph per
-        bucket instead of one per count."""
+        bucket instead of one per count.
+        `policy` (a model with add_policy): one registered policy name per observation.  Each observation runs under its own policy's LoRA
+        adapters (all of them in the same launches: engine.LoraLinear adapter slots), L1 head, proprio projector and un-normalisation statistics
+        (`unnorm_key` is looked up in the policy's own norm_stats when it has them); without per-policy heads the discrete token path with the
+        shared lm_head.  `pad_to` repeats observation 0's policy.  FiLM models and diffusion heads are not supported with `policy`."""
         cfg = self.cfg
         if use_film != self.engine.use_film:
             raise ValueError(f"use_film={use_film} but the model was built with use_film={self.engine.use_film}")
@@ -578,6 +669,17 @@ class OpenVLAForActionPrediction(_StoreModule):
             raise ValueError("predict_action_batch: no observations")
         if pixel_values.shape[0] != B:
             raise ValueError(f"predict_action_batch: {B} prompts but pixel_values holds {pixel_values.shape[0]} observations")
+        if policy is not None:
+            policy = list(policy)
+            if self.engine.use_film or noisy_action_projector is not None or hasattr(action_head, "noise_scheduler"):
+                raise ValueError("predict_action_batch(policy=...): FiLM models and diffusion heads are not supported with per-request policies")
+            if action_head is not None or proprio_projector is not None:
+                raise ValueError("predict_action_batch(policy=...): the action head and the proprio projector come from each observation's policy")
+            if len(policy) != B:
+                raise ValueError(f"predict_action_batch: {len(policy)} policy names for {B} observations")
+            unknown = sorted({str(p) for p in policy if p not in self._policies})
+            if unknown:
+                raise ValueError(f"predict_action_batch: unknown policy {unknown} (registered: {list(self._policies)})")
         if pad_to is not None and pad_to > B:
             fill = [0] * (pad_to - B)
 
@@ -593,9 +695,11 @@ class OpenVLAForActionPrediction(_StoreModule):
             actions, hidden = self.predict_action_batch(list(prompts) + [prompts[0]] * len(fill), rep(pixel_values), unnorm_key=unnorm_key,
                                                         proprio=None if prop_p is None else prop_p.cpu().numpy(), proprio_projector=proprio_projector,
                                                         action_head=action_head, noisy_action_projector=noisy_action_projector, use_film=use_film,
-                                                        noise=rep(noise))
+                                                        noise=rep(noise), policy=None if policy is None else policy + [policy[0]] * len(fill))
             return actions[:B], hidden[:B]
         use_proprio = proprio_projector is not None and proprio is not None
+        if policy is not None:
+            use_proprio = proprio is not None and next(iter(self._policies.values()))["pp"] is not None
         prop = None
         if use_proprio:
             prop = torch.as_tensor(np.asarray(proprio), dtype=torch.float32)
@@ -624,6 +728,10 @@ class OpenVLAForActionPrediction(_StoreModule):
             ids[b, : len(r)], mask[b, : len(r)] = r, True
             labels[b, len(r) - A - 1: len(r)] = ACTION_TOKEN_BEGIN_IDX + 1
             labels[b, len(r) - 1] = STOP_INDEX
+        if policy is not None:
+            normalized, hidden = self._predict_batch_policies(policy, ids, mask, labels, pixel_values, prop, use_proprio, Lb)
+            stats = [self.policy_norm_stats(p) for p in policy]
+            return np.stack([self._unnormalize_actions(normalized[b], unnorm_key, stats[b]) for b in range(B)]), hidden
         film, film_avg = self.engine.use_film, None
         graphed = self.use_graph
         if film and not graphed:
@@ -712,11 +820,12 @@ class OpenVLAForActionPrediction(_StoreModule):
     def get_action_dim(self, unnorm_key=None) -> int:
         return len(self.norm_stats[self._check_unnorm_key(self.norm_stats, unnorm_key)]["action"]["min"])
 
-    def get_action_stats(self, unnorm_key=None):
-        return self.norm_stats[self._check_unnorm_key(self.norm_stats, unnorm_key)]["action"]
+    def get_action_stats(self, unnorm_key=None, norm_stats=None):
+        norm_stats = self.norm_stats if norm_stats is None else norm_stats   # a policy's own statistics (add_policy)
+        return norm_stats[self._check_unnorm_key(norm_stats, unnorm_key)]["action"]
 
-    def _unnormalize_actions(self, normalized_actions, unnorm_key=None):
-        stats = self.get_action_stats(unnorm_key)
+    def _unnormalize_actions(self, normalized_actions, unnorm_key=None, norm_stats=None):
+        stats = self.get_action_stats(unnorm_key, norm_stats)
         if self.cfg.norm_type == "bounds":
             mask = stats.get("mask", np.ones_like(stats["min"], dtype=bool))
             high, low = np.array(stats["max"]), np.array(stats["min"])

@@ -709,6 +709,54 @@ def gather_rows(src, index, dim, *, dst=None, scatter_add=False, n_dst_rows=None
     return dst
 
 
+def _host_slots(obs_slot, host_slots):
+    """The optional host copy of the assignment as a ctypes int32 array (None without one); the library validates it (OVLA_EINVAL).  The
+    caller holds the array until the call has returned."""
+    if host_slots is None:
+        return None
+    vals = [int(v) for v in host_slots]
+    assert len(vals) == obs_slot.numel(), "host_slots must mirror obs_slot"
+    return (ctypes.c_int32 * len(vals))(*vals)
+
+
+def lora_route(t, obs_slot, *, G, n, r, rows_per_obs, host_slots=None):
+    """Multi-adapter routing, in place (ovla.h: ovla_lora_route): t bf16 [M, ld >= G*n*r] keeps, per row, the r columns of its own observation's
+    slot in every group and gets +0 stored over the other slots' columns.  obs_slot: device int32 [n_obs]; row m belongs to observation
+    m // rows_per_obs.  host_slots (optional, the same values on the host): an entry outside [0, n) raises before anything is launched."""
+    _chk(t, name="t"); _chk(obs_slot, torch.int32, "obs_slot")
+    assert t.dim() == 2 and t.stride(1) == 1 and obs_slot.is_contiguous()
+    hs = _host_slots(obs_slot, host_slots)
+    g = STRUCTS["ovla_lora_route_args"]()
+    g.t, g.ld, g.obs_slot = t.data_ptr(), t.stride(0), obs_slot.data_ptr()
+    g.obs_slot_host = ctypes.cast(hs, ctypes.c_void_p).value if hs is not None else None
+    g.M, g.G, g.n, g.r, g.rows_per_obs, g.n_obs = t.shape[0], G, n, r, rows_per_obs, obs_slot.numel()
+    e0 = _prof_begin()
+    _lib.call("ovla_lora_route", g, _stream())
+    _prof_end(e0, "lora_route", 0.0)
+    return t
+
+
+def select_by_slot(src, obs_slot, *, rows_per_obs, rows=None, out=None, host_slots=None):
+    """out[m] = src[obs_slot[m // rows_per_obs], m] (ovla.h: ovla_select_by_slot): src bf16 / fp32 [n, R, dim] (dim contiguous, rows contiguous
+    inside a slot), the first `rows` (default R) rows of every slot are candidates -> out [rows, dim]."""
+    assert src.dim() == 3 and src.is_cuda and src.dtype in (BF16, torch.float32) and src.stride(2) == 1 and src.stride(1) == src.shape[2]
+    _chk(obs_slot, torch.int32, "obs_slot")
+    n, R, dim = src.shape
+    rows = R if rows is None else rows
+    assert 0 < rows <= R and obs_slot.is_contiguous()
+    if out is None:
+        out = torch.empty((rows, dim), dtype=src.dtype, device=src.device)
+    assert out.shape == (rows, dim) and out.dtype == src.dtype and out.is_contiguous()
+    hs = _host_slots(obs_slot, host_slots)
+    g = STRUCTS["ovla_select_by_slot_args"]()
+    g.src, g.dst, g.obs_slot = src.data_ptr(), out.data_ptr(), obs_slot.data_ptr()
+    g.obs_slot_host = ctypes.cast(hs, ctypes.c_void_p).value if hs is not None else None
+    g.src_slot_stride = src.stride(0)
+    g.n, g.rows, g.dim, g.rows_per_obs, g.n_obs, g.elem_bytes = n, rows, dim, rows_per_obs, obs_slot.numel(), src.element_size()
+    _lib.call("ovla_select_by_slot", g, _stream())
+    return out
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 def token_ce(logits, targets, *, vocab=None, grad_scale=None, inplace_grad=True):
     """Next-token cross entropy on gathered rows (ovla.h: ovla_token_ce): logits bf16 [rows, ld >= vocab], targets int64 [rows] ->

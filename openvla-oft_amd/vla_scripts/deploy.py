@@ -18,6 +18,11 @@ Differences, all deliberate:
     coalesced `/act` answer is bit-identical to `/act_batch([payload])` -- the fixed-schedule batch path at B = 1 -- whatever it was merged
     with.  It is NOT promised identical to the uncoalesced `/act`, which runs `predict_action` on the planner's schedules and is
     unchanged.  At `coalesce_ms == 0` (the default) no coalescer exists and both endpoints behave exactly as before.
+  * `policies={name: fine-tune output directory | dict of add_policy arguments}` (not in the reference): one BASE model serves several
+    fine-tuned policies.  A payload then names its policy under the key "policy"; requests of different policies share one batched forward
+    (every policy's adapters ride in the same launches: OpenVLAForActionPrediction.add_policy / predict_action_batch(policy=...)), coalesced
+    or not.  The coalescer knows nothing of it: the name travels inside the item.  An unknown or missing name answers "error" like any
+    malformed payload.  With no policies configured a payload without "policy" is served exactly as before.
 """
 from __future__ import annotations
 
@@ -102,19 +107,33 @@ class DeployConfig:
 
 
 class OpenVLAServer:
-    def __init__(self, cfg, *, vla=None, processor=None, action_head=None, proprio_projector=None, noisy_action_projector=None):
+    def __init__(self, cfg, *, vla=None, processor=None, action_head=None, proprio_projector=None, noisy_action_projector=None, policies=None):
         self.cfg = cfg
         self.vla = vla if vla is not None else U.get_vla(cfg)
+        self.policies = tuple(policies) if policies else ()
+        for name, spec in (policies or {}).items():   # head, proprio projector and statistics come with each policy
+            if name in self.vla.policies:
+                continue
+            if isinstance(spec, dict):
+                self.vla.add_policy(name, **spec)
+            else:
+                U.get_policy(cfg, self.vla, name, spec)
         self.proprio_projector = proprio_projector
-        if self.proprio_projector is None and cfg.use_proprio:
+        if self.proprio_projector is None and cfg.use_proprio and not self.policies:
             self.proprio_projector = U.get_proprio_projector(cfg, self.vla.llm_dim, C.PROPRIO_DIM)
         self.action_head = action_head
-        if self.action_head is None and (cfg.use_l1_regression or cfg.use_diffusion):
+        if self.action_head is None and (cfg.use_l1_regression or cfg.use_diffusion) and not self.policies:
             self.action_head = U.get_action_head(cfg, self.vla.llm_dim)
         self.noisy_action_projector = noisy_action_projector
-        if self.noisy_action_projector is None and cfg.use_diffusion:
+        if self.noisy_action_projector is None and cfg.use_diffusion and not self.policies:
             self.noisy_action_projector = U.get_noisy_action_projector(cfg, self.vla.llm_dim)
-        assert cfg.unnorm_key in self.vla.norm_stats, f"Action un-norm key {cfg.unnorm_key} not found in VLA `norm_stats`!"
+        if self.policies:
+            if action_head is not None or proprio_projector is not None or noisy_action_projector is not None:
+                raise ValueError("OpenVLAServer(policies=...): heads and projectors come with each policy")
+            for name in self.policies:
+                assert cfg.unnorm_key in self._norm_stats(name), f"Action un-norm key {cfg.unnorm_key} not found in the `norm_stats` of policy {name}!"
+        else:
+            assert cfg.unnorm_key in self.vla.norm_stats, f"Action un-norm key {cfg.unnorm_key} not found in VLA `norm_stats`!"
         self.processor = processor if processor is not None else U.get_processor(cfg)
         if getattr(cfg, "graph_replay", True):   # every head, the diffusion sampler included (engine.DiffusionGraph)
             self.vla.enable_graph_replay(True)
@@ -128,9 +147,23 @@ class OpenVLAServer:
             self._coalescer = RequestCoalescer(self._run_batch, coalesce_ms=cfg.coalesce_ms, max_batch=getattr(cfg, "max_batch", 8), buckets=buckets)
 
     # -- coalescing mode: the worker thread of self._coalescer is the only thread that touches the engine ---------------------------------
-    def _proprio_dim(self) -> Optional[int]:
+    def _norm_stats(self, policy: Optional[str]) -> dict:
+        return self.vla.policy_norm_stats(policy) if policy is not None else self.vla.norm_stats
+
+    def _policy_of(self, observation) -> Optional[str]:
+        """The payload's policy name, checked against the configured set (None on a server without policies)."""
+        name = observation.get("policy") if isinstance(observation, dict) else None
+        if not self.policies:
+            if name is not None:
+                raise ValueError(f"the payload names policy {name!r} but this server has no policies configured")
+            return None
+        if not isinstance(name, str) or name not in self.policies:
+            raise ValueError(f"the payload needs a 'policy' out of {list(self.policies)}, got {name!r}")
+        return name
+
+    def _proprio_dim(self, policy: Optional[str] = None) -> Optional[int]:
         """Length of the state vector the un-normalisation statistics are for (None: the checkpoint carries none, nothing to compare with)."""
-        stats = self.vla.norm_stats.get(self.cfg.unnorm_key, {}).get("proprio")
+        stats = self._norm_stats(policy).get(self.cfg.unnorm_key, {}).get("proprio")
         for k in ("q01", "min", "q99", "max"):
             if stats and k in stats:
                 return len(stats[k])
@@ -143,6 +176,7 @@ class OpenVLAServer:
         observation, double = decode_payload(payload)
         if not isinstance(observation, dict) or not isinstance(observation.get("instruction"), str):
             raise ValueError("the payload needs an 'instruction' string")
+        policy = self._policy_of(observation)
         image = observation.get("full_image")
         if not isinstance(image, np.ndarray) or image.ndim != 3 or image.shape[-1] != 3:
             raise ValueError("the payload needs a 'full_image' array of shape [H, W, 3]")
@@ -150,7 +184,7 @@ class OpenVLAServer:
             if "state" not in observation:
                 raise ValueError("the payload needs a 'state' array (use_proprio)")
             state = np.asarray(observation["state"])
-            want = self._proprio_dim()
+            want = self._proprio_dim(policy)
             if state.ndim != 1 or state.dtype.kind not in "fiu" or (want is not None and state.shape[0] != want):
                 raise ValueError(f"'state' must be a numeric vector of length {want}, got dtype {state.dtype} shape {state.shape}")
         return observation, double
@@ -162,7 +196,8 @@ class OpenVLAServer:
         observations = [dict(o) for o, _ in items]
         actions = U.get_vla_action_batch(self.cfg, self.vla, self.processor, observations, [o["instruction"] for o in observations],
                                          action_head=self.action_head, proprio_projector=self.proprio_projector,
-                                         noisy_action_projector=self.noisy_action_projector, use_film=self.cfg.use_film, pad_to=pad_to)
+                                         noisy_action_projector=self.noisy_action_projector, use_film=self.cfg.use_film, pad_to=pad_to,
+                                         policies=[o["policy"] for o in observations] if self.policies else None)
         return [json.dumps(_encode(a)) if double else _encode(a) for a, (_, double) in zip(actions, items)]
 
     def close(self) -> None:
@@ -178,6 +213,9 @@ class OpenVLAServer:
                 return self._coalescer.submit(self._decode_valid(payload))
             observation, double = decode_payload(payload)
             instruction = observation["instruction"]
+            if self._policy_of(observation) is not None:   # a policy request always takes the batch path (at B = 1): that is where the slots are routed
+                with self._lock:
+                    return self._run_batch([(observation, double)], None)[0]
             with self._lock:      # one engine, static graph buffers: serialise (the reference does not lock)
                 action = U.get_vla_action(self.cfg, self.vla, self.processor, observation, instruction, action_head=self.action_head,
                                           proprio_projector=self.proprio_projector, noisy_action_projector=self.noisy_action_projector,
@@ -198,6 +236,9 @@ class OpenVLAServer:
             if self._coalescer is not None:   # through the same worker, as one pre-formed group
                 return self._coalescer.submit_group([self._decode_valid(p) for p in payloads])
             decoded = [decode_payload(p) for p in payloads]
+            if any(self._policy_of(o) is not None for o, _ in decoded):
+                with self._lock:
+                    return self._run_batch(decoded, None)
             observations = [o for o, _ in decoded]
             instructions = [o["instruction"] for o in observations]
             with self._lock:
