@@ -39,14 +39,18 @@ OVLA_DEV float gelu_erf_grad(float x) {
   const float pdf = 0.39894228040143267794f * __expf(-0.5f * x * x);
   return cdf + x * pdf;
 }
+// tanh-GELU, 0.5 x (1 + tanh u) with u = k (x + c x^3), evaluated as x * sigmoid(2 u): the same function, but 1 + tanhf(u) cancels in fp32 for
+// x < -4 (tanhf returns -1 or its neighbour: the result was -0 or -1.5e-7 where the value is 1e-8 ... 1e-10, hundreds of bf16 ulps), and
+// sigmoid keeps its relative accuracy down to x = -7.2, where __expf overflows and the result is the -0 the value has underflowed to anyway.
+// The derivative likewise: 0.5 (1 + t) = s and 1 - t^2 = 4 s (1 - s).
 OVLA_DEV float gelu_tanh(float x) {
   const float k = 0.7978845608028654f, c = 0.044715f;
-  return 0.5f * x * (1.0f + tanhf(k * (x + c * x * x * x)));
+  return x / (1.0f + __expf(-2.0f * k * (x + c * x * x * x)));
 }
 OVLA_DEV float gelu_tanh_grad(float x) {
   const float k = 0.7978845608028654f, c = 0.044715f;
-  const float t = tanhf(k * (x + c * x * x * x));
-  return 0.5f * (1.0f + t) + 0.5f * x * (1.0f - t * t) * k * (1.0f + 3.0f * c * x * x);
+  const float s = 1.0f / (1.0f + __expf(-2.0f * k * (x + c * x * x * x)));
+  return s * (1.0f + 2.0f * x * (1.0f - s) * k * (1.0f + 3.0f * c * x * x));
 }
 OVLA_DEV float silu(float x) { return x / (1.0f + __expf(-x)); }
 OVLA_DEV float sigmoidf_(float x) { return 1.0f / (1.0f + __expf(-x)); }

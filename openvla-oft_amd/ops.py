@@ -97,8 +97,9 @@ def check_device(index: int = 0) -> None:
 
 # ----------------------------------------------------------------------------------------------------------------------
 def gemm(a, b, *, out=None, bias=None, act=ACT_NONE, residual=None, colscale=None, c_pre=None, a2=None, b2=None,
-         k2_group_n=0, film=None, split_k=1, tile=0, alpha=1.0, a_group_n=0, dact=None, rope=None, rowsq_out=None, rowscale=None):
-    """out[M,N] = epilogue(a[M,K] @ b[N,K]^T (+ a2[M,G*K2] @ b2[N,K2]^T)); all bf16 2-D, last dim contiguous."""
+         k2_group_n=0, film=None, split_k=1, tile=0, alpha=1.0, a_group_n=0, dact=None, rope=None, rowsq_out=None, rowscale=None, schedule=None):
+    """out[M,N] = epilogue(a[M,K] @ b[N,K]^T (+ a2[M,G*K2] @ b2[N,K2]^T)); all bf16 2-D, last dim contiguous.
+    schedule=(tile, splits): run under exactly this fixed schedule (ovla_gemm_bf16_fixed) instead of the planner's or the cost model's choice."""
     _chk(a, name="a"); _chk(b, name="b")
     M, K = a.shape
     N = b.shape[0]
@@ -150,6 +151,16 @@ def gemm(a, b, *, out=None, bias=None, act=ACT_NONE, residual=None, colscale=Non
         parts, eps, rbuf = rowscale
         assert parts.dtype == torch.float32 and parts.shape == (M, K // 64) and parts.is_contiguous() and rbuf.dtype == torch.float32 and rbuf.numel() >= M
         g.rowscale_part, g.rowscale_slots, g.rowscale_eps, g.rowscale_r = parts.data_ptr(), K // 64, eps, rbuf.data_ptr()
+    if schedule is not None:   # the caller's fixed schedule: the library refuses what it cannot run (block-diagonal mode, backward epilogues, tile / split_k)
+        sched = STRUCTS["ovla_gemm_schedule"]()
+        sched.tile, sched.splits = schedule
+        g.M, g.N, g.K, g.act, g.split_k, g.tile, g.alpha, g.a_group_n = M, N, K, act, split_k, tile, alpha, a_group_n
+        ws = _workspace(a.device, max(gemm_fixed_workspace_bytes(M, N, sched), _WS_BYTES))
+        g.workspace, g.workspace_bytes = ws.data_ptr(), ws.numel() * 4
+        e0 = _prof_begin()
+        _lib.check(_lib.lib().ovla_gemm_bf16_fixed(ctypes.byref(g), ctypes.byref(sched), _stream()), "ovla_gemm_bf16_fixed")
+        _prof_end(e0, f"gemm_fixed_t{sched.tile}s{sched.splits}", 2.0 * M * N * (K + g.K2))
+        return out
     if getattr(_mode, "invariant", False) and dact is None and not a_group_n:   # batch-invariant mode: the caller's tile / split_k give way to the fixed schedule
         g.M, g.N, g.K, g.act, g.split_k, g.tile, g.alpha = M, N, K, act, 0, 0, alpha
         general = (act not in (ACT_NONE, ACT_SWIGLU) or c_pre is not None or colscale is not None or film is not None
