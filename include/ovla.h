@@ -473,7 +473,7 @@ int ovla_gather_rows(const ovla_gather_rows_args* a, void* stream);
  * mean) -- the caller gathers the rows whose shifted label is not ignored, so only those rows reach lm_head).
  * logits bf16 [rows, ld] (read as fp32, as `.float()` does) ; targets int64 [rows] in [0, vocab)
  *   loss_rows[r] = logsumexp(logits[r, :vocab]) - logits[r, target[r]]   (fp32)
- *   argmax[r]    = lowest index of the row maximum                       (predicted_token_ids, finetune.py:358)
+ *   argmax[r]    = lowest index of the row maximum                       (predicted_token_ids, finetune.py:358); 0 for a row that is all -inf or only NaN
  *   dlogits[r,j] = bf16((softmax(logits[r])[j] - [j == target[r]]) * grad_scale)   (optional; may alias logits)
  * grad_scale = loss_scale / number of non-ignored tokens in the batch (the mean's 1/N and the grad-accumulation divide). */
 typedef struct {

@@ -39,21 +39,36 @@ OVLA_DEV float gelu_erf_grad(float x) {
   const float pdf = 0.39894228040143267794f * __expf(-0.5f * x * x);
   return cdf + x * pdf;
 }
+// The sigmoid family is 1 / (1 + e) with e = __expf(-x), which overflows to inf at x = -88.7 although the result does not underflow before
+// x = -104: up to there the value is exp(x) (x exp(x) for SiLU) to fp32 accuracy, 1e-39 ... 4e-37 after the factors that multiply it -- normal
+// bf16 numbers that the overflow turned into 0.  exp2f (unlike __expf's bare v_exp_f32) returns denormals.  The select is taken only when e
+// is inf, where the old result was 0: every result computed from a finite e keeps its bits.
+OVLA_DEV float exp_tail(float x) { return exp2f(x * 1.44269504088896340736f); }
+OVLA_DEV float sigmoidf_(float x) {
+  const float e = __expf(-x);
+  return e == INFINITY ? exp_tail(x) : 1.0f / (1.0f + e);
+}
 // tanh-GELU, 0.5 x (1 + tanh u) with u = k (x + c x^3), evaluated as x * sigmoid(2 u): the same function, but 1 + tanhf(u) cancels in fp32 for
 // x < -4 (tanhf returns -1 or its neighbour: the result was -0 or -1.5e-7 where the value is 1e-8 ... 1e-10, hundreds of bf16 ulps), and
-// sigmoid keeps its relative accuracy down to x = -7.2, where __expf overflows and the result is the -0 the value has underflowed to anyway.
-// The derivative likewise: 0.5 (1 + t) = s and 1 - t^2 = 4 s (1 - s).
+// sigmoid keeps its relative accuracy down to x = -10.1, where __expf overflows (gelu_tanh then returns -0 for a value below 1e-37; its
+// derivative goes on through sigmoidf_'s tail).
+// The derivative likewise: 0.5 (1 + t) = s and 1 - t^2 = 4 s (1 - s).  Its polynomial factor takes x clamped to [-16, 16] (one v_med3): beyond
+// |x| = 16 the sigmoid is exactly 0 or 1 in fp32, the factor only has to stay finite (unclamped it overflows from |x| = 2e13 and the product
+// was 0 * inf = NaN), and inside the clamp is the identity, so every bit a finite result had is unchanged.  s keeps the raw x: NaN in, NaN out.
 OVLA_DEV float gelu_tanh(float x) {
   const float k = 0.7978845608028654f, c = 0.044715f;
   return x / (1.0f + __expf(-2.0f * k * (x + c * x * x * x)));
 }
 OVLA_DEV float gelu_tanh_grad(float x) {
   const float k = 0.7978845608028654f, c = 0.044715f;
-  const float s = 1.0f / (1.0f + __expf(-2.0f * k * (x + c * x * x * x)));
-  return s * (1.0f + 2.0f * x * (1.0f - s) * k * (1.0f + 3.0f * c * x * x));
+  const float s = sigmoidf_(2.0f * k * (x + c * x * x * x));
+  const float xc = fminf(fmaxf(x, -16.0f), 16.0f);
+  return s * (1.0f + 2.0f * xc * (1.0f - s) * k * (1.0f + 3.0f * c * xc * xc));
 }
-OVLA_DEV float silu(float x) { return x / (1.0f + __expf(-x)); }
-OVLA_DEV float sigmoidf_(float x) { return 1.0f / (1.0f + __expf(-x)); }
+OVLA_DEV float silu(float x) {
+  const float e = __expf(-x);
+  return e == INFINITY ? x * exp_tail(x) : x / (1.0f + e);
+}
 
 OVLA_DEV float apply_act(float v, int act) {
   switch (act) {

@@ -446,7 +446,7 @@ __global__ __launch_bounds__(256) void token_ce_kernel(const bf16_bits* __restri
   if (tid == 0) {
     float bm = red_f[0]; int bi = red_i[0];
     for (int w = 1; w < 4; ++w) if (red_f[w] > bm || (red_f[w] == bm && red_i[w] < bi)) { bm = red_f[w]; bi = red_i[w]; }
-    bc_f[0] = bm; bc_i = bi;
+    bc_f[0] = bm; bc_i = bi >= vocab ? 0 : bi;   // a row that is all -inf or holds only NaN (no column ever compared greater): column 0, argmax_bins_kernel's rule
   }
   __syncthreads();
   m = bc_f[0];

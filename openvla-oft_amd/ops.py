@@ -489,30 +489,33 @@ def rope_(qk, S, n_heads, hd, cos, sin, inverse=False):
     return qk
 
 
-def swiglu_fwd(gu):
+def swiglu_fwd(gu, out=None):
     _chk(gu)
     rows, F2 = gu.shape
-    h = torch.empty((rows, F2 // 2), dtype=BF16, device=gu.device)
+    h = torch.empty((rows, F2 // 2), dtype=BF16, device=gu.device) if out is None else out
+    assert h.shape == (rows, F2 // 2) and h.dtype == BF16 and h.is_contiguous()
     g = STRUCTS["ovla_swiglu_fwd_args"]()
     g.gu, g.h, g.rows, g.F = gu.data_ptr(), h.data_ptr(), rows, F2 // 2
     _lib.call("ovla_swiglu_fwd", g, _stream())
     return h
 
 
-def swiglu_bwd(gu, dh):
+def swiglu_bwd(gu, dh, out=None):
     _chk(gu); _chk(dh)
     rows, F2 = gu.shape
-    dgu = torch.empty_like(gu)
+    dgu = torch.empty_like(gu) if out is None else out
+    assert dgu.shape == gu.shape and dgu.dtype == BF16 and dgu.is_contiguous()
     g = STRUCTS["ovla_swiglu_bwd_args"]()
     g.gu, g.dh, g.dgu, g.rows, g.F = gu.data_ptr(), dh.data_ptr(), dgu.data_ptr(), rows, F2 // 2
     _lib.call("ovla_swiglu_bwd", g, _stream())
     return dgu
 
 
-def act_bwd(z, dh, act):
+def act_bwd(z, dh, act, out=None):
     _chk(z); _chk(dh)
     assert z.is_contiguous() and dh.is_contiguous()
-    dz = torch.empty_like(z)
+    dz = torch.empty_like(z) if out is None else out
+    assert dz.shape == z.shape and dz.dtype == BF16 and dz.is_contiguous()
     g = STRUCTS["ovla_act_bwd_args"]()
     g.z, g.dh, g.dz, g.n, g.act = z.data_ptr(), dh.data_ptr(), dz.data_ptr(), z.numel(), act
     _lib.call("ovla_act_bwd", g, _stream())
@@ -552,9 +555,10 @@ def im2col(pixels, c0, patch, k_padded, n_img=1, img_cstride=6):
     return out
 
 
-def vit_embed(patches, pos, prefix, B, n_patches, dim):
+def vit_embed(patches, pos, prefix, B, n_patches, dim, out=None):
     n_prefix = 0 if prefix is None else prefix.shape[0]
-    tokens = torch.empty((B * (n_patches + n_prefix), dim), dtype=BF16, device=patches.device)
+    tokens = torch.empty((B * (n_patches + n_prefix), dim), dtype=BF16, device=patches.device) if out is None else out
+    assert tokens.shape == (B * (n_patches + n_prefix), dim) and tokens.dtype == BF16 and tokens.is_contiguous()
     g = STRUCTS["ovla_vit_embed_args"]()
     g.patches, g.pos, g.prefix, g.tokens = patches.data_ptr(), pos.data_ptr(), _p(prefix), tokens.data_ptr()
     g.B, g.n_patches, g.n_prefix, g.dim = B, n_patches, n_prefix, dim
@@ -769,10 +773,10 @@ def select_by_slot(src, obs_slot, *, rows_per_obs, rows=None, out=None, host_slo
 
 
 # ----------------------------------------------------------------------------------------------------------------------
-def token_ce(logits, targets, *, vocab=None, grad_scale=None, inplace_grad=True):
+def token_ce(logits, targets, *, vocab=None, grad_scale=None, inplace_grad=True, dlogits=None):
     """Next-token cross entropy on gathered rows (ovla.h: ovla_token_ce): logits bf16 [rows, ld >= vocab], targets int64 [rows] ->
     (loss_rows fp32 [rows], argmax int32 [rows], dlogits bf16 or None).  With grad_scale the gradient overwrites `logits`
-    (inplace_grad) or goes to a new tensor."""
+    (inplace_grad), goes to `dlogits` (bf16 [rows, ld_d >= vocab]) when one is given, or to a new tensor."""
     _chk(logits)
     rows = logits.shape[0]
     vocab = logits.shape[1] if vocab is None else vocab
@@ -781,7 +785,8 @@ def token_ce(logits, targets, *, vocab=None, grad_scale=None, inplace_grad=True)
     amax = torch.empty(rows, dtype=torch.int32, device=logits.device)
     d = None
     if grad_scale is not None:
-        d = logits if inplace_grad else torch.empty_like(logits)
+        d = dlogits if dlogits is not None else (logits if inplace_grad else torch.empty_like(logits))
+        assert d.dtype == BF16 and d.shape[0] == rows and d.shape[1] >= vocab and d.stride(1) == 1
     g = STRUCTS["ovla_token_ce_args"]()
     g.logits, g.ld, g.targets, g.loss_rows, g.argmax = logits.data_ptr(), logits.stride(0), targets.data_ptr(), loss_rows.data_ptr(), amax.data_ptr()
     g.dlogits, g.ld_d = _p(d), (d.stride(0) if d is not None else 0)
@@ -839,10 +844,11 @@ def ddim_step(sample, eps, coef, step):
     return sample
 
 
-def head_out_fwd(x, W, b, target=None, loss_sum=None, mse=False):
+def head_out_fwd(x, W, b, target=None, loss_sum=None, mse=False, out=None):
     rows, dim = x.shape
     adim = W.shape[0]
-    pred = torch.empty((rows, adim), dtype=BF16, device=x.device)
+    pred = torch.empty((rows, adim), dtype=BF16, device=x.device) if out is None else out
+    assert pred.shape == (rows, adim) and pred.dtype == BF16 and pred.is_contiguous()
     g = STRUCTS["ovla_head_out_fwd_args"]()
     g.x, g.W, g.b, g.pred, g.target, g.loss_sum = x.data_ptr(), W.data_ptr(), _p(b), pred.data_ptr(), _p(target), _p(loss_sum)
     g.rows, g.dim, g.adim, g.mse = rows, dim, adim, int(mse)
@@ -881,11 +887,12 @@ def head_tail_fwd(x0, blocks, ln2, out_w, out_b, *, rows_real, target=None, loss
     return out
 
 
-def head_out_bwd(x, W, pred, target, dloss_scale, dW, db, mse=False, dpred=None):
+def head_out_bwd(x, W, pred, target, dloss_scale, dW, db, mse=False, dpred=None, out=None):
     """Backward of the head tail.  Either (pred, target, dloss_scale) -- fused L1/MSE gradient -- or an explicit dpred."""
     rows, dim = x.shape
     adim = W.shape[0]
-    dx = torch.empty_like(x)
+    dx = torch.empty_like(x) if out is None else out
+    assert dx.shape == x.shape and dx.dtype == BF16 and dx.is_contiguous()
     g = STRUCTS["ovla_head_out_bwd_args"]()
     g.x, g.W, g.pred, g.target, g.dpred = x.data_ptr(), W.data_ptr(), _p(pred), _p(target), _p(dpred)
     g.dloss_scale, g.mse = dloss_scale, int(mse)

@@ -311,13 +311,15 @@ def test_swiglu_pair_epilogue(ops, dev, tile):
 @pytest.mark.parametrize("tile", [1, 101, 17, 10, 18], ids=tname)
 def test_backward_epilogues(ops, dev, tile):
     """dact_mode 1 with each activation (ReLU exact, the others within 1 ulp; erf-GELU + 2e-7 |z|) and dact_mode 2 with ldc = ld_dact = 2 N + 8
-    (within 2 ulps; guard columns untouched).  Saved pre-activations are multiples of 1/4 in [-6, 6], the incoming gradient 2^-5 acc stays below 8."""
+    (within 2 ulps; guard columns untouched).  Saved pre-activations are multiples of 1/4 in [-6, 6], the incoming gradient 2^-5 acc stays below 8.
+    Row 0 also holds the extreme pre-activations -2e13, -1e19, -3e38 and +3e38 (the derivative there is 0 or 1; an unclamped tanh-GELU' is 0 * inf)."""
     c, fails = cfg_of(tile), Failures()
     g = R.rng(8000 + tile)
     M, N, K, alpha = c.BM + 37, c.BN + 24, 64, 2.0 ** -5
     a, b = R.operand(g, M, K), R.operand(g, N, K)
     ad, bd = a.to(dev), b.to(dev)
     z = (R.ints(g, (M, N), -24, 24).float() * 0.25).to(BF)
+    z[0, :4] = torch.tensor([-2e13, -1e19, -3e38, 3e38]).to(BF)
     for act, name in [(R.ACT_GELU, "gelu"), (R.ACT_RELU, "relu"), (R.ACT_SILU, "silu"), (R.ACT_GELU_TANH, "gelu_tanh")]:
         ref = R.reference(a, b, alpha=alpha, dact=("act", z, act))
         out = ops.gemm(ad, bd, alpha=alpha, dact=("act", z.to(dev), act), tile=tile)
