@@ -1082,6 +1082,14 @@ class VLAEngine:
         preds = torch.stack([h.fwd(ah)[0] for h in heads])                   # [n, B * chunk, action_dim]
         return ops.select_by_slot(preds, self.route.obs_slot, rows_per_obs=self.cfg.chunk, host_slots=self.route.host_slots)
 
+    def lm_head_rows(self, hidden_rows):
+        """lm_head on hidden rows [n, D] -> bf16 logits [n rounded up to a multiple of 8 (the GEMM's M granularity), vocab]; the rows past n are
+        those of zero inputs."""
+        n = hidden_rows.shape[0]
+        rows = torch.zeros(((n + 7) // 8 * 8, self.cfg.llm_dim), dtype=BF16, device=self.device)
+        rows[:n] = hidden_rows
+        return ops.gemm(rows, self.lm_head)
+
     def merged_state_dict(self) -> Dict[str, torch.Tensor]:
         """Base VLM weights under the reference's HF key layout (un-fused q/k/v, gate/up), after merge_lora(): what
         merge_lora_weights_and_save.py writes with `save_pretrained`."""
@@ -1538,9 +1546,61 @@ class VLAEngine:
 
 
 # ======================================================================================================================
+# what the two inference graphs below share
+# ======================================================================================================================
+class _StaticInputs:
+    """What ChunkGraph and DiffusionGraph share: the static device buffers that load() fills before a replay (ids / labels / text lengths /
+    pixels / proprio), the ragged FiLM average at the head of a captured forward, and the rule for a capture (one eager warm-up, then the
+    capture with a workspace cache of its own)."""
+
+    def __init__(self, engine: "VLAEngine", B: int, L: int, pixel_shape, use_proprio: bool, invariant: bool, film: bool):
+        if film and not engine.use_film:
+            raise ValueError(f"{type(self).__name__}(film=True) needs an engine built with use_film=True")
+        dev = engine.device
+        self.engine, self.B, self.L = engine, B, L
+        self.invariant = invariant   # capture every GEMM under its fixed schedule (ops.batch_invariant): the batched inference API
+        self.film = film
+        self.ids = torch.zeros((B, L), dtype=torch.int64, device=dev)
+        self.lab = torch.full((B, L), -100, dtype=torch.int64, device=dev)
+        self.lens = torch.full((B,), L, dtype=torch.int32, device=dev)
+        self.pixels = torch.zeros(tuple(pixel_shape), dtype=BF16, device=dev)
+        self.proprio = torch.zeros((B, engine.cfg.proprio_dim), dtype=BF16, device=dev) if use_proprio else None
+
+    def load(self, input_ids, attention_mask, pixel_values, labels, proprio=None):
+        lens = VLAEngine.check_right_padding(attention_mask)
+        assert tuple(input_ids.shape) == (self.B, self.L), f"{type(self).__name__} captured for ids {(self.B, self.L)}, got {tuple(input_ids.shape)}"
+        self.ids.copy_(input_ids.to(torch.int64), non_blocking=True)
+        self.lab.copy_(labels.to(torch.int64), non_blocking=True)
+        self.lens.copy_(lens.to(torch.int32), non_blocking=True)
+        self.pixels.copy_(pixel_values.reshape(self.pixels.shape), non_blocking=True)
+        if self.proprio is not None:
+            self.proprio.copy_(proprio.reshape(self.proprio.shape), non_blocking=True)
+
+    def _film_average(self):
+        """film=True: the conditioning vectors of the static ids / labels / lengths, one ragged launch; otherwise None (the engine's own rule)."""
+        if not self.film:
+            return None
+        eng = self.engine
+        film_avg = torch.zeros(((self.B + 7) // 8 * 8, eng.cfg.llm_dim), dtype=BF16, device=eng.device)
+        return ops.language_average_ragged(self.ids, self.lab, self.lens, eng.embed, film_avg)
+
+    @contextlib.contextmanager
+    def _capturing(self, warm_up):
+        """Call after load() of a representative input.  Runs `warm_up` eagerly once (lazy tables, kernel attributes); inside, the captures."""
+        assert ops.PROFILE is None, "no per-launch event timing inside a graph capture"
+        warm_up()
+        torch.cuda.synchronize(self.engine.device)
+        outer_ws, ops._ws_cache = ops._ws_cache, {}          # workspaces allocated while capturing belong to the graphs' pools
+        try:
+            yield
+        finally:
+            self._ws, ops._ws_cache = ops._ws_cache, outer_ws
+
+
+# ======================================================================================================================
 # hipGraph replay of the single-chunk inference forward (BASELINE.json configs[1])
 # ======================================================================================================================
-class ChunkGraph:
+class ChunkGraph(_StaticInputs):
     """The batch-B inference forward (vision towers on their two streams -> projector -> assembly -> Llama stack -> action
     row gather -> optional L1 head) captured ONCE as a hipGraph and replayed per observation: ~1.3 k kernel launches become
     one graph launch, which is what bounds batch-1 latency.  Inputs are copied into static device buffers before each
@@ -1575,21 +1635,14 @@ class ChunkGraph:
             self.obs_slot = torch.zeros(B, dtype=torch.int32, device=dev)
             if use_proprio:
                 proprio_projector = SlotProjectors([p for _, p in policies], engine.route)
-        self.engine, self.head, self.B, self.L = engine, head, B, L
-        self.invariant = invariant   # capture every GEMM under its fixed schedule (ops.batch_invariant): the batched inference API
-        if film and not engine.use_film:
-            raise ValueError("ChunkGraph(film=True) needs an engine built with use_film=True")
+        super().__init__(engine, B, L, pixel_shape, use_proprio, invariant, film)
+        self.head = head
         if discrete and (head is not None or engine.lm_head is None):
             raise ValueError("ChunkGraph(discrete=True) is the token path: no action head, and the checkpoint's lm_head must be loaded")
-        self.film, self.discrete = film, discrete
+        self.discrete = discrete
         self.n_tokens = n_tokens if n_tokens is not None else engine.cfg.vocab - engine.cfg.pad_to_multiple_of   # modeling_prismatic.py:732
         self.n_bins = n_bins if n_bins is not None else engine.cfg.n_action_bins - 1                              # bin_centers.shape[0]
         self.proprio_projector = proprio_projector
-        self.ids = torch.zeros((B, L), dtype=torch.int64, device=dev)
-        self.lab = torch.full((B, L), -100, dtype=torch.int64, device=dev)
-        self.lens = torch.full((B,), L, dtype=torch.int32, device=dev)
-        self.pixels = torch.zeros(tuple(pixel_shape), dtype=BF16, device=dev)
-        self.proprio = torch.zeros((B, engine.cfg.proprio_dim), dtype=BF16, device=dev) if use_proprio else None
         self.graph = None
         self.out = None
         self.captures = 0
@@ -1602,29 +1655,20 @@ class ChunkGraph:
 
     def _run_routed(self):
         eng = self.engine
-        D = eng.cfg.llm_dim
         with ops.batch_invariant(self.invariant):
-            film_avg = None
-            if self.film:
-                film_avg = torch.zeros(((self.B + 7) // 8 * 8, D), dtype=BF16, device=eng.device)
-                ops.language_average_ragged(self.ids, self.lab, self.lens, eng.embed, film_avg)
             out = eng.forward_dev(self.ids, self.lab, self.lens, self.pixels, proprio=self.proprio, train=False,
-                                  proprio_projector=self.proprio_projector, sel="actions", film_avg=film_avg)
+                                  proprio_projector=self.proprio_projector, sel="actions", film_avg=self._film_average())
             ah, _ = eng.action_hidden(out)
             pred = self.head.fwd(ah)[0] if self.head is not None else None
             if self.policies is not None and self.slot_heads is not None:
                 pred = eng.policy_heads_fwd(ah, self.slot_heads)
-            if self.discrete:   # modeling.logits_for's row padding and GEMM, then the decode on the bf16 logits
-                n = ah.shape[0]
-                rows = torch.zeros(((n + 7) // 8 * 8, D), dtype=BF16, device=eng.device)
-                rows[:n] = ah
-                tok, bins = ops.argmax_bins(ops.gemm(rows, eng.lm_head)[:n], n_tokens=self.n_tokens, n_bins=self.n_bins)
+            if self.discrete:   # modeling.logits_for's GEMM, then the decode on the bf16 logits
+                tok, bins = ops.argmax_bins(eng.lm_head_rows(ah)[: ah.shape[0]], n_tokens=self.n_tokens, n_bins=self.n_bins)
                 return pred, ah, tok, bins
         return pred, ah
 
     def load(self, input_ids, attention_mask, pixel_values, labels, proprio=None, slots=None):
-        lens = VLAEngine.check_right_padding(attention_mask)
-        assert tuple(input_ids.shape) == (self.B, self.L), f"ChunkGraph captured for ids {(self.B, self.L)}, got {tuple(input_ids.shape)}"
+        super().load(input_ids, attention_mask, pixel_values, labels, proprio)
         if (slots is None) != (self.obs_slot is None):
             raise ValueError("ChunkGraph.load: `slots` goes with a graph built with policies=")
         if slots is not None:   # the host sees the values here: an out-of-range slot never reaches a kernel
@@ -1632,26 +1676,14 @@ class ChunkGraph:
             if len(slots) != self.B or any(not 0 <= v < len(self.policies) for v in slots):
                 raise ValueError(f"ChunkGraph.load: slots {slots} for {self.B} observations and {len(self.policies)} policies")
             self.obs_slot.copy_(torch.tensor(slots, dtype=torch.int32), non_blocking=True)
-        self.ids.copy_(input_ids.to(torch.int64), non_blocking=True)
-        self.lab.copy_(labels.to(torch.int64), non_blocking=True)
-        self.lens.copy_(lens.to(torch.int32), non_blocking=True)
-        self.pixels.copy_(pixel_values.reshape(self.pixels.shape), non_blocking=True)
-        if self.proprio is not None:
-            self.proprio.copy_(proprio.reshape(self.proprio.shape), non_blocking=True)
 
     def capture(self):
         """Call after load() of a representative input: one eager warm-up (lazy tables, kernel attributes), then the capture."""
-        assert ops.PROFILE is None, "no per-launch event timing inside a graph capture"
-        self._run()
-        torch.cuda.synchronize(self.engine.device)
-        outer_ws, ops._ws_cache = ops._ws_cache, {}          # workspaces allocated while capturing belong to the graph's pool
-        try:
+        with self._capturing(self._run):
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph):
                 self.out = self._run()
             self.captures += 1
-        finally:
-            self._ws, ops._ws_cache = ops._ws_cache, outer_ws
         return self
 
     def replay(self):
@@ -1668,7 +1700,7 @@ class ChunkGraph:
 # ======================================================================================================================
 # hipGraph replay of the DDIM sampler (BASELINE.json configs[5]: FiLM + diffusion head)
 # ======================================================================================================================
-class DiffusionGraph:
+class DiffusionGraph(_StaticInputs):
     """The diffusion head's sampling loop (modeling_prismatic.py:793-877) as TWO captures over static buffers, with no host work between the
     steps:
 
@@ -1685,24 +1717,17 @@ class DiffusionGraph:
 
     def __init__(self, engine: "VLAEngine", B: int, L: int, pixel_shape, *, head, noisy_action_projector, coef, temb_table,
                  use_proprio: bool = True, proprio_projector=None, invariant: bool = False, film: bool = False):
+        super().__init__(engine, B, L, pixel_shape, use_proprio, invariant, film)
         dev, cfg = engine.device, engine.cfg
-        if film and not engine.use_film:
-            raise ValueError("DiffusionGraph(film=True) needs an engine built with use_film=True")
         if head is None or noisy_action_projector is None:
             raise ValueError("DiffusionGraph needs the noise-predicting head and the noisy-action projector")
-        self.engine, self.head, self.noisy_action_projector, self.proprio_projector = engine, head, noisy_action_projector, proprio_projector
-        self.B, self.L, self.invariant, self.film = B, L, invariant, film
+        self.head, self.noisy_action_projector, self.proprio_projector = head, noisy_action_projector, proprio_projector
         self.n_steps = int(coef.shape[0])
         if tuple(coef.shape) != (self.n_steps, 4) or tuple(temb_table.shape) != (self.n_steps, cfg.llm_dim):
             raise ValueError(f"DiffusionGraph: coef {tuple(coef.shape)} / temb_table {tuple(temb_table.shape)} for {self.n_steps} steps, D = {cfg.llm_dim}")
         self.coef = coef.to(dev, F32).contiguous()
         self.temb_table = temb_table.to(dev, BF16).contiguous()
         n = B * cfg.chunk * cfg.action_dim
-        self.ids = torch.zeros((B, L), dtype=torch.int64, device=dev)
-        self.lab = torch.full((B, L), -100, dtype=torch.int64, device=dev)
-        self.lens = torch.full((B,), L, dtype=torch.int32, device=dev)
-        self.pixels = torch.zeros(tuple(pixel_shape), dtype=BF16, device=dev)
-        self.proprio = torch.zeros((B, cfg.proprio_dim), dtype=BF16, device=dev) if use_proprio else None
         self.sample = torch.zeros(n, dtype=F32, device=dev)           # the trajectory, bf16-rounded values held in fp32 (as the host loop holds them)
         self.step = torch.zeros(1, dtype=torch.int32, device=dev)     # index into the scheduler's timesteps; n_steps = sampling finished
         self.temb = torch.zeros((B, cfg.llm_dim), dtype=BF16, device=dev)
@@ -1714,12 +1739,8 @@ class DiffusionGraph:
     def _run_prefix(self):
         eng = self.engine
         with ops.batch_invariant(self.invariant):
-            film_avg = None
-            if self.film:
-                film_avg = torch.zeros(((self.B + 7) // 8 * 8, eng.cfg.llm_dim), dtype=BF16, device=eng.device)
-                ops.language_average_ragged(self.ids, self.lab, self.lens, eng.embed, film_avg)
             pp = self.proprio_projector if self.proprio_projector is not None else eng.proprio
-            base, n_vis, _, _ = eng.patches_dev(self.ids, self.lab, self.pixels, self.proprio, pp, film_avg, False)
+            base, n_vis, _, _ = eng.patches_dev(self.ids, self.lab, self.pixels, self.proprio, pp, self._film_average(), False)
         return base, n_vis
 
     def _run_step(self, patches):
@@ -1735,36 +1756,26 @@ class DiffusionGraph:
 
     def load(self, input_ids, attention_mask, pixel_values, labels, proprio, noise):
         """noise: the start of the trajectory, fp32 [B, chunk, action_dim] already rounded through bf16."""
-        lens = VLAEngine.check_right_padding(attention_mask)
-        assert tuple(input_ids.shape) == (self.B, self.L), f"DiffusionGraph captured for ids {(self.B, self.L)}, got {tuple(input_ids.shape)}"
-        self.ids.copy_(input_ids.to(torch.int64), non_blocking=True)
-        self.lab.copy_(labels.to(torch.int64), non_blocking=True)
-        self.lens.copy_(lens.to(torch.int32), non_blocking=True)
-        self.pixels.copy_(pixel_values.reshape(self.pixels.shape), non_blocking=True)
-        if self.proprio is not None:
-            self.proprio.copy_(proprio.reshape(self.proprio.shape), non_blocking=True)
+        super().load(input_ids, attention_mask, pixel_values, labels, proprio)
         self.sample.copy_(noise.reshape(-1).to(F32), non_blocking=True)
         self.step.zero_()
 
     def capture(self):
         """Call after load() of a representative input: one eager prefix + step as warm-up (lazy tables, kernel attributes), the loaded sample
         and step index put back, then the two captures."""
-        assert ops.PROFILE is None, "no per-launch event timing inside a graph capture"
-        start = self.sample.clone()
-        self._run_step(self._run_prefix())
-        self.sample.copy_(start)
-        self.step.zero_()
-        torch.cuda.synchronize(self.engine.device)
-        outer_ws, ops._ws_cache = ops._ws_cache, {}          # workspaces allocated while capturing belong to the graphs' pools
-        try:
+        def warm_up():
+            start = self.sample.clone()
+            self._run_step(self._run_prefix())
+            self.sample.copy_(start)
+            self.step.zero_()
+
+        with self._capturing(warm_up):
             self.prefix_graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.prefix_graph):
                 self.patches = self._run_prefix()
             self.step_graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.step_graph):
                 self.ah = self._run_step(self.patches)
-        finally:
-            self._ws, ops._ws_cache = ops._ws_cache, outer_ws
         return self
 
     def replay(self):

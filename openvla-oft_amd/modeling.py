@@ -10,6 +10,7 @@ glue (`loss = L1Loss(gt, head.predict_action(h)); loss.backward()`) works unchan
 """
 from __future__ import annotations
 
+import contextlib
 import math
 from typing import Any, Dict, Optional, Tuple
 
@@ -433,50 +434,6 @@ class OpenVLAForActionPrediction(_StoreModule):
         own = self._policies[name]["norm_stats"] if name is not None else None
         return own if own is not None else self.norm_stats
 
-    def _predict_batch_policies(self, policy, ids, mask, labels, pixel_values, prop, use_proprio, Lb):
-        """predict_action_batch's forward for a mixed-policy batch -> (normalised actions [B, chunk, action_dim], hidden [B, A, D])."""
-        cfg, eng = self.cfg, self.engine
-        B, A, D = ids.shape[0], cfg.num_action_tokens, cfg.llm_dim
-        names = list(self._policies)
-        slots = [names.index(p) for p in policy]
-        pols = [self._policies[n] for n in names]
-        heads = [p["head"].comp for p in pols] if pols[0]["head"] is not None else None
-        pps = [p["pp"].comp for p in pols] if use_proprio else None
-        discrete, bins = heads is None, None
-        with ops.batch_invariant(ops.BATCH_INVARIANT_DEFAULT):
-            if self.use_graph:   # the key holds the policy set's identity and n, never the assignment: one capture serves every assignment
-                key = ("batch", B, Lb, tuple(pixel_values.shape), use_proprio, ops.BATCH_INVARIANT_DEFAULT, "policies", self._policy_gen, len(names),
-                       "discrete" if discrete else "l1")
-                g = self._graphs.pop(key, None)
-                if g is None:
-                    self._evict_batch_graph()
-                    g = ChunkGraph(eng, B, Lb, pixel_values.shape, use_proprio=use_proprio, invariant=ops.BATCH_INVARIANT_DEFAULT, discrete=discrete,
-                                   n_tokens=self.vocab_size, n_bins=self.bin_centers.shape[0],
-                                   policies=[(None if heads is None else heads[s], None if pps is None else pps[s]) for s in range(len(names))])
-                    g._keep = (heads, pps)
-                self._graphs[key] = g
-                res = g(ids, mask, pixel_values, labels, prop, slots=slots)
-                pred, hidden = res[0], res[1].view(B, A, D).clone()
-                if discrete:
-                    bins = res[3].cpu().numpy().astype(np.int64)
-                pred = pred.clone() if pred is not None else None
-            else:
-                with eng.routing(torch.tensor(slots, dtype=torch.int32).to(self.device), host_slots=slots):
-                    out = eng.forward(ids, mask, pixel_values, labels, proprio=prop, train=False,
-                                      proprio_projector=SlotProjectors(pps, eng.route) if use_proprio else None, sel="actions")
-                    ah, _ = eng.action_hidden(out)
-                    hidden = ah.view(B, A, D).clone()
-                    pred = eng.policy_heads_fwd(ah, heads) if heads is not None else None
-            if pred is not None:
-                normalized = pred.reshape(B, cfg.chunk, cfg.action_dim).float().cpu().numpy()
-            elif bins is not None:
-                normalized = self.bin_centers[bins].reshape(B, cfg.chunk, cfg.action_dim)
-            else:
-                tok = self.logits_for(hidden.view(B * A, D)).argmax(dim=1).cpu().numpy()
-                d = np.clip(self.vocab_size - tok - 1, a_min=0, a_max=self.bin_centers.shape[0] - 1)
-                normalized = self.bin_centers[d].reshape(B, cfg.chunk, cfg.action_dim)
-        return normalized, hidden
-
     def merge_and_unload(self):
         """peft `merge_and_unload()` of merge_lora_weights_and_save.py:60-67 on device: W += (alpha/r) B A for every adapted
         Linear; the model becomes inference-only.  Returns self, like peft."""
@@ -532,13 +489,9 @@ class OpenVLAForActionPrediction(_StoreModule):
         """lm_head on selected hidden rows [n, D] -> fp32 logits [n, vocab] (discrete action-token path, :929-942)."""
         if self.engine.lm_head is None:
             raise RuntimeError("this checkpoint was loaded without language_model.lm_head.weight")
-        n = hidden_rows.shape[0]
-        pad = (n + 7) // 8 * 8
-        rows = torch.zeros((pad, self.cfg.llm_dim), dtype=BF16, device=self.device)
-        rows[:n] = hidden_rows
-        return ops.cvt_bf16_to_f32(ops.gemm(rows, self.engine.lm_head))[:n]
+        return ops.cvt_bf16_to_f32(self.engine.lm_head_rows(hidden_rows))[: hidden_rows.shape[0]]
 
-    # -- graph replay of the DDIM sampler ---------------------------------------------------------------------------------------------------
+    # -- the one inference path behind predict_action and predict_action_batch, with graph replay on or off -------------------------------
     @staticmethod
     def _ddim_tables(action_head):
         """(coef fp32 [n_steps, 4], timestep embeddings bf16 [n_steps, D]) of the head's scheduler after set_timesteps: what the host loop
@@ -547,16 +500,26 @@ class OpenVLAForActionPrediction(_StoreModule):
         temb = torch.cat([action_head.time_encoder(torch.tensor([float(t)])).to(BF16).reshape(1, -1) for t in sched.timesteps])
         return sched.step_coefficients(), temb
 
-    def _diffusion_graph(self, key, B, L, pixel_shape, action_head, noisy_action_projector, pp_comp, use_proprio, *, invariant=False, film=False):
-        """The DiffusionGraph under `key` in self._graphs (captured on first use).  Batch keys follow predict_action_batch's LRU rule."""
+    def _graph_key(self, batch, B, L, pixel_shape, *, use_proprio, head_comp, pp_comp, film, discrete, ddim, n_policies):
+        """The key of a captured graph in self._graphs.  predict_action: one graph per (text length, head, projector), led by "ddim" for the
+        sampler.  The batch API: ("batch", B, text bucket, ...), what _evict_batch_graph counts.  `ddim`: (id of the noisy-action projector,
+        sampling steps, training steps)."""
+        shape = tuple(pixel_shape)
+        if n_policies:   # the key holds the policy set's identity and n, never the assignment: one capture serves every assignment
+            return ("batch", B, L, shape, use_proprio, ops.BATCH_INVARIANT_DEFAULT, "policies", self._policy_gen, n_policies, "discrete" if discrete else "l1")
+        if not batch:
+            return ("ddim", L, shape, id(head_comp), id(pp_comp)) + ddim if ddim else (L, shape, id(head_comp), id(pp_comp))
+        key = ("batch", B, L, shape, id(head_comp), id(pp_comp), ops.BATCH_INVARIANT_DEFAULT, film)
+        return key + ("ddim",) + ddim if ddim else key + (discrete,)
+
+    def _graph_for(self, key, build):
+        """The graph under `key` in self._graphs; on first use `build()` -> (the graph, the components whose parameters its kernels read)."""
         g = self._graphs.pop(key, None)
         if g is None:
             if key[0] == "batch":
                 self._evict_batch_graph()
-            coef, temb = self._ddim_tables(action_head)
-            g = DiffusionGraph(self.engine, B, L, pixel_shape, head=action_head.comp, noisy_action_projector=noisy_action_projector.comp, coef=coef,
-                               temb_table=temb, use_proprio=use_proprio, proprio_projector=pp_comp, invariant=invariant, film=film)
-            g._keep = (action_head.comp, pp_comp, noisy_action_projector.comp)   # the captured kernels read these parameter buffers: keep them alive
+            g, keep = build()
+            g._keep = keep   # the captured kernels read these parameter buffers: keep them alive
         self._graphs[key] = g   # (re)inserted last: dict order is least recently used first
         return g
 
@@ -564,6 +527,109 @@ class OpenVLAForActionPrediction(_StoreModule):
         batched = [k for k in self._graphs if k[0] == "batch"]
         if len(batched) >= self.max_batch_graphs:   # B and the bucket come from callers (/act_batch): keep the most recent few
             del self._graphs[batched[0]]
+
+    def _decode(self, pred, bins, hidden):
+        """Normalised actions [B, chunk, action_dim] from whichever the forward produced: the head's prediction (:923-927); the bin indices, when
+        the lm_head GEMM + ovla_argmax_bins ran inside a graph; otherwise the greedy token decode of the action hidden states (:929-942)."""
+        cfg = self.cfg
+        if pred is not None:
+            normalized = pred.float().cpu().numpy()
+        else:
+            if bins is None:
+                tok = self.logits_for(hidden.view(-1, cfg.llm_dim)).argmax(dim=1).cpu().numpy()
+                bins = np.clip(self.vocab_size - tok - 1, a_min=0, a_max=self.bin_centers.shape[0] - 1)
+            normalized = self.bin_centers[bins]
+        return normalized.reshape(hidden.shape[0], cfg.chunk, cfg.action_dim)
+
+    def _infer(self, ids, mask, labels, pixel_values, prop, *, batch: bool, action_head=None, proprio_projector=None, noisy_action_projector=None,
+               noise=None, policy=None):
+        """The forward on prepared ids / mask / labels [B, L], the action rows, the head (L1, or the DDIM sampler from `noise`) or the token
+        decode -> (normalised actions ndarray [B, chunk, action_dim], action hidden states [B, A, D] in a tensor of their own).
+        `batch` is the mode.  False (predict_action): the planner's GEMM schedules, FiLM's average over all L positions, a graph per key.
+        True (predict_action_batch): every GEMM under ops.batch_invariant(ops.BATCH_INVARIANT_DEFAULT), FiLM's average over each row's own
+        tokens, "batch" graph keys under the LRU rule, and the token decode inside the graph.
+        `policy`: (adapter slot per observation, the policies' head components or None, their proprio projector components or None)."""
+        cfg, eng = self.cfg, self.engine
+        (B, L), A, D = ids.shape, cfg.num_action_tokens, cfg.llm_dim
+        slots, heads, pps = policy if policy is not None else (None, None, None)
+        use_proprio = prop is not None
+        head_comp, nap_comp = getattr(action_head, "comp", None), getattr(noisy_action_projector, "comp", None)
+        pp_comp = proprio_projector.comp if use_proprio and proprio_projector is not None else None
+        use_diffusion = noisy_action_projector is not None and hasattr(action_head, "noise_scheduler")
+        discrete = action_head is None and heads is None
+        film, film_avg = batch and eng.use_film, None
+        if film and not self.use_graph:
+            # FiLM's language average over each prompt's OWN tokens (padding would enter the mean: film_vit_wrapper.py:243): one ragged launch
+            # for the batch, bit for bit ovla_language_average on each unpadded row.  (Under graph replay the launch is part of the graph.)
+            film_avg = torch.zeros(((B + 7) // 8 * 8, D), dtype=BF16, device=self.device)
+            ops.language_average_ragged(ids.to(self.device), labels.to(self.device), mask.sum(1).to(torch.int32).to(self.device), eng.embed, film_avg)
+        pred = bins = ddim = None
+        with ops.batch_invariant(ops.BATCH_INVARIANT_DEFAULT) if batch else contextlib.nullcontext():
+            if use_diffusion:                                                                 # :793-877, per sample
+                sched = action_head.noise_scheduler
+                sched.set_timesteps(action_head.num_diffusion_steps)
+                if noise is None:
+                    noise = torch.randn((B, cfg.chunk, cfg.action_dim))
+                cur = torch.as_tensor(noise).to("cpu", torch.float32).reshape(B, cfg.chunk, cfg.action_dim).to(BF16).float()
+                ddim = (id(nap_comp), len(sched.timesteps), sched.config.num_train_timesteps)
+            if self.use_graph:
+                def build():
+                    invariant = ops.BATCH_INVARIANT_DEFAULT if batch else False
+                    if use_diffusion:
+                        coef, temb = self._ddim_tables(action_head)
+                        g = DiffusionGraph(eng, B, L, pixel_values.shape, head=head_comp, noisy_action_projector=nap_comp, coef=coef, temb_table=temb,
+                                           use_proprio=use_proprio, proprio_projector=pp_comp, invariant=invariant, film=film)
+                        return g, (head_comp, pp_comp, nap_comp)
+                    per_slot, keep = None, (head_comp, pp_comp)
+                    if policy is not None:
+                        per_slot = [(None if heads is None else heads[s], None if pps is None else pps[s]) for s in range(len(self._policies))]
+                        keep = (heads, pps)
+                    g = ChunkGraph(eng, B, L, pixel_values.shape, head=head_comp, use_proprio=use_proprio, proprio_projector=pp_comp, invariant=invariant,
+                                   film=film, discrete=batch and discrete, n_tokens=self.vocab_size, n_bins=self.bin_centers.shape[0], policies=per_slot)
+                    return g, keep
+
+                key = self._graph_key(batch, B, L, pixel_values.shape, use_proprio=use_proprio, head_comp=head_comp, pp_comp=pp_comp, film=film,
+                                      discrete=discrete, ddim=ddim, n_policies=len(self._policies) if policy is not None else 0)
+                g = self._graph_for(key, build)
+                if use_diffusion:
+                    # the whole loop from two captured graphs, no host work between the steps (engine.DiffusionGraph): same bits as the loop below
+                    sample, ah = g(ids, mask, pixel_values, labels, prop, cur)
+                    cur = sample.reshape(B, cfg.chunk, cfg.action_dim)
+                else:
+                    # one hipGraph per key: ~1.3 k launches -> one graph launch (engine.ChunkGraph)
+                    res = g(ids, mask, pixel_values, labels, prop, slots=slots)
+                    pred, ah = res[0], res[1]
+                    if len(res) > 2:        # lm_head GEMM + ovla_argmax_bins ran inside the graph: only the bin indices come back
+                        bins = res[3].cpu().numpy().astype(np.int64)
+                hidden = ah.view(B, A, D).clone()   # out of the graph's static buffer
+            elif use_diffusion:
+                cached = None
+                for t in sched.timesteps:
+                    temb = action_head.time_encoder(torch.tensor([float(t)])).to(BF16).reshape(1, D).expand(B, D)
+                    out = self.engine.forward(ids, mask, pixel_values, labels, proprio=prop, train=False, noisy_actions=cur.to(BF16), timestep_emb=temb,
+                                              proprio_projector=pp_comp, noisy_action_projector=nap_comp, cached_patches=cached, sel="actions",
+                                              film_avg=film_avg)
+                    cached = out["patches"]                                                   # vision features reused across steps (:810)
+                    ah, _ = eng.action_hidden(out)
+                    eps = action_head.predict_noise(ah.view(B, A, D)).reshape(cur.shape).float().cpu()
+                    cur = sched.step(eps, int(t), cur).prev_sample.to(BF16).float()
+                hidden = ah.view(B, A, D).clone()
+            else:
+                route = contextlib.nullcontext()
+                if slots is not None:
+                    route = eng.routing(torch.tensor(slots, dtype=torch.int32).to(self.device), host_slots=slots)
+                with route:
+                    out = self.engine.forward(ids, mask, pixel_values, labels, proprio=prop, train=False,
+                                              proprio_projector=SlotProjectors(pps, eng.route) if pps is not None else pp_comp, sel="actions",
+                                              film_avg=film_avg)
+                    ah, _ = eng.action_hidden(out)                                            # rows P+NPT .. P+NPT+A-1 (:915-920)
+                    hidden = ah.view(B, A, D).clone()
+                    if heads is not None:
+                        pred = eng.policy_heads_fwd(ah, heads)
+                    elif action_head is not None:
+                        pred = action_head.predict_action(hidden)
+            normalized = cur.numpy() if use_diffusion else self._decode(pred, bins, hidden)
+        return normalized, hidden
 
     # -- predict_action (:946-1060) -------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -587,63 +653,9 @@ class OpenVLAForActionPrediction(_StoreModule):
         labels[:, -1] = STOP_INDEX
         use_proprio = proprio_projector is not None and proprio is not None
         prop = torch.as_tensor(np.asarray(proprio), dtype=torch.float32) if use_proprio else None
-        use_diffusion = noisy_action_projector is not None and hasattr(action_head, "noise_scheduler")
-        if use_diffusion:                                                                 # :793-877
-            sched = action_head.noise_scheduler
-            sched.set_timesteps(action_head.num_diffusion_steps)
-            cur = kwargs.get("noise")
-            if cur is None:
-                cur = torch.randn((1, cfg.chunk, cfg.action_dim))
-            cur = cur.to("cpu", torch.float32).to(BF16).float()
-            if self.use_graph:
-                # the whole loop from two captured graphs, no host work between the steps (engine.DiffusionGraph): same bits as the loop below
-                pp_comp = proprio_projector.comp if use_proprio else None
-                key = ("ddim", ids.shape[1], tuple(pixel_values.shape), id(action_head.comp), id(pp_comp), id(noisy_action_projector.comp),
-                       len(sched.timesteps), sched.config.num_train_timesteps)
-                g = self._diffusion_graph(key, 1, ids.shape[1], pixel_values.shape, action_head, noisy_action_projector, pp_comp, use_proprio)
-                sample, ah = g(ids, mask, pixel_values, labels, prop, cur)
-                normalized = sample.reshape(cfg.chunk, cfg.action_dim).numpy()
-                return self._unnormalize_actions(normalized, unnorm_key), ah.view(1, A, cfg.llm_dim).clone()
-            cached, ah = None, None
-            for t in sched.timesteps:
-                temb = action_head.time_encoder(torch.tensor([float(t)])).to(BF16)
-                out = self.engine.forward(ids, mask, pixel_values, labels, proprio=prop, train=False, noisy_actions=cur.to(BF16),
-                                          timestep_emb=temb, proprio_projector=proprio_projector.comp if use_proprio else None,
-                                          noisy_action_projector=noisy_action_projector.comp, cached_patches=cached, sel="actions")
-                cached = out["patches"]                                                   # vision features reused across steps (:810)
-                ah, _ = self.engine.action_hidden(out)
-                eps = action_head.predict_noise(ah.view(1, A, cfg.llm_dim)).reshape(cur.shape).float().cpu()
-                cur = sched.step(eps, int(t), cur).prev_sample.to(BF16).float()
-            normalized = cur.reshape(cfg.chunk, cfg.action_dim).numpy()
-            return self._unnormalize_actions(normalized, unnorm_key), ah.view(1, A, cfg.llm_dim)
-        if self.use_graph:
-            # one hipGraph per (text length, head, projector): ~1.3 k launches -> one graph launch (engine.ChunkGraph)
-            head_comp = getattr(action_head, "comp", None) if action_head is not None else None
-            pp_comp = proprio_projector.comp if use_proprio else None
-            key = (ids.shape[1], tuple(pixel_values.shape), id(head_comp), id(pp_comp))
-            g = self._graphs.get(key)
-            if g is None:
-                g = self._graphs[key] = ChunkGraph(self.engine, 1, ids.shape[1], pixel_values.shape, head=head_comp, use_proprio=use_proprio,
-                                                   proprio_projector=pp_comp)
-                g._keep = (head_comp, pp_comp)   # the captured kernels read these parameter buffers: keep them alive
-            pred, ah = g(ids, mask, pixel_values, labels, prop)
-            actions_hidden_states = ah.view(1, A, cfg.llm_dim).clone()
-            if action_head is not None:
-                normalized = pred.reshape(cfg.chunk, cfg.action_dim).float().cpu().numpy()
-                return self._unnormalize_actions(normalized, unnorm_key), actions_hidden_states
-            ah = actions_hidden_states.view(A, cfg.llm_dim)
-        else:
-            out = self.engine.forward(ids, mask, pixel_values, labels, proprio=prop, train=False,
-                                      proprio_projector=proprio_projector.comp if use_proprio else None, sel="actions")
-            ah, _ = self.engine.action_hidden(out)                                        # rows P+NPT .. P+NPT+A-1 (:915-920)
-            actions_hidden_states = ah.view(1, A, cfg.llm_dim)
-        if action_head is not None:                                                       # :923-927
-            normalized = action_head.predict_action(actions_hidden_states).reshape(cfg.chunk, cfg.action_dim).float().cpu().numpy()
-        else:                                                                             # :929-942
-            tok = self.logits_for(ah).argmax(dim=1).cpu().numpy()
-            d = np.clip(self.vocab_size - tok - 1, a_min=0, a_max=self.bin_centers.shape[0] - 1)
-            normalized = self.bin_centers[d].reshape(cfg.chunk, cfg.action_dim)
-        return self._unnormalize_actions(normalized, unnorm_key), actions_hidden_states
+        normalized, hidden = self._infer(ids, mask, labels, pixel_values, prop, batch=False, action_head=action_head, proprio_projector=proprio_projector,
+                                         noisy_action_projector=noisy_action_projector, noise=kwargs.get("noise"))
+        return self._unnormalize_actions(normalized[0], unnorm_key), hidden
 
     # -- batched inference (not in the reference: its predict_action asserts batch size 1) -----------------------------------------------
     @torch.no_grad()
@@ -664,7 +676,7 @@ class OpenVLAForActionPrediction(_StoreModule):
         cfg = self.cfg
         if use_film != self.engine.use_film:
             raise ValueError(f"use_film={use_film} but the model was built with use_film={self.engine.use_film}")
-        B, A, D = len(prompts), cfg.num_action_tokens, cfg.llm_dim
+        B, A = len(prompts), cfg.num_action_tokens
         if B == 0:
             raise ValueError("predict_action_batch: no observations")
         if pixel_values.shape[0] != B:
@@ -728,82 +740,17 @@ class OpenVLAForActionPrediction(_StoreModule):
             ids[b, : len(r)], mask[b, : len(r)] = r, True
             labels[b, len(r) - A - 1: len(r)] = ACTION_TOKEN_BEGIN_IDX + 1
             labels[b, len(r) - 1] = STOP_INDEX
-        if policy is not None:
-            normalized, hidden = self._predict_batch_policies(policy, ids, mask, labels, pixel_values, prop, use_proprio, Lb)
+        if policy is not None:   # each observation under its own policy's adapter slot, head, proprio projector and statistics
+            names = list(self._policies)
+            pols = list(self._policies.values())
+            heads = [p["head"].comp for p in pols] if pols[0]["head"] is not None else None
+            pps = [p["pp"].comp for p in pols] if use_proprio else None
+            normalized, hidden = self._infer(ids, mask, labels, pixel_values, prop, batch=True, policy=([names.index(p) for p in policy], heads, pps))
             stats = [self.policy_norm_stats(p) for p in policy]
             return np.stack([self._unnormalize_actions(normalized[b], unnorm_key, stats[b]) for b in range(B)]), hidden
-        film, film_avg = self.engine.use_film, None
-        graphed = self.use_graph
-        if film and not graphed:
-            # FiLM's language average over each prompt's OWN tokens (padding would enter the mean: film_vit_wrapper.py:243): one ragged launch
-            # for the batch, bit for bit ovla_language_average on each unpadded row.  (Under graph replay the launch is part of the graph.)
-            film_avg = torch.zeros(((B + 7) // 8 * 8, D), dtype=BF16, device=self.device)
-            ops.language_average_ragged(ids.to(self.device), labels.to(self.device), torch.tensor([len(r) for r in rows], dtype=torch.int32).to(self.device),
-                                        self.engine.embed, film_avg)
-        pp_comp = proprio_projector.comp if use_proprio else None
-        with ops.batch_invariant(ops.BATCH_INVARIANT_DEFAULT):
-            if use_diffusion:                                                                 # :793-877, per sample
-                sched = action_head.noise_scheduler
-                sched.set_timesteps(action_head.num_diffusion_steps)
-                if noise is None:
-                    noise = torch.randn((B, cfg.chunk, cfg.action_dim))
-                cur = torch.as_tensor(noise).to("cpu", torch.float32).reshape(B, cfg.chunk, cfg.action_dim).to(BF16).float()
-                if graphed:   # engine.DiffusionGraph: the ragged FiLM average, the towers and every sampling step replayed from captured graphs
-                    key = ("batch", B, Lb, tuple(pixel_values.shape), id(action_head.comp), id(pp_comp), ops.BATCH_INVARIANT_DEFAULT, film, "ddim",
-                           id(noisy_action_projector.comp), len(sched.timesteps), sched.config.num_train_timesteps)
-                    g = self._diffusion_graph(key, B, Lb, pixel_values.shape, action_head, noisy_action_projector, pp_comp, use_proprio,
-                                              invariant=ops.BATCH_INVARIANT_DEFAULT, film=film)
-                    sample, ah = g(ids, mask, pixel_values, labels, prop, cur)
-                    cur = sample.reshape(B, cfg.chunk, cfg.action_dim)
-                else:
-                    cached, ah = None, None
-                    for t in sched.timesteps:
-                        temb = action_head.time_encoder(torch.tensor([float(t)])).to(BF16).reshape(1, D).expand(B, D)
-                        out = self.engine.forward(ids, mask, pixel_values, labels, proprio=prop, train=False, noisy_actions=cur.to(BF16),
-                                                  timestep_emb=temb, proprio_projector=pp_comp, noisy_action_projector=noisy_action_projector.comp,
-                                                  cached_patches=cached, sel="actions", film_avg=film_avg)
-                        cached = out["patches"]
-                        ah, _ = self.engine.action_hidden(out)
-                        eps = action_head.predict_noise(ah.view(B, A, D)).reshape(cur.shape).float().cpu()
-                        cur = sched.step(eps, int(t), cur).prev_sample.to(BF16).float()
-                normalized = cur.numpy()
-                hidden = ah.view(B, A, D).clone()
-            else:
-                head_comp = getattr(action_head, "comp", None) if action_head is not None else None
-                discrete = action_head is None
-                bins = None
-                if graphed:
-                    key = ("batch", B, Lb, tuple(pixel_values.shape), id(head_comp), id(pp_comp), ops.BATCH_INVARIANT_DEFAULT, film, discrete)
-                    g = self._graphs.pop(key, None)
-                    if g is None:
-                        self._evict_batch_graph()
-                        g = ChunkGraph(self.engine, B, Lb, pixel_values.shape, head=head_comp, use_proprio=use_proprio, proprio_projector=pp_comp,
-                                       invariant=ops.BATCH_INVARIANT_DEFAULT, film=film, discrete=discrete, n_tokens=self.vocab_size,
-                                       n_bins=self.bin_centers.shape[0])
-                        g._keep = (head_comp, pp_comp)
-                    self._graphs[key] = g   # (re)inserted last: dict order is least recently used first
-                    res = g(ids, mask, pixel_values, labels, prop)
-                    pred, ah = res[0], res[1]
-                    if discrete:            # lm_head GEMM + ovla_argmax_bins ran inside the graph: only the bin indices come back
-                        bins = res[3].cpu().numpy().astype(np.int64)
-                    hidden = ah.view(B, A, D).clone()
-                    pred = pred.clone() if pred is not None else None
-                else:
-                    out = self.engine.forward(ids, mask, pixel_values, labels, proprio=prop, train=False, proprio_projector=pp_comp,
-                                              sel="actions", film_avg=film_avg)
-                    ah, _ = self.engine.action_hidden(out)
-                    hidden = ah.view(B, A, D).clone()
-                    pred = action_head.predict_action(hidden) if action_head is not None else None
-                if action_head is not None:
-                    normalized = pred.reshape(B, cfg.chunk, cfg.action_dim).float().cpu().numpy()
-                elif bins is not None:
-                    normalized = self.bin_centers[bins].reshape(B, cfg.chunk, cfg.action_dim)
-                else:
-                    tok = self.logits_for(hidden.view(B * A, D)).argmax(dim=1).cpu().numpy()
-                    d = np.clip(self.vocab_size - tok - 1, a_min=0, a_max=self.bin_centers.shape[0] - 1)
-                    normalized = self.bin_centers[d].reshape(B, cfg.chunk, cfg.action_dim)
-        actions = np.stack([self._unnormalize_actions(normalized[b], unnorm_key) for b in range(B)])
-        return actions, hidden
+        normalized, hidden = self._infer(ids, mask, labels, pixel_values, prop, batch=True, action_head=action_head, proprio_projector=proprio_projector,
+                                         noisy_action_projector=noisy_action_projector, noise=noise)
+        return np.stack([self._unnormalize_actions(normalized[b], unnorm_key) for b in range(B)]), hidden
 
     # -- statistics (:772-791, :1062-1087) -------------------------------------------------------------------------------
     @staticmethod
