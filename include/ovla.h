@@ -65,9 +65,9 @@ int ovla_check_device(int device);
  * split_k > 1 needs `workspace` of ovla_gemm_workspace_bytes() bytes.
  */
 enum { OVLA_ACT_NONE = 0, OVLA_ACT_GELU = 1, OVLA_ACT_RELU = 2, OVLA_ACT_SILU = 3, OVLA_ACT_GELU_TANH = 4,
-       /* ovla_gemm_bf16 only, on the 4-wave configurations only (tile 0, which takes 18; 18 / 118; 22 / 122; K % 64 == 0): B = [gate; up] stacked ([N = 2 F, K], F % 128 == 0), C is [M, F] = bf16(bf16(silu(g)) * u) with g | u the
+       /* ovla_gemm_bf16 only, on tiles 0 / 18 / 118 / 22 / 122 (the 4-wave configurations; tile 0 takes 18; K % 64 == 0): B = [gate; up] stacked ([N = 2 F, K], F % 128 == 0), C is [M, F] = bf16(bf16(silu(g)) * u) with g | u the
         * bf16-rounded projection outputs -- HF LlamaMLP's act_fn(gate_proj(x)) * up_proj(x) (modeling_llama.py) without the [M, 2 F] intermediate; nothing else
-        * in the epilogue but alpha, the RMSNorm-fold row scale (rowscale_part; 22 / 122) and C_pre (the [M, 2 F] projection output, kept by training).
+        * in the epilogue but alpha, the RMSNorm-fold row scale (rowscale_part; 22 / 122) and C_pre (the [M, 2 F] projection output, contiguous: row stride N; kept by training).
         * K-extension: 0 or 32 columns on 18 / 118, none on 22 / 122.  Same bits as ovla_gemm_bf16 + ovla_swiglu_fwd. */
        OVLA_ACT_SWIGLU = 5 };
 
@@ -77,7 +77,8 @@ typedef struct {
   const void* A2; int64_t lda2;  /* optional K-extension (LoRA) */
   const void* B2; int64_t ldb2;
   void* C; int64_t ldc;          /* bf16 [M,N] */
-  void* C_pre;                   /* optional bf16 [M,N] (ldc): value before the activation; with FiLM: before the modulation */
+  void* C_pre;                   /* optional bf16 [M,N] (ldc): value before the activation; with FiLM: before the modulation;
+                                    with OVLA_ACT_SWIGLU: the [M, N = 2 F] projection output, CONTIGUOUS (row stride N, not ldc) */
   const void* bias;              /* optional bf16 [N] */
   const void* colscale;          /* optional bf16 [N]  (timm LayerScale) */
   const void* residual; int64_t ldr; /* optional bf16 [M,N] */
@@ -103,9 +104,10 @@ typedef struct {
    *   producer side  rowsq_out [M, N/64] fp32: sum of squares of every 64-column group of the bf16 OUTPUT row (plain stores, one writer per
    *                  slot: summed later in slot order -- deterministic);
    *   consumer side  rowscale_part [M, rowscale_slots] fp32 = the producer's rowsq_out for this GEMM's A operand (rowscale_slots * 64 = K):
-   *                  C = epilogue(rstd[m] * alpha * acc), rstd[m] = rsqrt(sum(slots) / K + rowscale_eps); rowscale_r [M] fp32 scratch
-   *                  receives rstd (the hybrid-remainder reduce reads it).
-   * Supported on the 128x128 tile (tile 1 / 101, what the batch-1 shapes M <= ~1k resolve to) and on the 4-wave 128x256 configuration (tile 22 / 122,
+   *                  C = epilogue(acc * (alpha * rstd[m])), rstd[m] = rsqrt(sum(slots) / K + rowscale_eps): ONE fp32 factor alpha * rstd[m],
+   *                  multiplied into the accumulator once -- the same bits whichever path a tile takes (interior, edge, K-split remainder);
+   *                  rowscale_r [M] fp32 scratch receives rstd (the hybrid-remainder reduce reads it).
+   * Both sides run on tiles 1 / 101 (128x128, what the batch-1 shapes M <= ~1k resolve to) and 22 / 122 (the 4-wave 128x256 configuration,
    * what the engine's batch-1 path forces; consumer side for K <= 4096, no producer side in a launch that fuses RoPE); any other schedule is an error. */
   float* rowsq_out;
   const float* rowscale_part; int32_t rowscale_slots; float rowscale_eps; float* rowscale_r;

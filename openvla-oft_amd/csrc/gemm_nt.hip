@@ -54,20 +54,12 @@ struct GemmParams {
   int fast_swiglu_bwd;  // host: dact_mode 2 with 16-byte aligned [M, 2N] operands and nothing else in the epilogue -> SwiGLU' in the unrolled read-back
   int dbg;  // timing ablations, compiled in ONLY with -DOVLA_GEMM_ABLATE (build.sh ablate -> libovla_hip_ablate.so, tools/gemm_ablate.py): bit0 = stage only the first two K tiles, bit1 = read fragments once, bit2 = every workgroup stages tile (0,0): all L2 hits, bit3 = no epilogue, bit4 = epilogue without its stores, bit5 = nontemporal stores, bit6 = force the LDS-staged epilogue, bit7 / bit8 / bit9 = no (A and B) / B / A fragment reads after the first K tile
   int full_tiles, rem_tiles, rem_splits;  // hybrid schedule: tiles >= full_tiles are split rem_splits ways along K
-  // RMSNorm fold (ovla.h): producer writes per-row sums of squares of its output's 64-column groups; consumer scales the accumulator by rstd[m]
+  // RMSNorm fold (ovla.h): producer writes per-row sums of squares of its output's 64-column groups; consumer multiplies the accumulator by alpha * rstd[m]
   float* rowsq_out;
   const float* rowscale_part; int rowscale_slots; float rowscale_eps; float* rowscale_r;
   int hyb_cnt_n;
   unsigned* hyb_cnt;   // per-remainder-tile arrival counters (all zero between launches) for the in-launch reduce; nullptr: separate reduce kernel
 };
-
-// sum of squares of 4 bf16-rounded outputs, reduced over the 16 lanes that hold one row's 64-column group (lanes aligned to 16)
-OVLA_DEV float rowsq16(f32x4 v) {
-  float s = v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
-#pragma unroll
-  for (int o = 1; o < 16; o <<= 1) s += __shfl_xor(s, o, 64);
-  return s;
-}
 
 // Stage ROWS x 64 bf16 of a row-major [rows, ld] matrix into an LDS tile (swizzled 128-byte rows) with LDS-DMA.
 template <int ROWS, int NW>
@@ -136,99 +128,227 @@ OVLA_DEV bf16x8_bits lds_frag(const bf16_bits* tile, int row, int chunk) {
 #define OVLA_FRAG(var, expr, bits) var = (expr)
 #endif
 
-// Epilogue on 4 consecutive columns n..n+3 of row m.  Every step rounds to bf16, as the reference's separate ops do.
-OVLA_DEV f32x4 epilogue_store(const GemmParams& p, int m, int n, f32x4 v) {   // returns the stored (bf16-rounded) values
-  v *= p.alpha;
-  if (p.bias) {
-    const bf16x4_bits b = *reinterpret_cast<const bf16x4_bits*>(p.bias + n);
+// ---- epilogue arithmetic: every body ONCE, on W consecutive columns n .. n + W - 1 of row m ---------------------------------------------------
+// W = 4: the rolled general read-backs and the reduce kernels (8-byte accesses); W = 8: the unrolled read-backs of interior tiles (16-byte
+// accesses).  The row factor ra = alpha (* rstd[m] with the RMSNorm fold) is formed once by the caller and multiplied into the accumulator
+// once: C = epilogue(acc * (alpha * rstd[m])), the same bits whichever path a tile takes.  Every step rounds to bf16, as the reference's separate ops do.
+template <int W> using bfvec = std::conditional_t<W == 8, bf16x8_bits, bf16x4_bits>;
+template <int W> OVLA_DEV bfvec<W> ld_bf(const bf16_bits* s) { return *reinterpret_cast<const bfvec<W>*>(s); }
+template <int W> OVLA_DEV void st_bf(bf16_bits* d, bfvec<W> o) { *reinterpret_cast<bfvec<W>*>(d) = o; }
+template <int W> OVLA_DEV bfvec<W> to_bf(const float (&v)[W]) {
+  bfvec<W> o;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = bfround(v[j] + bf2f((bf16_bits)b[j]));
-  } else {
+  for (int e = 0; e < W; ++e) o[e] = (short)f2bf(v[e]);
+  return o;
+}
+template <int W> OVLA_DEV void ld_slab(const float* s, float (&v)[W]) {   // W fp32 sums of one slab row (16-byte reads)
 #pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = bfround(v[j]);
+  for (int q = 0; q < W / 4; ++q) {
+    const f32x4 t = *reinterpret_cast<const f32x4*>(s + 4 * q);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[4 * q + e] = t[e];
   }
-  if (p.Cpre && !p.film_gamma) {   // value before the activation (saved for the backward)
-    bf16x4_bits o;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = (short)f2bf(v[j]);
-    *reinterpret_cast<bf16x4_bits*>(p.Cpre + (int64_t)m * p.ldc + n) = o;
-  }
-  if (p.act != OVLA_ACT_NONE) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = bfround(apply_act(v[j], p.act));
-  }
-  if (p.colscale) {
-    const bf16x4_bits s = *reinterpret_cast<const bf16x4_bits*>(p.colscale + n);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = bfround(v[j] * bf2f((bf16_bits)s[j]));
-  }
-  if (p.residual) {
-    const bf16x4_bits r = *reinterpret_cast<const bf16x4_bits*>(p.residual + (int64_t)m * p.ldr + n);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = bfround(v[j] + bf2f((bf16_bits)r[j]));
-  }
-  if (p.film_gamma) {
-    if (p.Cpre) {   // with FiLM, C_pre receives the value BEFORE the modulation (needed for d gamma)
-      bf16x4_bits o;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) o[j] = (short)f2bf(v[j]);
-      *reinterpret_cast<bf16x4_bits*>(p.Cpre + (int64_t)m * p.ldc + n) = o;
-    }
-    const int64_t off = (int64_t)(m / p.film_rows) * p.N + n;
-    const bf16x4_bits g = *reinterpret_cast<const bf16x4_bits*>(p.film_gamma + off);
-    const bf16x4_bits b = *reinterpret_cast<const bf16x4_bits*>(p.film_beta + off);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float one_plus = bfround(1.0f + bf2f((bf16_bits)g[j]));
-      v[j] = bfround(bfround(v[j] * one_plus) + bf2f((bf16_bits)b[j]));
-    }
-  }
-  if (p.dact_mode == 1) {          // dz = dh * act'(z): same arithmetic as act_bwd_kernel on the bf16-rounded dh
-    const bf16x4_bits z = *reinterpret_cast<const bf16x4_bits*>(p.dact_src + (int64_t)m * p.ld_dact + n);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = bfround(v[j]) * act_grad(bf2f((bf16_bits)z[j]), p.dact_act);
-  } else if (p.dact_mode == 2) {   // SwiGLU backward (swiglu_bwd_kernel's arithmetic): two outputs per element
-    const bf16x4_bits g4 = *reinterpret_cast<const bf16x4_bits*>(p.dact_src + (int64_t)m * p.ld_dact + n);
-    const bf16x4_bits u4 = *reinterpret_cast<const bf16x4_bits*>(p.dact_src + (int64_t)m * p.ld_dact + p.N + n);
-    bf16x4_bits du;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float d = bfround(v[j]), g = bf2f((bf16_bits)g4[j]), u = bf2f((bf16_bits)u4[j]);
-      const float s = sigmoidf_(g);
-      du[j] = (short)f2bf(d * bfround(g * s));
-      v[j] = d * u * (s * (1.f + g * (1.f - s)));
-    }
-    *reinterpret_cast<bf16x4_bits*>(p.C + (int64_t)m * p.ldc + p.N + n) = du;
-  }
-  bf16x4_bits o;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { o[j] = (short)f2bf(v[j]); v[j] = bf2f((bf16_bits)o[j]); }
-  if (OVLA_DBG(16) && v[0] != 123.456f) return v;          // timing ablation: the whole epilogue except the store
-  if (OVLA_DBG(32)) {                                          // timing ablation: write-through store that does not stay in this XCD's L2
-    __builtin_nontemporal_store(o, reinterpret_cast<bf16x4_bits*>(p.C + (int64_t)m * p.ldc + n));
-    return v;
-  }
-  *reinterpret_cast<bf16x4_bits*>(p.C + (int64_t)m * p.ldc + n) = o;
-  return v;
 }
 
-// RoPE epilogue (head_dim 128): v = this lane's 4 accumulator sums at columns n..n+3 of row m, vp = the sums at the rotation
-// partner columns n +- 64 (same head).  y = bf16(acc) is the q|k projection output the reference rotates; arithmetic and rounding
-// points are rope_kernel's (elementwise.hip): lo' = bf16(a c) + bf16(-b s), hi' = bf16(b c) + bf16(a s).
-OVLA_DEV void rope_store(const GemmParams& p, int m, int n, f32x4 v, f32x4 vp) {
-  const int c = n & 127;                  // column within the head
-  const bool lo = c < 64;
-  const int pos = m % p.rope_S;
-  const bf16x4_bits cs = *reinterpret_cast<const bf16x4_bits*>(p.rope_cos + (int64_t)pos * 64 + (c & 63));
-  const bf16x4_bits sn = *reinterpret_cast<const bf16x4_bits*>(p.rope_sin + (int64_t)pos * 64 + (c & 63));
-  bf16x4_bits o;
+// SwiGLU backward (swiglu_bwd_kernel's arithmetic): v = the bf16-rounded d h on entry, d gate (not yet rounded) on return; d up goes to columns N + n.
+template <int W>
+OVLA_DEV void epi_swiglu_bwd(const GemmParams& p, int m, int n, float (&v)[W]) {
+  const bfvec<W> gv = ld_bf<W>(p.dact_src + (int64_t)m * p.ld_dact + n), uv = ld_bf<W>(p.dact_src + (int64_t)m * p.ld_dact + p.N + n);
+  bfvec<W> du;
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float x = bfround(v[j]), y = bfround(vp[j]);
-    const float cc = bf2f((bf16_bits)cs[j]), sv = bf2f((bf16_bits)sn[j]);
-    o[j] = (short)f2bf(lo ? bfround(x * cc) + bfround(-y * sv) : bfround(x * cc) + bfround(y * sv));
+  for (int e = 0; e < W; ++e) {
+    const float d = v[e], g = bf2f((bf16_bits)gv[e]), u = bf2f((bf16_bits)uv[e]);
+    const float s = sigmoidf_(g);
+    du[e] = (short)f2bf(d * bfround(g * s));
+    v[e] = d * u * (s * (1.f + g * (1.f - s)));
   }
-  *reinterpret_cast<bf16x4_bits*>(p.C + (int64_t)m * p.ldc + n) = o;
+  st_bf<W>(p.C + (int64_t)m * p.ldc + p.N + n, du);
+}
+
+// The forward epilogue and the dact_mode 1 / 2 backward ones: v = accumulator sums on entry, the stored (bf16-rounded) values on return.
+// ACT: pre-activation save, activation, LayerScale compiled in;  TAIL: FiLM and the backward epilogues compiled in (the unrolled read-backs
+// exclude them by their host flags; the 256x256 instantiations also exclude ACT: unrolled activation code spills there);  RES_LOADED: the
+// caller requested the residual values earlier (`res`).
+template <int W, bool ACT = true, bool TAIL = true, bool RES_LOADED = false>
+OVLA_DEV void epi_forward(const GemmParams& p, int m, int n, float (&v)[W], float ra, const bfvec<W>& res = bfvec<W>{}) {
+#pragma unroll
+  for (int e = 0; e < W; ++e) v[e] = v[e] * ra;
+  if (p.bias) {
+    const bfvec<W> b = ld_bf<W>(p.bias + n);
+#pragma unroll
+    for (int e = 0; e < W; ++e) v[e] = v[e] + bf2f((bf16_bits)b[e]);
+  }
+#pragma unroll
+  for (int e = 0; e < W; ++e) v[e] = bfround(v[e]);
+  if constexpr (ACT) {
+    if (p.Cpre && !(TAIL && p.film_gamma)) st_bf<W>(p.Cpre + (int64_t)m * p.ldc + n, to_bf<W>(v));   // value before the activation (saved for the backward)
+    if (p.act != OVLA_ACT_NONE) {
+#pragma unroll
+      for (int e = 0; e < W; ++e) v[e] = bfround(apply_act(v[e], p.act));
+    }
+    if (p.colscale) {
+      const bfvec<W> s = ld_bf<W>(p.colscale + n);
+#pragma unroll
+      for (int e = 0; e < W; ++e) v[e] = bfround(v[e] * bf2f((bf16_bits)s[e]));
+    }
+  }
+  if (p.residual) {
+    bfvec<W> r = res;
+    if constexpr (!RES_LOADED) r = ld_bf<W>(p.residual + (int64_t)m * p.ldr + n);
+#pragma unroll
+    for (int e = 0; e < W; ++e) v[e] = bfround(v[e] + bf2f((bf16_bits)r[e]));
+  }
+  if constexpr (TAIL) {
+    if (p.film_gamma) {
+      if (p.Cpre) st_bf<W>(p.Cpre + (int64_t)m * p.ldc + n, to_bf<W>(v));   // with FiLM, C_pre receives the value BEFORE the modulation (needed for d gamma)
+      const int64_t off = (int64_t)(m / p.film_rows) * p.N + n;
+      const bfvec<W> g = ld_bf<W>(p.film_gamma + off), b = ld_bf<W>(p.film_beta + off);
+#pragma unroll
+      for (int e = 0; e < W; ++e) {
+        const float one_plus = bfround(1.0f + bf2f((bf16_bits)g[e]));
+        v[e] = bfround(bfround(v[e] * one_plus) + bf2f((bf16_bits)b[e]));
+      }
+    }
+    if (p.dact_mode == 1) {          // dz = dh * act'(z): same arithmetic as act_bwd_kernel on the bf16-rounded dh
+      const bfvec<W> z = ld_bf<W>(p.dact_src + (int64_t)m * p.ld_dact + n);
+#pragma unroll
+      for (int e = 0; e < W; ++e) v[e] = v[e] * act_grad(bf2f((bf16_bits)z[e]), p.dact_act);
+    } else if (p.dact_mode == 2) {   // two outputs per element
+      epi_swiglu_bwd<W>(p, m, n, v);
+    }
+  }
+  const bfvec<W> o = to_bf<W>(v);
+#pragma unroll
+  for (int e = 0; e < W; ++e) v[e] = bf2f((bf16_bits)o[e]);
+  if (OVLA_DBG(16) && v[0] != 123.456f) return;          // timing ablation: the whole epilogue except the store
+  if (OVLA_DBG(32)) {                                      // timing ablation: write-through store that does not stay in this XCD's L2
+    __builtin_nontemporal_store(o, reinterpret_cast<bfvec<W>*>(p.C + (int64_t)m * p.ldc + n));
+    return;
+  }
+  st_bf<W>(p.C + (int64_t)m * p.ldc + n, o);
+}
+
+// RoPE (head_dim 128): x = the accumulator sums at this lane's columns, y = the sums at the rotation partner columns n +- 64 of the same head,
+// cs / sn = the table values of the columns' position in the 64-wide half, upper = the columns lie in the head's upper half.  bf16(ra * acc) is
+// the q | k projection output the reference rotates; arithmetic and rounding points are rope_kernel's (elementwise.hip):
+// lo' = bf16(a c) + bf16(-b s), hi' = bf16(b c) + bf16(a s).
+template <int W>
+OVLA_DEV bfvec<W> epi_rope(const float (&x)[W], const float (&y)[W], bfvec<W> cs, bfvec<W> sn, bool upper, float ra) {
+  bfvec<W> o;
+#pragma unroll
+  for (int e = 0; e < W; ++e) {
+    const float a = bfround(x[e] * ra), b = bfround(y[e] * ra);
+    const float cc = bf2f((bf16_bits)cs[e]), sv = bf2f((bf16_bits)sn[e]);
+    o[e] = (short)f2bf(upper ? bfround(a * cc) + bfround(b * sv) : bfround(a * cc) + bfround(-b * sv));
+  }
+  return o;
+}
+// ... with the table loads and the store, 4 wide (the rolled read-backs and the remainder reduce)
+OVLA_DEV void rope_store(const GemmParams& p, int m, int n, const float (&x)[4], const float (&y)[4], float ra) {
+  const int c = n & 127, pos = m % p.rope_S;     // column within the head
+  const bf16x4_bits cs = ld_bf<4>(p.rope_cos + (int64_t)pos * 64 + (c & 63)), sn = ld_bf<4>(p.rope_sin + (int64_t)pos * 64 + (c & 63));
+  st_bf<4>(p.C + (int64_t)m * p.ldc + n, epi_rope<4>(x, y, cs, sn, c >= 64, ra));
+}
+
+// SwiGLU pair (swiglu_fwd_kernel's arithmetic on the bf16-rounded projection outputs): g / u = the gate sums at columns n .. and the up sums at
+// F + n ..;  C[m, n ..] = bf16(bf16(silu(g)) * u);  C_pre, if given, receives the [M, 2 F] projection output itself (contiguous: row stride N).
+template <int W>
+OVLA_DEV void epi_swiglu_pair(const GemmParams& p, int m, int n, const float (&g)[W], const float (&u)[W], float ra) {
+  bfvec<W> o, og, ou;
+#pragma unroll
+  for (int e = 0; e < W; ++e) {
+    og[e] = (short)f2bf(g[e] * ra); ou[e] = (short)f2bf(u[e] * ra);
+    o[e] = (short)f2bf(bfround(silu(bf2f((bf16_bits)og[e]))) * bf2f((bf16_bits)ou[e]));
+  }
+  st_bf<W>(p.C + (int64_t)m * p.ldc + n, o);
+  if (p.Cpre) {
+    st_bf<W>(p.Cpre + (int64_t)m * p.N + n, og);
+    st_bf<W>(p.Cpre + (int64_t)m * p.N + (p.N >> 1) + n, ou);
+  }
+}
+
+// RMSNorm fold, producer side: sum of squares of the stored values of row m's 64-column group, held W each by LANES = 64 / W consecutive
+// lanes (16 x 4 wide, 8 x 8 wide; aligned to LANES, in uniform control flow); the group's first lane stores (`first`: it is that lane and inside the matrix).
+template <int W>
+OVLA_DEV void epi_rowsq(const GemmParams& p, int m, int n, const float (&st)[W], bool first) {
+  float s = 0.f;
+#pragma unroll
+  for (int e = 0; e < W; ++e) s += st[e] * st[e];
+#pragma unroll
+  for (int o = 1; o < 64 / W; o <<= 1) s += __shfl_xor(s, o, 64);
+  if (first) p.rowsq_out[(int64_t)m * (p.N >> 6) + (n >> 6)] = s;
+}
+
+// ---- the accumulators' ways out of the registers, shared by the tile kernels -----------------------------------------------------------------
+// MFMA layout (operands swapped): of m-tile i and n-tile j a lane owns row 16 i + (lane & 15), columns 4 (lane >> 4) .. + 3 of the n-tile.
+// Every index into acc is a compile-time constant (static_for): the 4-wave kernel's accumulators live in AGPRs behind asm MFMAs, and one
+// dynamically indexed use would put all 256 of them into scratch memory.  `col[j]`: first column of n-tile j inside the tile.
+// RM m-tiles (round ROUND of the read-back) to the wave's fp32 LDS slab, row stride 16 NT + 4 floats (conflict-free ds_write_b128), and wait for them.
+template <int RM, int ROUND, int MT, int NT>
+OVLA_DEV void acc_to_slab(float* slab, int lane, const f32x4 (&acc)[MT][NT]) {
+  static_for<RM * NT>([&](auto e_tag) {
+    constexpr int ii = decltype(e_tag)::value / NT, j = decltype(e_tag)::value % NT;
+    *reinterpret_cast<f32x4*>(slab + (ii * 16 + (lane & 15)) * (NT * 16 + 4) + j * 16 + 4 * (lane >> 4)) = acc[ROUND * RM + ii][j];
+  });
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's own slab writes have landed
+}
+// split-K: raw fp32 partials [split][M][N]; the reduce kernel applies the epilogue
+template <int MT, int NT>
+OVLA_DEV void store_splitk_partial(const GemmParams& p, int split, int mbase, int n0, const int (&col)[NT], int lane, const f32x4 (&acc)[MT][NT]) {
+  static_for<MT * NT>([&](auto e_tag) {
+    constexpr int i = decltype(e_tag)::value / NT, j = decltype(e_tag)::value % NT;
+    const int m = mbase + i * 16 + (lane & 15), n = n0 + col[j] + 4 * (lane >> 4);
+    if (m < p.M && n < p.N) *reinterpret_cast<f32x4*>(p.ws + ((int64_t)split * p.M + m) * p.N + n) = acc[i][j];
+  });
+}
+// hybrid remainder unit: tile-local fp32 slab [rem_unit][BM][BN] (`row0`: the wave's first row inside the tile)
+template <int BM, int BN, int MT, int NT>
+OVLA_DEV void store_remainder_slab(const GemmParams& p, int rem_unit, int row0, const int (&col)[NT], int lane, const f32x4 (&acc)[MT][NT]) {
+  float* slab = p.ws + (int64_t)rem_unit * (BM * BN);
+  static_for<MT * NT>([&](auto e_tag) {
+    constexpr int i = decltype(e_tag)::value / NT, j = decltype(e_tag)::value % NT;
+    *reinterpret_cast<f32x4*>(slab + (row0 + i * 16 + (lane & 15)) * BN + col[j] + 4 * (lane >> 4)) = acc[i][j];
+  });
+}
+
+// The rolled read-back (edge tiles and every epilogue term): each round's RM m-tiles through the wave's slab, then 4 columns per lane and step,
+// 16 NT / 4 consecutive lanes per row.  ROPE: one slab row is one 128-wide head, the rotation partner quad is 16 quads away in the same row.
+// FOLD: the RMSNorm fold (16 NT = 64: a slab row is one 64-column group read back by 16 consecutive lanes; the host guarantees N % 64 == 0 with
+// rowsq_out, so the 16 lanes are inside or outside the matrix together and the shuffles run in uniform control flow); `rstd`: the factors of
+// the wave's rows (consumer side) or nullptr.  RMAP: the 4-wave kernel's RoPE column map (slab column -> output column; no producer side).
+template <int RM, bool ROPE, bool FOLD, bool RMAP, int MT, int NT>
+OVLA_DEV void readback_general(const GemmParams& p, float* slab, int lane, int mbase, int nbase, const float* rstd, const f32x4 (&acc)[MT][NT]) {
+  constexpr int LDSW = NT * 16 + 4, QUADS = NT * 4;
+  static_for<MT / RM>([&](auto rd_tag) {
+    constexpr int rd = decltype(rd_tag)::value;
+    acc_to_slab<RM, rd>(slab, lane, acc);
+#pragma unroll 1
+    for (int it = 0; it < RM * 16 * QUADS / 64; ++it) {
+      const int idx = it * 64 + lane, row = idx / QUADS, c4 = idx % QUADS;
+      float v[4];
+      ld_slab<4>(slab + row * LDSW + c4 * 4, v);
+      const int m = mbase + rd * RM * 16 + row, n = nbase + (RMAP ? ((c4 * 4) & 31) + 64 * ((c4 * 4) >> 5) : c4 * 4);
+      float ra = p.alpha;
+      if constexpr (FOLD) { if (rstd) ra *= rstd[rd * RM * 16 + row]; }
+      if constexpr (ROPE) {
+        if (p.rope_cos && n < p.rope_cols) {
+          float y[4];
+          ld_slab<4>(slab + row * LDSW + (c4 ^ 16) * 4, y);
+          if (m < p.M) rope_store(p, m, n, v, y, ra);
+          continue;
+        }
+      }
+      const bool inside = m < p.M && n < p.N;
+      if (inside) epi_forward<4>(p, m, n, v, ra);
+      if constexpr (FOLD && !RMAP) {
+        if (p.rowsq_out) {
+          if (!inside) v[0] = v[1] = v[2] = v[3] = 0.f;
+          epi_rowsq<4>(p, m, n, v, inside && c4 == 0);
+        }
+      }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (keeps the next round's slab writes behind this round's reads)
+  });
 }
 
 template <int BM, int BN>
@@ -311,7 +431,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_kernel(const GemmParams 
 #pragma unroll
     for (int j = 0; j < NT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  // RMSNorm fold, consumer side (128x128 config only): rstd of this tile's 128 rows from the producer's per-64-column sums of squares, into
+  // RMSNorm fold, consumer side (this kernel: the 128x128 config only): rstd of this tile's 128 rows from the producer's per-64-column sums of squares, into
   // LDS behind the K-tile buffers / epilogue slabs.  Two lanes per row, 8 16-byte loads each; they are in flight with the first K tile's
   // LDS-DMA and waited for by the same vmcnt(0), and the K loop's first barrier publishes s_rstd: the prologue costs no round trip of its own.
   constexpr bool NORMFOLD = (BM == 128 && BN == 128 && WM == 2 && WN == 2);
@@ -497,14 +617,8 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_kernel(const GemmParams 
     return;
   }
   // ---- epilogue ---------------------------------------------------------------------------------------------
-  // MFMA layout (operands swapped): lane owns C[m][n..n+3] with m = tile row (lane&15), n = 4*(lane>>4).
-  if (rem_unit >= 0) {  // hybrid remainder unit: tile-local fp32 slab [rem_unit][BM][BN]
-    float* slab = p.ws + (int64_t)rem_unit * (BM * BN);
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-      for (int j = 0; j < NT; ++j)
-        *reinterpret_cast<f32x4*>(slab + (wm * WTM + i * 16 + (lane & 15)) * BN + bcol[j] + 4 * (lane >> 4)) = acc[i][j];
+  if (rem_unit >= 0) {
+    store_remainder_slab<BM, BN>(p, rem_unit, wm * WTM, bcol, lane, acc);
     if (p.hyb_cnt == nullptr) return;          // the separate gemm_hybrid_reduce_kernel launch does the rest
     // In-launch reduce: the LAST of a tile's rem_splits units to arrive adds the slabs (its own included, from memory, in slab order: the same
     // bits as the reduce kernel) and runs the epilogue.  Arrival = agent-scope release of the workgroup's slab stores + one relaxed atomic on the
@@ -531,16 +645,8 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_kernel(const GemmParams 
     hybrid_reduce_quads<BM, BN>(p, rem_unit / p.rem_splits, tid, 64 * NW);
     return;
   }
-  if (p.split_k > 1) {  // raw fp32 partials; the reduce kernel applies the epilogue
-#pragma unroll
-    for (int i = 0; i < MT; ++i) {
-      const int m = m0 + wm * WTM + i * 16 + (lane & 15);
-#pragma unroll
-      for (int j = 0; j < NT; ++j) {
-        const int n = n0 + wn * WTN + j * 16 + 4 * (lane >> 4);
-        if (m < p.M && n < p.N) *reinterpret_cast<f32x4*>(p.ws + ((int64_t)split * p.M + m) * p.N + n) = acc[i][j];
-      }
-    }
+  if (p.split_k > 1) {   // (RoPE is never fused into a split-K launch: bcol is the plain map here)
+    store_splitk_partial(p, split, m0 + wm * WTM, n0, bcol, lane, acc);
     return;
   }
   // Accumulators go through a wave-private fp32 LDS slab (32 rows at a time, row stride WTN+4 floats: conflict-free
@@ -550,222 +656,108 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_kernel(const GemmParams 
   // waves may still be reading), then only LDS waits.
   constexpr int LDSW = WTN + 4;
   constexpr int RM = MT < 2 ? MT : 2;  // m-tiles per round
-  constexpr int QUADS = WTN / 4;       // 4-column groups per sub-tile row
+  constexpr int OCT = WTN / 8;         // 8-column groups per slab row
   float* wstage = reinterpret_cast<float*>(smem_raw) + wave * (RM * 16 * LDSW);
-  // Fast path: interior tile, every epilogue term except FiLM / the backward epilogues / RoPE (alpha, bias, pre-activation save,
-  // activation, LayerScale, residual: every Llama and ViT projection, forward and data-gradient).  Fully unrolled read-back, 8 columns
-  // = one 16-byte store per lane and step, no bounds checks.  (tools/gemm_ablate.py, tile + 8000: the rolled general loop below cost
-  // 11-17 % of a 256x256 tile's time and 44 % of a ViT fc1 launch: bias + GELU + pre-activation save.)
-  // (the 256x256 configs hold 128 accumulator registers: unrolling the activation code there spills, and no 256x256-tiled GEMM of
-  // this model has an activation -- those keep the alpha / bias / residual subset)
-  if ((WTN % 8) == 0 && p.fast_swiglu_bwd && m0 + BM <= p.M && n0 + BN <= p.N) {
-    // SwiGLU backward in the unrolled read-back (swiglu_bwd_kernel's arithmetic on the bf16-rounded d h, as epilogue_store's dact_mode 2): this
-    // tile of d h = dy . W_down yields d gate AND d up for its columns; gate / up come from the saved [M, 2N] projection output.
-    constexpr int OCT = WTN / 8;
+  const int mbase = m0 + wm * WTM, nbase = n0 + wn * WTN;
+  const bool interior = m0 + BM <= p.M && n0 + BN <= p.N;
+  auto row_factor = [&](int row) {   // alpha (* rstd of the wave's slab row `row` with the fold)
+    float ra = p.alpha;
+    if constexpr (NORMFOLD) { if (rowscale) ra *= s_rstd[wm * WTM + row]; }
+    return ra;
+  };
+  // The unrolled read-backs: interior tiles, 8 columns = one 16-byte store per lane and step, no bounds checks.  (tools/gemm_ablate.py,
+  // tile + 8000: the rolled general loop cost 11-17 % of a 256x256 tile's time and 44 % of a ViT fc1 launch: bias + GELU + pre-activation save.)
+  if (p.fast_swiglu_bwd && interior) {
+    // SwiGLU backward: this tile of d h = dy . W_down yields d gate AND d up for its columns; gate / up come from the saved [M, 2N] projection output.
     constexpr int STEPS = RM * 16 * OCT / 64;
-    const int mbase = m0 + wm * WTM, nbase = n0 + wn * WTN;
     __syncthreads();
-#pragma unroll
-    for (int round = 0; round < MT / RM; ++round) {
-#pragma unroll
-      for (int ii = 0; ii < RM; ++ii)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-          *reinterpret_cast<f32x4*>(wstage + (ii * 16 + (lane & 15)) * LDSW + j * 16 + 4 * (lane >> 4)) = acc[round * RM + ii][j];
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    static_for<MT / RM>([&](auto rd_tag) {
+      constexpr int round = decltype(rd_tag)::value;
+      acc_to_slab<RM, round>(wstage, lane, acc);
 #pragma unroll
       for (int st = 0; st < STEPS; ++st) {
         const int idx = st * 64 + lane, row = idx / OCT, c8 = idx % OCT;
-        const f32x4 lo = *reinterpret_cast<const f32x4*>(wstage + row * LDSW + c8 * 8), hi = *reinterpret_cast<const f32x4*>(wstage + row * LDSW + c8 * 8 + 4);
         const int m = mbase + round * RM * 16 + row, n = nbase + c8 * 8;
-        const bf16x8_bits g8 = *reinterpret_cast<const bf16x8_bits*>(p.dact_src + (int64_t)m * p.ld_dact + n);
-        const bf16x8_bits u8 = *reinterpret_cast<const bf16x8_bits*>(p.dact_src + (int64_t)m * p.ld_dact + p.N + n);
-        bf16x8_bits dg, du;
+        float x[8];
+        ld_slab<8>(wstage + row * LDSW + c8 * 8, x);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float d = bfround((e < 4 ? lo[e] : hi[e - 4]) * p.alpha), g = bf2f((bf16_bits)g8[e]), u = bf2f((bf16_bits)u8[e]);
-          const float sg = sigmoidf_(g);
-          du[e] = (short)f2bf(d * bfround(g * sg));
-          dg[e] = (short)f2bf(d * u * (sg * (1.f + g * (1.f - sg))));
-        }
-        *reinterpret_cast<bf16x8_bits*>(p.C + (int64_t)m * p.ldc + n) = dg;
-        *reinterpret_cast<bf16x8_bits*>(p.C + (int64_t)m * p.ldc + p.N + n) = du;
+        for (int e = 0; e < 8; ++e) x[e] = bfround(x[e] * p.alpha);
+        epi_swiglu_bwd<8>(p, m, n, x);
+        st_bf<8>(p.C + (int64_t)m * p.ldc + n, to_bf<8>(x));
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    }
+    });
     return;
   }
   if constexpr (ROPE_LAYOUT) {
-    if (rope_tile) {   // RoPE in the unrolled read-back (host guarantees whole column tiles, alpha only, 16-byte aligned tables; rows past M are skipped)
+    if (rope_tile) {   // RoPE (host guarantees whole column tiles, alpha only, 16-byte aligned tables; rows past M are skipped)
       constexpr int STEPS = RM * 16 * 8 / 64;
-      const int mbase = m0 + wm * WTM, nhead = n0 + (wn >> 1) * 128, chalf = (wn & 1) * 32;
+      const int nhead = n0 + (wn >> 1) * 128, chalf = (wn & 1) * 32;
       __syncthreads();
-#pragma unroll
-      for (int round = 0; round < MT / RM; ++round) {
-#pragma unroll
-        for (int ii = 0; ii < RM; ++ii)
-#pragma unroll
-          for (int j = 0; j < NT; ++j)
-            *reinterpret_cast<f32x4*>(wstage + (ii * 16 + (lane & 15)) * LDSW + j * 16 + 4 * (lane >> 4)) = acc[round * RM + ii][j];
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      static_for<MT / RM>([&](auto rd_tag) {
+        constexpr int round = decltype(rd_tag)::value;
+        acc_to_slab<RM, round>(wstage, lane, acc);
 #pragma unroll
         for (int st = 0; st < STEPS; ++st) {
           const int idx = st * 64 + lane, row = idx >> 3, c8 = idx & 7;
-          const float* xs = wstage + row * LDSW + c8 * 8;
-          const float* ys = wstage + row * LDSW + (c8 ^ 4) * 8;          // rotation partner: slab column +- 32 = output column +- 64
-          const f32x4 xlo = *reinterpret_cast<const f32x4*>(xs), xhi = *reinterpret_cast<const f32x4*>(xs + 4);
-          const f32x4 ylo = *reinterpret_cast<const f32x4*>(ys), yhi = *reinterpret_cast<const f32x4*>(ys + 4);
+          float x[8], y[8];
+          ld_slab<8>(wstage + row * LDSW + c8 * 8, x);
+          ld_slab<8>(wstage + row * LDSW + (c8 ^ 4) * 8, y);            // rotation partner: slab column +- 32 = output column +- 64
           const int cin = chalf + ((c8 & 3) << 3);                         // column within the 64-wide half of the head
           const bool upper = c8 >= 4;
           const int m = mbase + round * RM * 16 + row, n = nhead + cin + (upper ? 64 : 0);
-          float ra = p.alpha;
-          if constexpr (NORMFOLD) { if (rowscale) ra *= s_rstd[wm * WTM + round * RM * 16 + row]; }
           const int pos = m % p.rope_S;
-          const bf16x8_bits cs = *reinterpret_cast<const bf16x8_bits*>(p.rope_cos + (int64_t)pos * 64 + cin);
-          const bf16x8_bits sn = *reinterpret_cast<const bf16x8_bits*>(p.rope_sin + (int64_t)pos * 64 + cin);
-          bf16x8_bits o;
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {    // rope_kernel's arithmetic on y = bf16(acc): lo' = bf16(a c) + bf16(-b s), hi' = bf16(b c) + bf16(a s)
-            const float x = bfround((e < 4 ? xlo[e] : xhi[e - 4]) * ra), y = bfround((e < 4 ? ylo[e] : yhi[e - 4]) * ra);
-            const float cc = bf2f((bf16_bits)cs[e]), sv = bf2f((bf16_bits)sn[e]);
-            o[e] = (short)f2bf(upper ? bfround(x * cc) + bfround(y * sv) : bfround(x * cc) + bfround(-y * sv));
-          }
-          if (m < p.M) *reinterpret_cast<bf16x8_bits*>(p.C + (int64_t)m * p.ldc + n) = o;
+          const bf16x8_bits o = epi_rope<8>(x, y, ld_bf<8>(p.rope_cos + (int64_t)pos * 64 + cin), ld_bf<8>(p.rope_sin + (int64_t)pos * 64 + cin), upper,
+                                            row_factor(round * RM * 16 + row));
+          if (m < p.M) st_bf<8>(p.C + (int64_t)m * p.ldc + n, o);
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      }
+      });
       return;
     }
   }
+  // Every epilogue term except FiLM / the backward epilogues / RoPE (alpha, bias, pre-activation save, activation, LayerScale, residual: every
+  // Llama and ViT projection, forward and data-gradient).  (The 256x256 configs hold 128 accumulator registers: unrolling the activation code
+  // there spills, and no 256x256-tiled GEMM of this model has an activation -- those keep the alpha / bias / residual subset.)
   constexpr bool FAST_ACT = MT * NT <= 16;
-  if (p.fast_epi && (FAST_ACT || (p.act == OVLA_ACT_NONE && !p.Cpre && !p.colscale)) && !OVLA_DBG(64) && m0 + BM <= p.M && n0 + BN <= p.N &&
-      (WTN % 8) == 0) {
-    constexpr int OCT = WTN / 8;                 // 8-column groups per slab row
+  if (p.fast_epi && (FAST_ACT || (p.act == OVLA_ACT_NONE && !p.Cpre && !p.colscale)) && !OVLA_DBG(64) && interior) {
     constexpr int STEPS = RM * 16 * OCT / 64;    // read-back steps per round
-    const int mbase = m0 + wm * WTM, nbase = n0 + wn * WTN;
     __syncthreads();
-#pragma unroll
-    for (int round = 0; round < MT / RM; ++round) {
-#pragma unroll
-      for (int ii = 0; ii < RM; ++ii)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-          *reinterpret_cast<f32x4*>(wstage + (ii * 16 + (lane & 15)) * LDSW + j * 16 + 4 * (lane >> 4)) = acc[round * RM + ii][j];
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's own slab writes have landed
+    static_for<MT / RM>([&](auto rd_tag) {
+      constexpr int round = decltype(rd_tag)::value;
+      acc_to_slab<RM, round>(wstage, lane, acc);
       constexpr int GRP = STEPS < 2 ? STEPS : 2;   // read-back steps in flight (the accumulators of later rounds are still live)
 #pragma unroll
       for (int st0 = 0; st0 < STEPS; st0 += GRP) {
-      f32x4 lo[GRP], hi[GRP];
+        float x[GRP][8];
 #pragma unroll
-      for (int s2 = 0; s2 < GRP; ++s2) {
-        const int idx = (st0 + s2) * 64 + lane, row = idx / OCT, c8 = idx % OCT;
-        lo[s2] = *reinterpret_cast<const f32x4*>(wstage + row * LDSW + c8 * 8);
-        hi[s2] = *reinterpret_cast<const f32x4*>(wstage + row * LDSW + c8 * 8 + 4);
-      }
-#pragma unroll
-      for (int s2 = 0; s2 < GRP; ++s2) {
-        const int st = st0 + s2;
-        const int idx = st * 64 + lane, row = idx / OCT, c8 = idx % OCT;
-        const int m = mbase + round * RM * 16 + row, n = nbase + c8 * 8;
-        float x[8];
-        float ra = p.alpha;
-        if constexpr (NORMFOLD) { if (rowscale) ra *= s_rstd[wm * WTM + round * RM * 16 + row]; }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { x[e] = lo[s2][e] * ra; x[4 + e] = hi[s2][e] * ra; }
-        if (p.bias) {
-          const bf16x8_bits b8 = *reinterpret_cast<const bf16x8_bits*>(p.bias + n);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) x[e] = x[e] + bf2f((bf16_bits)b8[e]);
+        for (int s2 = 0; s2 < GRP; ++s2) {
+          const int idx = (st0 + s2) * 64 + lane, row = idx / OCT, c8 = idx % OCT;
+          ld_slab<8>(wstage + row * LDSW + c8 * 8, x[s2]);
         }
 #pragma unroll
-        for (int e = 0; e < 8; ++e) x[e] = bfround(x[e]);
-        if constexpr (FAST_ACT) {
-          if (p.Cpre) {        // value before the activation, saved for the backward
-            bf16x8_bits z;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) z[e] = (short)f2bf(x[e]);
-            *reinterpret_cast<bf16x8_bits*>(p.Cpre + (int64_t)m * p.ldc + n) = z;
-          }
-          if (p.act != OVLA_ACT_NONE) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) x[e] = bfround(apply_act(x[e], p.act));
-          }
-          if (p.colscale) {
-            const bf16x8_bits c8 = *reinterpret_cast<const bf16x8_bits*>(p.colscale + n);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) x[e] = bfround(x[e] * bf2f((bf16_bits)c8[e]));
+        for (int s2 = 0; s2 < GRP; ++s2) {
+          const int idx = (st0 + s2) * 64 + lane, row = idx / OCT, c8 = idx % OCT;
+          const int m = mbase + round * RM * 16 + row, n = nbase + c8 * 8;
+          epi_forward<8, FAST_ACT, false>(p, m, n, x[s2], row_factor(round * RM * 16 + row));
+          if constexpr (NORMFOLD) {   // producer side: this wave's slab row is one 64-column group of row m
+            if (p.rowsq_out) epi_rowsq<8>(p, m, n, x[s2], c8 == 0);
           }
         }
-        if (p.residual) {
-          const bf16x8_bits r8 = *reinterpret_cast<const bf16x8_bits*>(p.residual + (int64_t)m * p.ldr + n);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) x[e] = bfround(x[e] + bf2f((bf16_bits)r8[e]));
-        }
-        bf16x8_bits o;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = (short)f2bf(x[e]);
-        if constexpr (NORMFOLD) {
-          if (p.rowsq_out) {   // producer side: this wave's 64-column group of row m = 8 lanes x 8 stored values (x is already bf16-rounded here)
-            float sq = 0.f;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { const float f = bf2f((bf16_bits)o[e]); sq += f * f; }
-            sq += __shfl_xor(sq, 1, 64); sq += __shfl_xor(sq, 2, 64); sq += __shfl_xor(sq, 4, 64);
-            if (c8 == 0) p.rowsq_out[(int64_t)m * (p.N >> 6) + (nbase >> 6)] = sq;
-          }
-        }
-        if (OVLA_DBG(32)) __builtin_nontemporal_store(o, reinterpret_cast<bf16x8_bits*>(p.C + (int64_t)m * p.ldc + n));
-        else *reinterpret_cast<bf16x8_bits*>(p.C + (int64_t)m * p.ldc + n) = o;
-      }
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (reads consumed above; keeps the next round's writes behind them)
-    }
+    });
 #ifdef OVLA_GEMM_STAMPS
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the tile's stores have been acknowledged
     OVLA_STAMP(4);
 #endif
     return;
   }
-  // General path (activations, pre-activation save, LayerScale, FiLM, backward epilogues, RoPE, edge tiles): one rolled loop.
+  // General path (activations, pre-activation save, LayerScale, FiLM, backward epilogues, RoPE, edge tiles).
   __syncthreads();  // every wave is done reading the K-tile buffers the slabs alias; from here on a wave touches only its own slab
-#pragma unroll
-  for (int round = 0; round < MT / RM; ++round) {
-#pragma unroll
-    for (int ii = 0; ii < RM; ++ii)
-#pragma unroll
-      for (int j = 0; j < NT; ++j)
-        *reinterpret_cast<f32x4*>(wstage + (ii * 16 + (lane & 15)) * LDSW + j * 16 + 4 * (lane >> 4)) = acc[round * RM + ii][j];
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll 1
-    for (int it = 0; it < RM * 16 * QUADS / 64; ++it) {
-      const int idx = it * 64 + lane;
-      const int row = idx / QUADS, c4 = idx % QUADS;
-      const f32x4 v = *reinterpret_cast<const f32x4*>(wstage + row * LDSW + c4 * 4);
-      const int m = m0 + wm * WTM + round * RM * 16 + row;
-      const int n = n0 + wn * WTN + c4 * 4;
-      if constexpr (WTN == 128) {   // one wave slab = one 128-wide head: the rotation partner quad is 16 quads away in the same slab row
-        if (p.rope_cos && n < p.rope_cols) {
-          const f32x4 vp = *reinterpret_cast<const f32x4*>(wstage + row * LDSW + (c4 ^ 16) * 4);
-          if (m < p.M) rope_store(p, m, n, v, vp);
-          continue;
-        }
-      }
-      if constexpr (NORMFOLD) {
-        // (WTN = 64: a slab row is one 64-column group, read back by 16 consecutive lanes; the host guarantees N % 64 == 0, so the 16 lanes of
-        // a row are inside or outside the matrix together and the shuffles run in uniform control flow)
-        f32x4 vs = v;
-        if (rowscale) vs *= s_rstd[wm * WTM + round * RM * 16 + row];
-        f32x4 st = {0.f, 0.f, 0.f, 0.f};
-        const bool inside = m < p.M && n < p.N;
-        if (inside) st = epilogue_store(p, m, n, vs);
-        if (p.rowsq_out) {
-          const float sq = rowsq16(st);
-          if (inside && c4 == 0) p.rowsq_out[(int64_t)m * (p.N >> 6) + (n >> 6)] = sq;
-        }
-        continue;
-      }
-      if (m < p.M && n < p.N) epilogue_store(p, m, n, v);
-    }
-  }
+  const float* rstd = nullptr;
+  if constexpr (NORMFOLD) { if (rowscale) rstd = s_rstd + wm * WTM; }
+  readback_general<RM, WTN == 128, NORMFOLD, false>(p, wstage, lane, mbase, nbase, rstd, acc);
 }
 
 // =====================================================================================================================
@@ -1114,21 +1106,19 @@ __global__ __launch_bounds__(256) void gemm_nt_w4_kernel(const GemmParams p) {
   asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 7" ::: "memory");   // the compiler's hazard recognizer does not see the asm MFMAs' AGPR writes
   OVLA_STAMP(3);
 
+  // The epilogue takes the lane id from an opaque copy: whatever it derived from `lane` itself the compiler would share with the prologue's
+  // staging addresses and keep in VGPRs across the K loop (two such values cost the 128x256 RoPE instantiation its second wave per SIMD).
+  int elane = lane;
+  asm volatile("" : "+v"(elane));
   // (compile-time indices everywhere: one dynamically indexed use would keep the accumulator array in scratch memory, written through after every MFMA)
+  int wcol[NT];   // first column of n-tile j inside the tile
+  static_for<NT>([&](auto j_tag) { constexpr int j = decltype(j_tag)::value; wcol[j] = cb + cj(j); });
   if (rem_unit >= 0) {
-    float* slab = p.ws + (int64_t)rem_unit * (BM * BN);
-    static_for<MT * NT>([&](auto e_tag) {
-      constexpr int i = decltype(e_tag)::value / NT, j = decltype(e_tag)::value % NT;
-      *reinterpret_cast<f32x4*>(slab + (wm * WTM + i * 16 + (lane & 15)) * BN + cb + cj(j) + 4 * (lane >> 4)) = acc[i][j];
-    });
+    store_remainder_slab<BM, BN>(p, rem_unit, wm * WTM, wcol, elane, acc);
     return;
   }
   if (p.split_k > 1) {
-    static_for<MT * NT>([&](auto e_tag) {
-      constexpr int i = decltype(e_tag)::value / NT, j = decltype(e_tag)::value % NT;
-      const int m = m0 + wm * WTM + i * 16 + (lane & 15), n = n0 + cb + cj(j) + 4 * (lane >> 4);
-      if (m < p.M && n < p.N) *reinterpret_cast<f32x4*>(p.ws + ((int64_t)split * p.M + m) * p.N + n) = acc[i][j];
-    });
+    store_splitk_partial(p, split, m0 + wm * WTM, n0, wcol, elane, acc);
     return;
   }
   // accumulators -> wave-private fp32 LDS slab (two m-tiles = 32 rows x (128 + 4) per round, four rounds) -> read back in row order, 16 lanes per row,
@@ -1140,181 +1130,90 @@ __global__ __launch_bounds__(256) void gemm_nt_w4_kernel(const GemmParams p) {
   const int mbase = m0 + wm * WTM, nbase = n0 + cb;   // (RMAP: a slab column sc is output column nbase + scol(sc))
   __syncthreads();   // nobody reads the K tiles any more; from here on a wave touches only its own slab
   constexpr int OCT = WTN / 8, STEPS = 32 * OCT / 64;   // 8-column groups per slab row; read-back steps per round (8 / 4)
-  auto to_slab = [&](auto rd_tag) {
-    constexpr int rd = decltype(rd_tag)::value;
-    static_for<2 * NT>([&](auto e_tag) {
-      constexpr int ii = decltype(e_tag)::value / NT, j = decltype(e_tag)::value % NT;
-      *reinterpret_cast<f32x4*>(slab + (ii * 16 + (lane & 15)) * LDSW + j * 16 + 4 * (lane >> 4)) = acc[rd * 2 + ii][j];
-    });
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  };
   const bool interior = m0 + BM <= p.M && n0 + BN <= p.N;
-  if (WNW == 2 && p.rope_cos && nbase < p.rope_cols) {   // RoPE, 256x256 configuration (head_dim 128 = this wave's 128 columns): the rotation partner of octet c8 is octet c8 ^ 8 of the same slab row
+  auto row_factor = [&](int row) {   // alpha (* rstd of the tile's row `row` with the fold: 128x256 configuration)
+    float ra = p.alpha;
+    if constexpr (WNW == 4) { if (rowscale) ra *= s_rstd[row]; }
+    return ra;
+  };
+  // RoPE.  256x256 configuration: head_dim 128 = this wave's 128 columns, the rotation partner of octet c8 is octet c8 ^ 8 of the same slab row.
+  // 128x256 configuration (RMAP): slab columns [0, 32) are the lower-half columns 32 w2 + c of the head, [32, 64) their partners + 64: octet c8 ^ 4.
+  if ((WNW == 2 && p.rope_cos && nbase < p.rope_cols) || (RMAP && p.rope_cos && n0 + (wn >> 1) * 128 < p.rope_cols)) {
+    constexpr int HALF = OCT / 2;   // octets per half head in a slab row
     static_for<MT / 2>([&](auto rd_tag) {
       constexpr int rd = decltype(rd_tag)::value;
-      bf16x8_bits csv[8], snv[8];
+      bf16x8_bits csv[STEPS], snv[STEPS];
 #pragma unroll
-      for (int st = 0; st < 8; ++st) {
-        const int idx = st * 64 + lane, row = idx >> 4, c8 = idx & 15;
-        const int m = mbase + rd * 32 + row, cin = (c8 & 7) * 8;
+      for (int st = 0; st < STEPS; ++st) {
+        const int idx = st * 64 + elane, row = idx / OCT, c8 = idx % OCT;
+        const int m = mbase + rd * 32 + row, cin = (RMAP ? (wn & 1) * 32 : 0) + (c8 & (HALF - 1)) * 8;
         const int pos = (m < p.M ? m : p.M - 1) % p.rope_S;
-        csv[st] = *reinterpret_cast<const bf16x8_bits*>(p.rope_cos + (int64_t)pos * 64 + cin);
-        snv[st] = *reinterpret_cast<const bf16x8_bits*>(p.rope_sin + (int64_t)pos * 64 + cin);
+        csv[st] = ld_bf<8>(p.rope_cos + (int64_t)pos * 64 + cin);
+        snv[st] = ld_bf<8>(p.rope_sin + (int64_t)pos * 64 + cin);
       }
-      to_slab(rd_tag);
+      acc_to_slab<2, rd>(slab, elane, acc);
 #pragma unroll
-      for (int st = 0; st < 8; ++st) {
-        const int idx = st * 64 + lane, row = idx >> 4, c8 = idx & 15;
-        const float* xs = slab + row * LDSW + c8 * 8;
-        const float* ys = slab + row * LDSW + (c8 ^ 8) * 8;
-        const f32x4 xlo = *reinterpret_cast<const f32x4*>(xs), xhi = *reinterpret_cast<const f32x4*>(xs + 4);
-        const f32x4 ylo = *reinterpret_cast<const f32x4*>(ys), yhi = *reinterpret_cast<const f32x4*>(ys + 4);
-        const int m = mbase + rd * 32 + row, n = nbase + c8 * 8;
-        const bool upper = c8 >= 8;
-        const bf16x8_bits cs = csv[st], sn = snv[st];
-        bf16x8_bits o;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {    // rope_kernel's arithmetic on y = bf16(acc): lo' = bf16(a c) + bf16(-b s), hi' = bf16(b c) + bf16(a s)
-          const float x = bfround((e < 4 ? xlo[e] : xhi[e - 4]) * p.alpha), y = bfround((e < 4 ? ylo[e] : yhi[e - 4]) * p.alpha);
-          const float cc = bf2f((bf16_bits)cs[e]), sv = bf2f((bf16_bits)sn[e]);
-          o[e] = (short)f2bf(upper ? bfround(x * cc) + bfround(y * sv) : bfround(x * cc) + bfround(-y * sv));
-        }
-        if (m < p.M && n < p.N) *reinterpret_cast<bf16x8_bits*>(p.C + (int64_t)m * p.ldc + n) = o;
+      for (int st = 0; st < STEPS; ++st) {
+        const int idx = st * 64 + elane, row = idx / OCT, c8 = idx % OCT;
+        float x[8], y[8];
+        ld_slab<8>(slab + row * LDSW + c8 * 8, x);
+        ld_slab<8>(slab + row * LDSW + (c8 ^ HALF) * 8, y);
+        const int m = mbase + rd * 32 + row, n = nbase + scol(c8 * 8);
+        const bf16x8_bits o = epi_rope<8>(x, y, csv[st], snv[st], c8 >= HALF, row_factor(rd * 32 + row));
+        if (m < p.M && n < p.N) st_bf<8>(p.C + (int64_t)m * p.ldc + n, o);
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     });
     return;
   }
-  if constexpr (GMAP) {   // SwiGLU in the read-back (swiglu_fwd_kernel's arithmetic on the bf16-rounded projection outputs): h = bf16(bf16(silu(g)) * u)
-    constexpr int HO = OCT / 2, GST = 32 * HO / 64;   // output octets per slab row (gate octet c8 and its up partner HO octets on); read-back steps per round (4 / 2)
-    const int F = p.N >> 1;
+  if constexpr (GMAP) {   // SwiGLU in the read-back: gate octet c8 and its up partner HO octets on
+    constexpr int HO = OCT / 2, GST = 32 * HO / 64;   // output octets per slab row; read-back steps per round (4 / 2)
     static_for<MT / 2>([&](auto rd_tag) {
       constexpr int rd = decltype(rd_tag)::value;
-      to_slab(rd_tag);
-      f32x4 gl[GST], gh[GST], ul[GST], uh[GST];
+      acc_to_slab<2, rd>(slab, elane, acc);
+      float gv[GST][8], uv[GST][8];
 #pragma unroll
       for (int st = 0; st < GST; ++st) {
-        const int idx = st * 64 + lane, row = idx / HO, c8 = idx % HO;
-        const float* gs = slab + row * LDSW + c8 * 8;
-        gl[st] = *reinterpret_cast<const f32x4*>(gs); gh[st] = *reinterpret_cast<const f32x4*>(gs + 4);
-        ul[st] = *reinterpret_cast<const f32x4*>(gs + WTN / 2); uh[st] = *reinterpret_cast<const f32x4*>(gs + WTN / 2 + 4);
+        const int idx = st * 64 + elane, row = idx / HO, c8 = idx % HO;
+        ld_slab<8>(slab + row * LDSW + c8 * 8, gv[st]);
+        ld_slab<8>(slab + row * LDSW + c8 * 8 + WTN / 2, uv[st]);
       }
 #pragma unroll
       for (int st = 0; st < GST; ++st) {
-        const int idx = st * 64 + lane, row = idx / HO, c8 = idx % HO;
+        const int idx = st * 64 + elane, row = idx / HO, c8 = idx % HO;
         const int m = mbase + rd * 32 + row, n = n0 + cb + c8 * 8;
-        float ra = p.alpha;
-        if constexpr (WNW == 4) { if (rowscale) ra *= s_rstd[rd * 32 + row]; }
-        bf16x8_bits o, og, ou;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          og[e] = (short)f2bf((e < 4 ? gl[st][e] : gh[st][e - 4]) * ra); ou[e] = (short)f2bf((e < 4 ? ul[st][e] : uh[st][e - 4]) * ra);
-          o[e] = (short)f2bf(bfround(silu(bf2f((bf16_bits)og[e]))) * bf2f((bf16_bits)ou[e]));
-        }
-        if (m < p.M && n < F) {
-          *reinterpret_cast<bf16x8_bits*>(p.C + (int64_t)m * p.ldc + n) = o;
-          if (p.Cpre) {   // the projection output itself, [M, 2 F] with row stride N
-            *reinterpret_cast<bf16x8_bits*>(p.Cpre + (int64_t)m * p.N + n) = og;
-            *reinterpret_cast<bf16x8_bits*>(p.Cpre + (int64_t)m * p.N + F + n) = ou;
-          }
-        }
+        if (m < p.M && n < (p.N >> 1)) epi_swiglu_pair<8>(p, m, n, gv[st], uv[st], row_factor(rd * 32 + row));
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     });
     return;
-  }
-  if constexpr (RMAP) {
-    if (p.rope_cos && n0 + (wn >> 1) * 128 < p.rope_cols) {   // RoPE, 128x256 configuration: slab columns [0, 32) are the lower-half columns 32 w2 + c of the head, [32, 64) their partners + 64
-      static_for<MT / 2>([&](auto rd_tag) {
-        constexpr int rd = decltype(rd_tag)::value;
-        bf16x8_bits csv[STEPS], snv[STEPS];
-#pragma unroll
-        for (int st = 0; st < STEPS; ++st) {
-          const int idx = st * 64 + lane, row = idx / OCT, c8 = idx % OCT;
-          const int m = mbase + rd * 32 + row, cin = (wn & 1) * 32 + (c8 & 3) * 8;
-          const int pos = (m < p.M ? m : p.M - 1) % p.rope_S;
-          csv[st] = *reinterpret_cast<const bf16x8_bits*>(p.rope_cos + (int64_t)pos * 64 + cin);
-          snv[st] = *reinterpret_cast<const bf16x8_bits*>(p.rope_sin + (int64_t)pos * 64 + cin);
-        }
-        to_slab(rd_tag);
-#pragma unroll
-        for (int st = 0; st < STEPS; ++st) {
-          const int idx = st * 64 + lane, row = idx / OCT, c8 = idx % OCT;
-          const float* xs = slab + row * LDSW + c8 * 8;
-          const float* ys = slab + row * LDSW + (c8 ^ 4) * 8;
-          const f32x4 xlo = *reinterpret_cast<const f32x4*>(xs), xhi = *reinterpret_cast<const f32x4*>(xs + 4);
-          const f32x4 ylo = *reinterpret_cast<const f32x4*>(ys), yhi = *reinterpret_cast<const f32x4*>(ys + 4);
-          const int m = mbase + rd * 32 + row, n = nbase + scol(c8 * 8);
-          const bool upper = c8 >= 4;
-          const float ra = p.alpha * (rowscale ? s_rstd[rd * 32 + row] : 1.f);
-          const bf16x8_bits cs = csv[st], sn = snv[st];
-          bf16x8_bits o;
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {    // rope_kernel's arithmetic on y = bf16(acc): lo' = bf16(a c) + bf16(-b s), hi' = bf16(b c) + bf16(a s)
-            const float x = bfround((e < 4 ? xlo[e] : xhi[e - 4]) * ra), y = bfround((e < 4 ? ylo[e] : yhi[e - 4]) * ra);
-            const float cc = bf2f((bf16_bits)cs[e]), sv = bf2f((bf16_bits)sn[e]);
-            o[e] = (short)f2bf(upper ? bfround(x * cc) + bfround(y * sv) : bfround(x * cc) + bfround(-y * sv));
-          }
-          if (m < p.M && n < p.N) *reinterpret_cast<bf16x8_bits*>(p.C + (int64_t)m * p.ldc + n) = o;
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      });
-      return;
-    }
   }
   if (p.fast_epi && interior && p.act == OVLA_ACT_NONE && !p.Cpre && !p.colscale) {   // alpha, bias, residual: every Llama projection, forward and data-gradient
     static_for<MT / 2>([&](auto rd_tag) {
       constexpr int rd = decltype(rd_tag)::value;
-      constexpr int GRP = STEPS;
-      bf16x8_bits r8[GRP];
+      bf16x8_bits r8[STEPS];
       if (p.residual) {
 #pragma unroll
-        for (int s2 = 0; s2 < GRP; ++s2) {
-          const int idx = s2 * 64 + lane, row = idx / OCT, c8 = idx % OCT;
-          r8[s2] = *reinterpret_cast<const bf16x8_bits*>(p.residual + (int64_t)(mbase + rd * 32 + row) * p.ldr + nbase + scol(c8 * 8));
+        for (int st = 0; st < STEPS; ++st) {
+          const int idx = st * 64 + elane, row = idx / OCT, c8 = idx % OCT;
+          r8[st] = ld_bf<8>(p.residual + (int64_t)(mbase + rd * 32 + row) * p.ldr + nbase + scol(c8 * 8));
         }
       }
-      to_slab(rd_tag);
-      f32x4 lo[GRP], hi[GRP];
+      acc_to_slab<2, rd>(slab, elane, acc);
+      float x[STEPS][8];
 #pragma unroll
-      for (int s2 = 0; s2 < GRP; ++s2) {
-        const int idx = s2 * 64 + lane, row = idx / OCT, c8 = idx % OCT;
-        lo[s2] = *reinterpret_cast<const f32x4*>(slab + row * LDSW + c8 * 8);
-        hi[s2] = *reinterpret_cast<const f32x4*>(slab + row * LDSW + c8 * 8 + 4);
+      for (int st = 0; st < STEPS; ++st) {
+        const int idx = st * 64 + elane, row = idx / OCT, c8 = idx % OCT;
+        ld_slab<8>(slab + row * LDSW + c8 * 8, x[st]);
       }
 #pragma unroll
-      for (int s2 = 0; s2 < GRP; ++s2) {
-        const int idx = s2 * 64 + lane, row = idx / OCT, c8 = idx % OCT;
+      for (int st = 0; st < STEPS; ++st) {
+        const int idx = st * 64 + elane, row = idx / OCT, c8 = idx % OCT;
         const int m = mbase + rd * 32 + row, n = nbase + scol(c8 * 8);
-        float x[8];
-        float ra = p.alpha;
-        if constexpr (WNW == 4) { if (rowscale) ra *= s_rstd[rd * 32 + row]; }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { x[e] = lo[s2][e] * ra; x[4 + e] = hi[s2][e] * ra; }
-        if (p.bias) {
-          const bf16x8_bits b8 = *reinterpret_cast<const bf16x8_bits*>(p.bias + n);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) x[e] = x[e] + bf2f((bf16_bits)b8[e]);
+        epi_forward<8, false, false, true>(p, m, n, x[st], row_factor(rd * 32 + row), r8[st]);
+        if constexpr (WNW == 4 && !RMAP) {   // RMSNorm fold, producer side: this wave's slab row IS one 64-column group
+          if (p.rowsq_out) epi_rowsq<8>(p, m, n, x[st], c8 == 0);
         }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) x[e] = bfround(x[e]);
-        if (p.residual) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) x[e] = bfround(x[e] + bf2f((bf16_bits)r8[s2][e]));
-        }
-        bf16x8_bits o;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = (short)f2bf(x[e]);
-        if constexpr (WNW == 4 && !RMAP) {
-          if (p.rowsq_out) {   // RMSNorm fold, producer side: this wave's slab row IS one 64-column group: 8 lanes x 8 stored (bf16-rounded) values
-            float sq = 0.f;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { const float f = bf2f((bf16_bits)o[e]); sq += f * f; }
-            sq += __shfl_xor(sq, 1, 64); sq += __shfl_xor(sq, 2, 64); sq += __shfl_xor(sq, 4, 64);
-            if (c8 == 0) p.rowsq_out[(int64_t)m * (p.N >> 6) + (nbase >> 6)] = sq;
-          }
-        }
-        *reinterpret_cast<bf16x8_bits*>(p.C + (int64_t)m * p.ldc + n) = o;
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     });
@@ -1324,30 +1223,8 @@ __global__ __launch_bounds__(256) void gemm_nt_w4_kernel(const GemmParams p) {
 #endif
     return;
   }
-  // general path (edge tiles, activations, pre-activation save, LayerScale, FiLM, backward epilogues): one rolled loop per round
-  static_for<MT / 2>([&](auto rd_tag) {
-    constexpr int rd = decltype(rd_tag)::value;
-    to_slab(rd_tag);
-#pragma unroll 1
-    for (int it = 0; it < WTN / 8; ++it) {
-      const int idx = it * 64 + lane, row = idx / (WTN / 4), c4 = idx % (WTN / 4);
-      f32x4 v = *reinterpret_cast<const f32x4*>(slab + row * LDSW + c4 * 4);
-      const int m = mbase + rd * 32 + row, n = nbase + scol(c4 * 4);
-      if constexpr (WNW == 4) {   // (one slab row = one 64-column group, read back by 16 consecutive lanes; N % 64 == 0 with the fold: the 16 lanes are inside or outside together)
-        if (rowscale) v *= s_rstd[rd * 32 + row];
-        f32x4 st = {0.f, 0.f, 0.f, 0.f};
-        const bool inside = m < p.M && n < p.N;
-        if (inside) st = epilogue_store(p, m, n, v);
-        if (!RMAP && p.rowsq_out) {
-          const float sq = rowsq16(st);
-          if (inside && c4 == 0) p.rowsq_out[(int64_t)m * (p.N >> 6) + (n >> 6)] = sq;
-        }
-        continue;
-      }
-      if (m < p.M && n < p.N) epilogue_store(p, m, n, v);
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  });
+  // general path (edge tiles, activations, pre-activation save, LayerScale, FiLM, backward epilogues)
+  readback_general<2, false, WNW == 4, RMAP>(p, slab, elane, mbase, nbase, rowscale ? s_rstd : nullptr, acc);
 }
 
 
@@ -1679,41 +1556,17 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_pipe_kernel(const GemmPa
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
+  int col[NT];
+#pragma unroll
+  for (int j = 0; j < NT; ++j) col[j] = wn * WTN + j * 16;
   if (p.split_k > 1) {
-#pragma unroll
-    for (int i = 0; i < MT; ++i) {
-      const int m = m0 + wm * WTM + i * 16 + (lane & 15);
-#pragma unroll
-      for (int j = 0; j < NT; ++j) {
-        const int n = n0 + wn * WTN + j * 16 + 4 * (lane >> 4);
-        if (m < p.M && n < p.N) *reinterpret_cast<f32x4*>(p.ws + ((int64_t)split * p.M + m) * p.N + n) = acc[i][j];
-      }
-    }
+    store_splitk_partial(p, split, m0 + wm * WTM, n0, col, lane, acc);
     return;
   }
-  constexpr int LDSW = WTN + 4;
   constexpr int RM = MT < 2 ? MT : 2;
-  constexpr int QUADS = WTN / 4;
-  float* wstage = reinterpret_cast<float*>(smem_raw) + wave * (RM * 16 * LDSW);
-#pragma unroll
-  for (int round = 0; round < MT / RM; ++round) {
-    __syncthreads();
-#pragma unroll
-    for (int ii = 0; ii < RM; ++ii)
-#pragma unroll
-      for (int j = 0; j < NT; ++j)
-        *reinterpret_cast<f32x4*>(wstage + (ii * 16 + (lane & 15)) * LDSW + j * 16 + 4 * (lane >> 4)) = acc[round * RM + ii][j];
-    __syncthreads();
-#pragma unroll 1
-    for (int it = 0; it < RM * 16 * QUADS / 64; ++it) {
-      const int idx = it * 64 + lane;
-      const int row = idx / QUADS, c4 = idx % QUADS;
-      const f32x4 v = *reinterpret_cast<const f32x4*>(wstage + row * LDSW + c4 * 4);
-      const int m = m0 + wm * WTM + round * RM * 16 + row;
-      const int n = n0 + wn * WTN + c4 * 4;
-      if (m < p.M && n < p.N) epilogue_store(p, m, n, v);
-    }
-  }
+  float* wstage = reinterpret_cast<float*>(smem_raw) + wave * (RM * 16 * (WTN + 4));
+  __syncthreads();   // the wave slabs alias the ring's stages
+  readback_general<RM, false, false, false>(p, wstage, lane, m0 + wm * WTM, n0 + wn * WTN, nullptr, acc);
 }
 
 __global__ __launch_bounds__(256) void gemm_splitk_reduce_kernel(const GemmParams p) {
@@ -1721,9 +1574,10 @@ __global__ __launch_bounds__(256) void gemm_splitk_reduce_kernel(const GemmParam
   for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += (int64_t)gridDim.x * blockDim.x) {
     const int m = (int)(q / (p.N / 4));
     const int n = (int)(q % (p.N / 4)) * 4;
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    for (int s = 0; s < p.split_k; ++s) v += *reinterpret_cast<const f32x4*>(p.ws + ((int64_t)s * p.M + m) * p.N + n);
-    epilogue_store(p, m, n, v);
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int s = 0; s < p.split_k; ++s) acc += *reinterpret_cast<const f32x4*>(p.ws + ((int64_t)s * p.M + m) * p.N + n);
+    float v[4] = {acc[0], acc[1], acc[2], acc[3]};
+    epi_forward<4>(p, m, n, v, p.alpha);
   }
 }
 
@@ -1740,47 +1594,36 @@ OVLA_DEV void hybrid_reduce_quads(const GemmParams& p, int rt, int q0, int qstri
   const int in_group = t_mn - gid * group_sz;
   const int m0 = (first_m + in_group % gm) * BM, n0 = (in_group / gm) * BN;
   const float* slab0 = p.ws + (int64_t)rt * p.rem_splits * (BM * BN);
+  auto slab_sum = [&](int lm, int ln, float (&v)[4]) {   // the rem_splits partial sums of 4 tile-local columns, added in slab order
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int sidx = 0; sidx < p.rem_splits; ++sidx) acc += *reinterpret_cast<const f32x4*>(slab0 + (int64_t)sidx * (BM * BN) + lm * BN + ln);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = acc[e];
+  };
   for (int q = q0; q < BM * BN / 4; q += qstride) {
     const int lm = q / (BN / 4), ln = (q % (BN / 4)) * 4;
+    const int m = m0 + lm;
+    float v[4], w[4];
     if (p.act == OVLA_ACT_SWIGLU) {   // SwiGLU pair map (4-wave configs): tile-local columns [0, 128) are gate columns tn * 128 + ln, [128, 256) their up partners
-      if (ln >= 128) continue;
-      const int F = p.N >> 1, mg = m0 + lm, ng = (in_group / gm) * 128 + ln;
-      if (mg >= p.M || ng >= F) continue;
-      f32x4 vg = {0.f, 0.f, 0.f, 0.f}, vu = {0.f, 0.f, 0.f, 0.f};
-      for (int sidx = 0; sidx < p.rem_splits; ++sidx) {
-        vg += *reinterpret_cast<const f32x4*>(slab0 + (int64_t)sidx * (BM * BN) + lm * BN + ln);
-        vu += *reinterpret_cast<const f32x4*>(slab0 + (int64_t)sidx * (BM * BN) + lm * BN + 128 + ln);
-      }
-      const float ra = p.alpha * (p.rowscale_part ? p.rowscale_r[mg] : 1.f);
-      bf16x4_bits o, og, ou;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        og[e] = (short)f2bf(vg[e] * ra); ou[e] = (short)f2bf(vu[e] * ra);
-        o[e] = (short)f2bf(bfround(silu(bf2f((bf16_bits)og[e]))) * bf2f((bf16_bits)ou[e]));
-      }
-      *reinterpret_cast<bf16x4_bits*>(p.C + (int64_t)mg * p.ldc + ng) = o;
-      if (p.Cpre) {
-        *reinterpret_cast<bf16x4_bits*>(p.Cpre + (int64_t)mg * p.N + ng) = og;
-        *reinterpret_cast<bf16x4_bits*>(p.Cpre + (int64_t)mg * p.N + F + ng) = ou;
-      }
+      const int ng = (in_group / gm) * 128 + ln;
+      if (ln >= 128 || m >= p.M || ng >= (p.N >> 1)) continue;
+      slab_sum(lm, ln, v);
+      slab_sum(lm, 128 + ln, w);
+      epi_swiglu_pair<4>(p, m, ng, v, w, p.alpha * (p.rowscale_part ? p.rowscale_r[m] : 1.f));
       continue;
     }
-    const int m = m0 + lm, n = n0 + ln;
+    const int n = n0 + ln;
     if (m >= p.M || n >= p.N) continue;
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    for (int sidx = 0; sidx < p.rem_splits; ++sidx) v += *reinterpret_cast<const f32x4*>(slab0 + (int64_t)sidx * (BM * BN) + lm * BN + ln);
-    const float rs = p.rowscale_part ? p.rowscale_r[m] : 1.f;      // RMSNorm fold, consumer side: rstd written by the GEMM kernel's prologue
+    slab_sum(lm, ln, v);
+    const float ra = p.alpha * (p.rowscale_part ? p.rowscale_r[m] : 1.f);      // RMSNorm fold, consumer side: rstd written by the GEMM kernel's prologue
     if (p.rope_cos && n < p.rope_cols) {   // BN is a multiple of 128 here (launch_cfg checks): the partner quad is in the same tile
-      f32x4 vp = {0.f, 0.f, 0.f, 0.f};
-      for (int sidx = 0; sidx < p.rem_splits; ++sidx) vp += *reinterpret_cast<const f32x4*>(slab0 + (int64_t)sidx * (BM * BN) + lm * BN + (ln ^ 64));
-      rope_store(p, m, n, v * rs, vp * rs);
+      slab_sum(lm, ln ^ 64, w);
+      rope_store(p, m, n, v, w, ra);
       continue;
     }
-    const f32x4 st = epilogue_store(p, m, n, v * rs);
-    if (p.rowsq_out) {   // producer side: 16 consecutive threads hold one row's 64-column group (rows / columns outside the matrix skipped above, whole groups at a time)
-      const float sq = rowsq16(st);
-      if (((ln >> 2) & 15) == 0) p.rowsq_out[(int64_t)m * (p.N >> 6) + (n >> 6)] = sq;
-    }
+    epi_forward<4>(p, m, n, v, ra);
+    // producer side: 16 consecutive threads hold one row's 64-column group (rows / columns outside the matrix skipped above, whole groups at a time)
+    if (p.rowsq_out) epi_rowsq<4>(p, m, n, v, ((ln >> 2) & 15) == 0);
   }
 }
 
@@ -2343,7 +2186,7 @@ bool fixed_ok(const TileCfg& c, int N, int K, int K2, int k2_group_n, int flags,
   if (splits < 1 || splits > 8 || (splits > 1 && splits * 4 > T1)) return false;   // splits keep >= 4 K tiles per part
   const bool rope = flags & OVLA_EPI_ROPE, rowscale = flags & OVLA_EPI_ROWSCALE, rowsq = flags & OVLA_EPI_ROWSQ, swiglu = flags & OVLA_EPI_SWIGLU;
   if (!group_ok(c, k2_group_n) || !k_ok(c, K) || !kext_ok(c, K2, swiglu, rope) || !fold_ok(c, rowsq, rowscale, K, rope) || (swiglu && !swiglu_ok(c, N))) return false;
-  // The 4-wave configs: no general epilogue (the launch takes a forced tile = 18 with one, through epilogue_store), and long K only -- the
+  // The 4-wave configs: no general epilogue (the launch takes a forced tile = 18 with one, through the rolled read-back), and long K only -- the
   // hand-scheduled loop is measured and tested there; a forced tile = 18 with T1 < 8 launches.
   if (c.fam == FAM_W4 && ((flags & OVLA_EPI_GENERAL) || T1 < 8)) return false;
   if (rope) {

@@ -9,7 +9,9 @@ column off, a truncating store -- each changes bits.  `reference` asserts that e
 
 Epilogue order and rounding points are those of include/ovla.h ("Epilogue order") as the kernels implement them:
 
-    z = bf16(alpha * acc + bias)            [C_pre = z]          (rowscale: z = bf16(rstd[m] * alpha * acc + bias))
+    z = bf16(alpha * acc + bias)            [C_pre = z]
+    rowscale:  C = epilogue(acc * (alpha * rstd[m])): ONE fp32 factor ra = alpha * rstd[m], formed first and multiplied into the accumulator
+               once, on every path a tile can take (z = bf16(ra * acc + bias); `fold_orders` below is that formula in fp32)
     v = bf16(act(z));  v = bf16(v * colscale[n]);  v = bf16(v + residual[m, n])
     FiLM:  [C_pre = v];  v = bf16(bf16(v * bf16(1 + gamma[m / film_rows, n])) + beta[...])
     RoPE (columns [0, rope_cols), head_dim 128, pos = m % rope_S, x = own column, y = partner column +-64, both bf16(acc)):
@@ -22,6 +24,7 @@ Epilogue order and rounding points are those of include/ovla.h ("Epilogue order"
 What cannot be exact (a transcendental, the fold's rsqrt) is checked by `assert_ulps` against the float64 value in units of the bf16 ulp of
 the reference; the bounds are derived where they are used (`ULPS`).
 """
+import functools
 import math
 from types import SimpleNamespace
 
@@ -274,6 +277,70 @@ def reference(a, b, *, a2=None, b2=None, k2_group_n=0, a_group_n=0, alpha=1.0, b
             assert float(v.abs().max()) <= 256, "rowsq_out: |out| must stay <= 256 for exact fp32 sums of squares"
         r.rowsq = chk(v.view(M, N // 64, 64).pow(2).sum(-1), "rowsq_out").float()
     return r
+
+
+# ---- the fold's single row factor ---------------------------------------------------------------------------------------------------------------
+# With the RMSNorm fold the kernel multiplies the accumulator by ONE fp32 factor alpha * rstd[m].  The accumulator of exact operands is an
+# exact fp32 integer, so given the kernel's own rstd (rowscale_r) the output is known to the bit: bf16(fp32(acc) * fp32(alpha * rstd[m])).
+# The other order, (acc * rstd[m]) * alpha, gives other bf16 bits for about one element in 10^5 of random data when alpha is no power of two:
+# too few to notice in one small launch.  `fold_alpha_problem` therefore picks the producer's row sums: for every row, the sum (among those a
+# parts row can have) under which the most elements of that row's accumulators round differently under the two orders.  The GPU's rsqrt may
+# differ from the CPU's in the last place, which moves every such element: rows take turns being picked for rstd as the CPU rounds it, one
+# fp32 ulp below and one above, so a third of the rows tells the orders apart whichever way a row's rstd falls.
+FOLD_ALPHAS = (0.3, 1.7)
+
+
+def rstd32(parts, eps):
+    """rstd as the kernel's prologue forms it in fp32: the slot sums are exact integers, then one division, one addition, rsqrt."""
+    return torch.rsqrt(parts.float().sum(-1) / float(parts.shape[1] * 64) + torch.tensor(eps, dtype=torch.float32))
+
+
+def fold_orders(acc, r32, alpha):
+    """(bf16(acc * (alpha * r[m])), bf16((acc * r[m]) * alpha)) in fp32 arithmetic: the documented formula and the order it replaced."""
+    x, r, al = acc.float(), r32.float().cpu()[:, None], torch.tensor(alpha, dtype=torch.float32)
+    return (x * (al * r)).to(BF), ((x * r) * al).to(BF)
+
+
+@functools.lru_cache(maxsize=None)
+def _fold_table(K, alpha, eps):
+    """sums [S] a parts row of integers in [1000, 2000] can have, and tells[3, S, 512]: |acc| = v rounds differently under the two orders with
+    rstd of that sum one ulp below / as the CPU rounds it / one ulp above."""
+    slots = K // 64
+    sums, vals = torch.arange(1000 * slots, 2000 * slots + 1), torch.arange(512)[None, :].expand(1000 * slots + 1, -1)
+    r = torch.rsqrt(sums.float() / float(K) + torch.tensor(eps, dtype=torch.float32))
+    tells = []
+    for rr in (torch.nextafter(r, torch.zeros(())), r, torch.nextafter(r, torch.ones(()))):
+        one, two = fold_orders(vals, rr, alpha)
+        tells.append((one != two).float())
+    return sums, torch.stack(tells)
+
+
+def fold_alpha_problem(g, M, N, K, alpha, eps):
+    """a, b (exact operands) and parts fp32 [M, K / 64] (integers in [1000, 2000]) whose row sums tell the two orders apart (see above)."""
+    a, b = operand(g, M, K), operand(g, N, K)
+    sums, tells = _fold_table(K, alpha, eps)
+    mag = accumulate(a, b)[0].abs().long().clamp_max(511)
+    hist = torch.zeros((M, 512)).scatter_add_(1, mag, torch.ones((M, N)))          # how often row m's accumulators take each magnitude
+    rows = torch.zeros(M, dtype=torch.long)
+    for v in range(3):                                                             # rows 0, 3, ..: as the CPU rounds; 1, 4, ..: one ulp above; 2, 5, ..: below
+        rows[v::3] = sums[(hist[v::3] @ tells[(v + 1) % 3].T).argmax(-1)]
+    slots = K // 64
+    parts = (rows // slots)[:, None] + (torch.arange(slots)[None, :] < (rows % slots)[:, None])
+    assert torch.equal(parts.sum(-1), rows)
+    return a, b, parts.float()
+
+
+def fold_alpha_case(tile, BM, BN, alpha):
+    """The non-power-of-two-alpha consumer case of test_rmsnorm_fold for one tile id: (a, b, parts, eps) at M = BM + 37, N = BN + 24, K = 512."""
+    eps = 1e-5
+    return (*fold_alpha_problem(rng(6500 + tile), BM + 37, BN + 24, 512, alpha, eps), eps)
+
+
+def fold_told_apart(one, two, BM, BN):
+    """How many elements of the interior tile [0, BM) x [0, BN) and of the edge tiles differ between the two outputs."""
+    d = one.cpu() != two.cpu()
+    inner = int(d[:BM, :BN].sum())
+    return inner, int(d.sum()) - inner
 
 
 # ---- embedding operands in larger allocations ------------------------------------------------------------------------------------------------

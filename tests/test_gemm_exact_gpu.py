@@ -252,7 +252,10 @@ def test_rmsnorm_fold(ops, dev, tile):
     """Producer: rowsq_out exact (K = 64 keeps |out| <= 256, so every 64-column sum of squares is an exact fp32 integer; the reference asserts
     it).  Consumer: C within 1 ulp of bf16(rstd * acc) in float64, rowscale_r within 3 fp32 roundings of float64's rstd: the slot sums are
     exact integers, the division by K and the addition of eps round once each (their error is halved by the square root) and rsqrtf is good
-    to 1 ulp = 2 units: (1 + 1) / 2 + 2 = 3 units of 2^-24, asserted as 2^-22."""
+    to 1 ulp = 2 units: (1 + 1) / 2 + 2 = 3 units of 2^-24, asserted as 2^-22.
+    Consumer with alpha no power of two: given the rowscale_r the launch wrote, C is bf16(fp32(acc) * fp32(alpha * rowscale_r[m])) to the bit
+    (one factor, one multiplication: gemm_reference.fold_orders), in the interior tile and the edge tiles alike; the inputs are chosen so that
+    (acc * rstd) * alpha gives other bits in both regions (tests/test_gemm_reference.py counts them on the CPU; re-counted here)."""
     c, fails = cfg_of(tile), Failures()
     g = R.rng(6000 + tile)
     M, N, K = c.BM + 37, c.BN + 64, 64
@@ -272,6 +275,42 @@ def test_rmsnorm_fold(ops, dev, tile):
     rel = ((rbuf.cpu().double() - ref.rstd) / ref.rstd).abs().max().item()
     _note("rowscale_r (units of 2^-24)", rel * 2 ** 24)
     fails.check(rel <= 2.0 ** -22, f"{tname(tile)} rowscale_r: relative error {rel:.3e} > 2^-22")
+    for alpha in R.FOLD_ALPHAS:
+        a, b, parts, eps = R.fold_alpha_case(tile, c.BM, c.BN, alpha)
+        rbuf = torch.full((M,), float("nan"), device=dev)
+        out = ops.gemm(a.to(dev), b.to(dev), rowscale=(parts.to(dev), eps, rbuf), alpha=alpha, tile=tile)
+        want, other = R.fold_orders(R.accumulate(a, b)[0], rbuf, alpha)
+        fails.exact(out, want, f"{tname(tile)} consumer, alpha {alpha}: bf16(acc * (alpha * rowscale_r[m]))", (c.BM, c.BN))
+        inner, edge = R.fold_told_apart(want, other, c.BM, c.BN)
+        fails.check(inner >= 1 and edge >= 1, f"{tname(tile)} alpha {alpha}: with the launch's rowscale_r the two orders differ in {inner} interior and {edge} edge elements")
+    fails.done()
+
+
+# ---- one epilogue body: the path a tile takes changes no bit ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("tile", [1, 101, 17, 117, 18, 118, 22, 122], ids=tname)
+def test_same_bits_whatever_path_the_tile_took(ops, dev, tile):
+    """Rows [0, BM), columns [0, N - 64) computed twice from the same operand rows: inside an N-column launch of whole tiles (the unrolled or
+    fused read-back of an interior tile) and as an (N - 64)-column launch (an edge tile: the rolled read-back; RoPE: refused, so the plain
+    projection and the rope kernel).  Bit-identical, with alpha no power of two wherever the epilogue takes one (RoPE requires alpha 1).
+    N = BN and K = 128; the fold consumer needs K = 512 (eight slots).  RoPE runs on N = 2 BN against 2 BN - 64 with rope_cols = BN on every
+    tile: tile 17 fuses it only when all of M, N and rope_cols are multiples of 256, and tile 1's BN - 64 would be narrower than one head."""
+    c, fails = cfg_of(tile), Failures()
+    g = R.rng(6600 + tile)
+    M, N, tl = c.BM, c.BN, (c.BM, c.BN)
+    a, b, bias, res = R.operand(g, M, 128), R.operand(g, N, 128), R.bias_like(g, N), R.bias_like(g, M, N)
+    ad, bd, biasd, resd = a.to(dev), b.to(dev), bias.to(dev), res.to(dev)
+    whole = ops.gemm(ad, bd, bias=biasd, residual=resd, alpha=0.3, tile=tile)
+    part = ops.gemm(ad, bd[:N - 64], bias=biasd[:N - 64], residual=resd[:, :N - 64], alpha=0.3, tile=tile)
+    fails.exact(part, whole[:, :N - 64], f"{tname(tile)} bias + residual, alpha 0.3: edge tile against interior tile", tl)
+    if tile % 100 in (1, 22):
+        a, b, parts = R.fold_alpha_problem(g, M, N, 512, 0.3, 1e-5)      # (row sums under which the two multiplication orders round differently)
+        outs = [ops.gemm(a.to(dev), b.to(dev)[:n], rowscale=(parts.to(dev), 1e-5, torch.empty(M, device=dev)), alpha=0.3, tile=tile) for n in (N, N - 64)]
+        fails.exact(outs[1], outs[0][:, :N - 64], f"{tname(tile)} fold consumer, alpha 0.3: edge tile against interior tile", tl)
+    S, N2 = 77, 2 * c.BN
+    cos, sin = (t.to(dev) for t in R.rope_tables(g, S + 3))
+    a, b = R.operand(g, M, 128).to(dev), R.operand(g, N2, 128).to(dev)
+    outs = [ops.gemm(a, b[:n], rope=(cos, sin, S, c.BN), tile=tile) for n in (N2, N2 - 64)]
+    fails.exact(outs[1], outs[0][:, :N2 - 64], f"{tname(tile)} rope: refused (N = {N2 - 64}) against fused (N = {N2})", tl)
     fails.done()
 
 

@@ -204,6 +204,32 @@ def test_old_check_accepts_what_the_exact_check_rejects(mut):
     assert old_close(got, ref) == (mut in OLD_CHECK_ACCEPTS), f"{mut}: old check {'accepts' if old_close(got, ref) else 'rejects'}"
 
 
+# ---- the fold's single row factor -----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("alpha", R.FOLD_ALPHAS)
+@pytest.mark.parametrize("tile,BM,BN", [(1, 128, 128), (101, 128, 128), (22, 128, 256), (122, 128, 256)])
+def test_fold_alpha_case_tells_the_two_multiplication_orders_apart(tile, BM, BN, alpha):
+    """The inputs test_rmsnorm_fold feeds its alpha != 2^k consumer case: with the CPU's fp32 rstd at least 8 elements of the interior tile and
+    8 of the edge tiles round differently under (acc * rstd) * alpha than under acc * (alpha * rstd), so assert_exact rejects the old order in
+    either region; and with rstd one ulp either side (the GPU's rsqrt) both regions still tell them apart."""
+    a, b, parts, eps = R.fold_alpha_case(tile, BM, BN, alpha)
+    assert parts.shape == (BM + 37, 8) and float(parts.min()) >= 100 and float(parts.max()) <= 3000
+    acc, r = R.accumulate(a, b)[0], R.rstd32(parts, eps)
+    want, other = R.fold_orders(acc, r, alpha)
+    inner, edge = R.fold_told_apart(want, other, BM, BN)
+    assert inner >= 8 and edge >= 8, (inner, edge)
+    for region in (want[:BM, :BN], want[BM:], want[:, BN:]):
+        assert region.float().abs().max() > 0
+    with pytest.raises(AssertionError, match="elements differ"):
+        R.assert_exact(other[:BM, :BN], want[:BM, :BN], "interior tile, the other order", tile=(BM, BN))
+    with pytest.raises(AssertionError, match="elements differ"):
+        R.assert_exact(torch.cat([other[BM:].flatten(), other[:BM, BN:].flatten()])[None], torch.cat([want[BM:].flatten(), want[:BM, BN:].flatten()])[None], "edge tiles, the other order")
+    for rr in (torch.nextafter(r, torch.zeros(())), torch.nextafter(r, torch.ones(()))):
+        inner, edge = R.fold_told_apart(*R.fold_orders(acc, rr, alpha), BM, BN)
+        assert inner >= 1 and edge >= 1, (inner, edge)
+    ref = R.reference(a, b, rowscale=(parts, eps), alpha=alpha, exact=True)          # and the float64 reference agrees within its 1 ulp
+    R.assert_ulps(want, ref.out64, R.ULPS["rowscale"], what="fold_orders against the float64 reference")
+
+
 # ---- the helpers themselves ---------------------------------------------------------------------------------------------------------------------
 def test_rbf_is_round_to_nearest_even_and_ulp_is_a_bf16_ulp():
     torch.manual_seed(0)
