@@ -237,6 +237,67 @@ typedef struct {
 } ovla_select_by_slot_args;
 int ovla_select_by_slot(const ovla_select_by_slot_args* a, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * LoRA dropout (FinetuneConfig.lora_dropout, finetune.py:119 -> LoraConfig, :862-871): peft puts an independent nn.Dropout(p) in front of the
+ * lora_A of every adapted nn.Linear, active in training mode only:  y = W x + s B_g(A_g(dropout_g(x))).  A fused q|k|v or gate|up linear
+ * therefore has one mask per fused group.  Here the mask is a pure function of (seed, call, module, row, column), evaluated in registers by
+ * whichever kernel holds the element; it is never stored.  THE MASK CONTRACT (identical in the three kernels below and in the numpy
+ * restatement tests/lora_dropout_reference.py):
+ *   generator   Philox4x32-10, multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85.
+ *   call        one generator call per 16-byte vector = 8 consecutive columns of one row: q = m * (K / 8) + (k >> 3) as a 64-bit number,
+ *               counter (q_lo, q_hi, module, call), key (seed_lo, seed_hi).  Output word w gives column 8 (k >> 3) + 2 w from its low 16 bits
+ *               and column 8 (k >> 3) + 2 w + 1 from its high 16 bits.
+ *   keep rule   keep iff u16 >= thr, thr = floor(p * 65536) with p the fp32 argument widened to double: the drop probability is exactly
+ *               thr / 65536.  0 <= p < 1, K % 8 == 0.
+ *   indexing    m, k are the logical row and column of the linear's own input matrix [M, K]; the mask does not depend on a leading dimension,
+ *               on launch geometry or on which kernel evaluates it.  `module` is a caller-chosen 32-bit id per adapted sub-linear, `call` a
+ *               32-bit counter the caller advances once per training forward.
+ *   scale       inv = 1.0f / (1.0f - p) in fp32 (IEEE division, no contraction).  A kept element is bf16_rne(float(x) * inv); a dropped
+ *               element is STORED as +0, never multiplied, so a NaN in a dropped position does not survive (ovla_lora_route's convention).
+ * All three entry points are stream-ordered and capturable, use no atomics (t and dx feed the bit-reproducible gradient chain) and launch
+ * nothing on OVLA_EINVAL.  G <= 4 groups; module[g] for g < G. */
+
+/* out[g][m, k] = dropout_g(x)[m, k]: G contiguous [M, K] bf16 buffers from ONE read of x [M, K] (row stride ldx).  Columns >= K of x are not
+ * read.  K % 8 == 0, ldx % 8 == 0, 16-byte aligned x and out[g], out[g] != x. */
+typedef struct {
+  const void* x; int64_t ldx;
+  void* out[4];
+  uint32_t module[4];
+  uint32_t seed_lo, seed_hi, call;
+  float p;
+  int32_t M, K, G;
+} ovla_lora_dropout_apply_args;
+int ovla_lora_dropout_apply(const ovla_lora_dropout_apply_args* a, void* stream);
+
+/* t[m, g r + j] = bf16(alpha * sum_k dropout_g(x)[m, k] * A[g r + j, k]) for all G groups in one launch; r == 32, fp32 accumulation, the K
+ * split over a workgroup's 4 waves is reduced through LDS in wave order (run-to-run bit-identical).  x [M, K] (ldx), A [G r, K] (lda),
+ * t [M, G r] (ldt; columns >= G r untouched).  K % 8 == 0, ldx % 8 == 0, lda % 8 == 0, ldt % 4 == 0, x and A 16-byte, t 8-byte aligned. */
+typedef struct {
+  const void* x; int64_t ldx;
+  const void* A; int64_t lda;
+  void* t; int64_t ldt;
+  uint32_t module[4];
+  uint32_t seed_lo, seed_hi, call;
+  float p, alpha;
+  int32_t M, K, G, r;
+} ovla_lora_dropout_proj_args;
+int ovla_lora_dropout_proj(const ovla_lora_dropout_proj_args* a, void* stream);
+
+/* In place on dx [M, K] (ld; columns >= K untouched):
+ *   dx[m, k] = bf16(float(dx[m, k]) + sum_g (keep_g(m, k) ? inv * acc_g[m, k] : 0)),  acc_g[m, k] = sum_j dt[m, g r + j] * AT[k, g r + j] in fp32,
+ * the sum over g in group order, one rounding.  dt [M, G r] (ld_dt), AT [K, G r] (ld_at) = A^T.  r % 8 == 0, r <= 128 (fragments are
+ * zero-padded to the MFMA's K in registers), K % 8 == 0, every ld % 8 == 0, 16-byte aligned bases. */
+typedef struct {
+  void* dx; int64_t ld;
+  const void* dt; int64_t ld_dt;
+  const void* AT; int64_t ld_at;
+  uint32_t module[4];
+  uint32_t seed_lo, seed_hi, call;
+  float p;
+  int32_t M, K, G, r;
+} ovla_lora_dropout_backproj_args;
+int ovla_lora_dropout_backproj(const ovla_lora_dropout_backproj_args* a, void* stream);
+
 /* column sums  out[n] (+)= sum_m X[m,n]   (bias gradients).  out fp32, atomic accumulate. */
 typedef struct { const void* X; int64_t ldx; float* out; int32_t M, N; } ovla_colsum_args;
 int ovla_colsum_bf16(const ovla_colsum_args* a, void* stream);

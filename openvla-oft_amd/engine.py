@@ -65,6 +65,9 @@ _FUSE_SWIGLU_FWD = os.environ.get("OVLA_FUSE_SWIGLU_FWD", "0") == "1"
 # three-kernel path -- reading dy once saves 0.4 GB per layer, but a 2-D (rows x 256-column) decomposition pays it back as fp32 partial-dt slabs
 # (+25 % of dy's bytes, written and read) and dB atomics (+21 %, at a quarter of the streaming rate); left OFF.
 _LORA_BWD_FUSED = os.environ.get("OVLA_LORA_BWD", "0") == "1"
+# OVLA_LORA_DROPOUT_FUSED=0: with lora_dropout > 0 the training forward materialises dropout_g(x) per fused group (ovla_lora_dropout_apply) and
+# projects each with an ordinary GEMM, instead of masking the fragments in registers (ovla_lora_dropout_proj).  Same masks; A/B switch.
+_LORA_DROPOUT_FUSED = os.environ.get("OVLA_LORA_DROPOUT_FUSED", "1") != "0"
 
 
 # ======================================================================================================================
@@ -185,6 +188,32 @@ class SlotRoute:
         self.host_slots: Optional[List[int]] = None   # the same values on the host where the caller has them: the library validates them
 
 
+class DropoutState:
+    """The engine-level state of peft's lora_dropout (finetune.py:119 -> LoraConfig): probability, 64-bit seed, the 32-bit `call` counter that
+    advances once per training forward (every micro-batch of a gradient accumulation draws fresh masks) and whether the running forward drops.
+    Every adapted LoraLinear holds the engine's one instance; the masks themselves are never stored (ovla.h "LoRA dropout")."""
+
+    def __init__(self, p: float = 0.0, seed: int = 0):
+        p = float(p)
+        if not 0.0 <= p < 1.0:
+            raise ValueError(f"lora_dropout = {p} is outside [0, 1)")
+        if p > 0.0 and _FUSE != "none":
+            raise ValueError("lora_dropout > 0 cannot be combined with OVLA_FUSE_DACT: the activation derivative cannot ride in the epilogue of a "
+                             "data-gradient GEMM whose sum is completed by a later kernel")
+        self.p, self.seed, self.call, self.active = p, int(seed) & 0xFFFFFFFFFFFFFFFF, 0, False
+
+    def begin_forward(self, train: bool):
+        """Called once per forward: training forwards advance `call` and drop, everything else never drops."""
+        self.active = bool(train) and self.p > 0.0
+        if self.active:
+            self.call = (self.call + 1) & 0xFFFFFFFF
+
+    def end_forward(self):
+        """`active` is true only WHILE a training forward runs: whatever calls a linear outside one (a graph's prefix capture through
+        patches_dev, a component forward) does not drop.  The backward needs no flag: it takes `call` from what the forward saved."""
+        self.active = False
+
+
 class SlotProjectors:
     """Every registered policy's proprio projector on all B observations, then each observation's own row (ovla_select_by_slot): n small
     forwards instead of data-dependent grouping, which a captured graph could not hold.  Quacks like MlpProjector.fwd for patches_dev."""
@@ -201,12 +230,22 @@ class SlotProjectors:
         return out, None
 
 
+def launch_tn(probs):
+    """The weight-gradient TN problems of one linear, or of a tn_queue, in launches of at most ops.TN_MAX_GROUP (more than one launch only
+    with dropout's per-group dA problems on a fused linear: G dB + G dA instead of G + 1)."""
+    for i in range(0, len(probs), ops.TN_MAX_GROUP):
+        ops.gemm_tn_grouped(probs[i:i + ops.TN_MAX_GROUP])
+
+
 class LoraLinear:
     """Frozen nn.Linear (+ optional bias) with peft-style LoRA adapters; `groups` fused sub-linears share the input.
 
     forward:  t_s = s * x A^T ;  y = x W^T (+ bias) + t_s B^T                     (one K-extended GEMM)
     backward: dt  = s * dy_g B_g   (per group);  dx = dy W + dt A                  (one K-extended GEMM on W^T / A^T)
               dB_g += dy_g^T t_s,g ;  dA += dt^T x                                 (TN GEMMs, fp32 accumulate)
+    with lora_dropout active (training forwards of an engine built with lora_dropout > 0; masks from ovla.h "LoRA dropout"):
+    forward:  t_s,g = s * dropout_g(x) A_g^T  (ovla_lora_dropout_proj: masks in registers), the K-extended GEMM as above
+    backward: dx = dy W, then dx += sum_g mask_g * inv * (dt_g A_g) in place (ovla_lora_dropout_backproj);  dA_g += dt_g^T dropout_g(x)
     """
 
     def __init__(self, store: Optional[ParamStore], name: str, W: torch.Tensor, bias: Optional[torch.Tensor], lora_A: Optional[torch.Tensor],
@@ -224,6 +263,8 @@ class LoraLinear:
             self.B = store.add(name + ".lora_B", lora_B.to(BF16))
             self.AT = None   # [in, G*r]   derived
             self.BT = None   # list of [r, group_n] derived
+        self.dropout: Optional[DropoutState] = None   # the engine's DropoutState when lora_dropout > 0 (VLAEngine.__init__)
+        self.module_ids: List[int] = []               # one mask stream per fused group (peft: one nn.Dropout per adapted nn.Linear)
 
     def derived_pairs(self):
         """(src, dst) transposes that re-derive A^T [in, G*r] and the stacked B_g^T [G*r, group_n] from the trainable factors."""
@@ -315,6 +356,21 @@ class LoraLinear:
                          a2=t_s, b2=self.B_slots, k2_group_n=self.group_n if self.groups > 1 else 0, rope=rope)
             return y, None
         if self.has_lora and not getattr(self, "merged", False):
+            do = self.dropout
+            if do is not None and do.active:
+                # t_s = s * dropout_g(x) . A_g^T with the masks evaluated in registers; the K-extended main GEMM below is the usual one
+                key = dict(modules=self.module_ids, p=do.p, seed=do.seed, call=do.call)
+                if _LORA_DROPOUT_FUSED and self.r == 32:
+                    t_s = ops.lora_dropout_proj(x, self.A.data, alpha=self.scale, **key)
+                else:
+                    r = self.r
+                    xd = ops.lora_dropout_apply(x, **key)
+                    t_s = torch.empty((x.shape[0], self.groups * r), dtype=BF16, device=x.device)
+                    for g in range(self.groups):
+                        ops.gemm(xd[g], self.A.data[g * r:(g + 1) * r], alpha=self.scale, out=t_s[:, g * r:(g + 1) * r])
+                y = ops.gemm(x, self.W, out=out, bias=self.bias, act=act, residual=residual, colscale=colscale, c_pre=c_pre, film=film,
+                             a2=t_s, b2=self.B.data, k2_group_n=self.group_n if self.groups > 1 else 0, rope=rope)
+                return y, (x, t_s, do.call)
             t_s = ops.gemm(x, self.A.data, alpha=self.scale)
             y = ops.gemm(x, self.W, out=out, bias=self.bias, act=act, residual=residual, colscale=colscale, c_pre=c_pre, film=film,
                          a2=t_s, b2=self.B.data, k2_group_n=self.group_n if self.groups > 1 else 0, rope=rope)
@@ -330,7 +386,8 @@ class LoraLinear:
         list (ops.gemm_tn_grouped) BEFORE anything overwrites `dy` -- two neighbouring linears' four small problems share one launch."""
         if getattr(self, "n_slots", 0):
             raise RuntimeError(f"{self.name}: this linear carries adapter slots (multi-policy serving); that path is inference-only")
-        x, t_s = saved
+        x, t_s = saved[:2]
+        drop_call = saved[2] if len(saved) > 2 else None   # the forward dropped: its masks are regenerated from (seed, call, module)
         dx = None
         if getattr(self, "merged", False):
             raise RuntimeError(f"{self.name}: LoRA adapters were merged into the base weight; this engine is inference-only")
@@ -346,11 +403,23 @@ class LoraLinear:
                 # dB_g += dy_g^T t_g ; dA += dt^T x : one grouped launch
                 probs = [(dy[:, g * gn:(g + 1) * gn], t_s[:, g * r:(g + 1) * r], self.B.grad[g * gn:(g + 1) * gn]) for g in range(G)]
                 probs.append((dt, x, self.A.grad))
+            if drop_call is not None:
+                # dA_g += dt_g^T dropout_g(x): the dropped input is regenerated into a buffer of its own (not a fixed workspace: tn_queue may launch
+                # the problem later, and the two towers run on two streams)
+                assert dact is None, "lora_dropout: a fused activation derivative needs the complete dx"
+                do = self.dropout
+                key = dict(modules=self.module_ids, p=do.p, seed=do.seed, call=drop_call)
+                xd = ops.lora_dropout_apply(x, **key)
+                probs.pop()
+                probs.extend((dt[:, g * r:(g + 1) * r], xd[g], self.A.grad[g * r:(g + 1) * r]) for g in range(G))
             if tn_queue is not None:
                 tn_queue.extend(probs)
             else:
-                ops.gemm_tn_grouped(probs)
-            if need_dx:
+                launch_tn(probs)
+            if need_dx and drop_call is not None:
+                dx = ops.gemm(dy, self.WT)
+                ops.lora_dropout_backproj(dx, dt, self.AT, **key)
+            elif need_dx:
                 dx = ops.gemm(dy, self.WT, a2=dt, b2=self.AT, dact=dact)
         elif need_dx:
             dx = ops.gemm(dy, self.WT, dact=dact)
@@ -552,7 +621,7 @@ class VitTower:
                 dz = ops.act_bwd(z, blk["fc2"].bwd(d, s_fc2, tn_queue=tnq), self.act)
             dh2 = blk["fc1"].bwd(dz, s_fc1, tn_queue=tnq)
             if tnq:
-                ops.gemm_tn_grouped(tnq)
+                launch_tn(tnq)
             ops.norm_bwd(x2, dh2, blk["ln2_w"], mean2, rstd2, rms=False, dx=dx, dx_accum=True)       # dx now = d x2
             if fsv is not None:   # through the FiLM modulation: dgamma, dbeta, dx <- dx * (1 + gamma)
                 gamma, s_sc, s_sh, xpre, frows = fsv
@@ -572,7 +641,7 @@ class VitTower:
                          dv=dqkv[:, 2 * D:])
             dh1 = blk["qkv"].bwd(dqkv, s_qkv, need_dx=not first_block, tn_queue=tnq)   # block 0 still needs its LoRA gradients, not d x
             if tnq:
-                ops.gemm_tn_grouped(tnq)
+                launch_tn(tnq)
             if not first_block:
                 ops.norm_bwd(x, dh1, blk["ln1_w"], mean1, rstd1, rms=False, dx=dx, dx_accum=True)    # dx now = d x
         return None  # patch embedding / position embedding are frozen and the pixels need no gradient
@@ -944,9 +1013,10 @@ class VLAEngine:
     (see weights.py for the state-dict naming)."""
 
     def __init__(self, cfg: VLAConfig, get, device, *, lora: bool = True, use_proprio: bool = True, head: str = "l1", use_film: bool = False,
-                 has=None):
+                 has=None, lora_dropout: float = 0.0, dropout_seed: int = 0):
         if head not in ("l1", "diffusion", "none"):
             raise ValueError(head)
+        self.dropout = DropoutState(lora_dropout, dropout_seed)
         ops.check_device(device.index or 0)
         self.cfg, self.device, self.lora = cfg, device, lora
         self.route, self.n_slots = SlotRoute(), 0   # multi-policy serving (set_adapter_slots / routing)
@@ -980,6 +1050,11 @@ class VLAEngine:
             self.head = build_component(ActionHead, device, get, "action_head.noise_predictor.mlp_resnet." if head == "diffusion" else "action_head.model.",
                                         cfg=cfg)
         self.refresh_derived()
+        ids = self.dropout_module_ids()
+        for lin in self.all_linears():
+            if isinstance(lin, LoraLinear) and lin.has_lora:
+                lin.module_ids = [ids[rn] for rn in lin.ref_names]
+                lin.dropout = self.dropout if self.dropout.p > 0.0 else None
         if _FOLD_RMSNORM and not any(l.has_lora for l in self.llm.linears()):
             self.llm.fold_norms()       # an adapter-free decoder (merged checkpoint): inference-only model, fold the RMSNorms (LlamaStack.fold_norms)
 
@@ -1009,6 +1084,12 @@ class VLAEngine:
             if m is not None:
                 yield from m.linears()
         yield from self.llm.linears()
+
+    def dropout_module_ids(self) -> Dict[str, int]:
+        """The stable 32-bit `module` id of every adapted reference sub-linear (its word of the mask's Philox counter): the position in
+        all_linears() x ref_names, so the fused q|k|v and gate|up linears carry one id -- one independent mask -- per fused group."""
+        names = [rn for lin in self.all_linears() if isinstance(lin, LoraLinear) and lin.has_lora for rn in lin.ref_names]
+        return {rn: i for i, rn in enumerate(names)}
 
     def merge_lora(self):
         """Folds every LoRA adapter of the VLM into its base weight (what the reference does before deployment:
@@ -1179,9 +1260,12 @@ class VLAEngine:
                 tag = "bf16" if dt == BF16 else "f32"
                 out[f"store{i}.{tag}.exp_avg"] = st.exp_avg[dt]
                 out[f"store{i}.{tag}.exp_avg_sq"] = st.exp_avg_sq[dt]
+        out["lora_dropout.call"] = torch.tensor([self.dropout.call], dtype=torch.int64)   # the mask stream's position: a resumed run draws the masks the uninterrupted one would
         return out
 
     def load_optimizer_state_dict(self, sd: Dict[str, torch.Tensor]):
+        if "lora_dropout.call" in sd:
+            self.dropout.call = int(sd["lora_dropout.call"].item()) & 0xFFFFFFFF
         for i, st in enumerate(self.stores):
             if not st.exp_avg:
                 st.init_optimizer()
@@ -1334,6 +1418,8 @@ class VLAEngine:
         cfg, dev = self.cfg, self.device
         B = ids.shape[0]
         psaved = None
+        if not train:
+            self.dropout.end_forward()   # (entered on its own by a graph's prefix capture: never drops, whatever ran before)
         if self.use_film and film_avg is None:
             film_avg = self.language_average(ids, lab)
         patches, vsaved = self.vision_fwd(pixel_values.to(dev, BF16).contiguous(), train, film_avg)
@@ -1352,6 +1438,15 @@ class VLAEngine:
                     proprio_projector=None, noisy_action_projector=None, cached_patches=None, film_avg=None, sel=None):
         """Device-only part of forward(): ids / lab int64 [B, L] and text_lens int32 [B] already on the device; launches
         kernels and allocates, never synchronises or reads host memory -- the part a hipGraph can capture (ChunkGraph)."""
+        self.dropout.begin_forward(train)
+        try:
+            return self._forward_dev(ids, lab, text_lens, pixel_values, proprio, noisy_actions, timestep_emb, train, proprio_projector,
+                                     noisy_action_projector, cached_patches, film_avg, sel)
+        finally:
+            self.dropout.end_forward()
+
+    def _forward_dev(self, ids, lab, text_lens, pixel_values, proprio, noisy_actions, timestep_emb, train, proprio_projector,
+                     noisy_action_projector, cached_patches, film_avg, sel):
         cfg = self.cfg
         dev = self.device
         B, L = ids.shape

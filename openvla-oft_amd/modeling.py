@@ -364,7 +364,7 @@ class OpenVLAForActionPrediction(_StoreModule):
     """prismatic/extern/hf/modeling_prismatic.py:720-1087 over the HIP engine."""
 
     def __init__(self, cfg: VLAConfig, state_dict: Dict[str, torch.Tensor], *, device=None, lora: Optional[bool] = None,
-                 norm_stats: Optional[dict] = None, use_film: Optional[bool] = None):
+                 norm_stats: Optional[dict] = None, use_film: Optional[bool] = None, lora_dropout: float = 0.0, dropout_seed: int = 0):
         self.cfg = cfg
         self.device = _device(device)
         get, has = make_getter(state_dict, self.device)
@@ -372,7 +372,8 @@ class OpenVLAForActionPrediction(_StoreModule):
             lora = "auto" if any(k.endswith(".lora_A.weight") for k in state_dict) else False
         if use_film is None:
             use_film = any(".scale.weight" in k for k in state_dict)
-        self.engine = VLAEngine(cfg, get, self.device, lora=lora, use_proprio=False, head="none", has=has, use_film=use_film)
+        self.engine = VLAEngine(cfg, get, self.device, lora=lora, use_proprio=False, head="none", has=has, use_film=use_film,
+                                lora_dropout=lora_dropout, dropout_seed=dropout_seed)   # (training forwards only: predict_action* never drops)
         self.store = self.engine.store
         self.llm_dim = cfg.llm_dim
         self.norm_stats = norm_stats or {}

@@ -243,6 +243,9 @@ def _tn_workspace(g, group_size, device):
     return ws
 
 
+TN_MAX_GROUP = 4   # OVLA_TN_MAX_GROUP (ovla.h)
+
+
 def gemm_tn_grouped(problems):
     """problems: list of (x, y, out_fp32) with out accumulated (+=).  One launch for up to 4 TN GEMMs."""
     import ctypes
@@ -770,6 +773,76 @@ def select_by_slot(src, obs_slot, *, rows_per_obs, rows=None, out=None, host_slo
     g.n, g.rows, g.dim, g.rows_per_obs, g.n_obs, g.elem_bytes = n, rows, dim, rows_per_obs, obs_slot.numel(), src.element_size()
     _lib.call("ovla_select_by_slot", g, _stream())
     return out
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+def _dropout_key(g, modules, p, seed, call):
+    """The mask-contract fields shared by the three LoRA-dropout argument structs (ovla.h "LoRA dropout")."""
+    if not 1 <= len(modules) <= 4:
+        raise ValueError(f"lora dropout: {len(modules)} groups (1 .. 4 supported)")
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"lora dropout: p = {p} is outside [0, 1)")
+    g.module = (ctypes.c_uint32 * 4)(*[int(v) & 0xFFFFFFFF for v in modules])
+    g.seed_lo, g.seed_hi, g.call, g.p, g.G = int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF, int(call) & 0xFFFFFFFF, p, len(modules)
+
+
+def lora_dropout_apply(x, *, modules, p, seed, call, out=None):
+    """xd_g = dropout_g(x) for every module id in `modules` (ovla.h: ovla_lora_dropout_apply): x bf16 [M, K] (row stride free) is read once,
+    returns bf16 [G, M, K] contiguous."""
+    _chk(x, name="x")
+    assert x.dim() == 2 and x.stride(1) == 1
+    M, K = x.shape
+    if out is None:
+        out = torch.empty((len(modules), M, K), dtype=BF16, device=x.device)
+    assert out.shape == (len(modules), M, K) and out.dtype == BF16 and out.is_contiguous()
+    g = STRUCTS["ovla_lora_dropout_apply_args"]()
+    _dropout_key(g, modules, p, seed, call)
+    g.x, g.ldx, g.M, g.K = x.data_ptr(), x.stride(0), M, K
+    g.out = (ctypes.c_void_p * 4)(*[out[i].data_ptr() for i in range(len(modules))])
+    e0 = _prof_begin()
+    _lib.call("ovla_lora_dropout_apply", g, _stream())
+    _prof_end(e0, "lora_dropout", 0.0)
+    return out
+
+
+def lora_dropout_proj(x, A, *, alpha, modules, p, seed, call, out=None):
+    """t[:, g r : (g + 1) r] = bf16(alpha * dropout_g(x) . A_g^T) for all groups in one launch (ovla.h: ovla_lora_dropout_proj): x bf16 [M, K],
+    A bf16 [G * 32, K] -> t bf16 [M, G * 32].  The dropped activations exist in registers only."""
+    _chk(x, name="x"); _chk(A, name="A")
+    assert x.dim() == 2 and A.dim() == 2 and x.stride(1) == 1 and A.stride(1) == 1 and x.shape[1] == A.shape[1]
+    M, K = x.shape
+    G = len(modules)
+    assert A.shape[0] % G == 0
+    r = A.shape[0] // G
+    if out is None:
+        out = torch.empty((M, G * r), dtype=BF16, device=x.device)
+    assert out.shape == (M, G * r) and out.dtype == BF16 and out.stride(1) == 1
+    g = STRUCTS["ovla_lora_dropout_proj_args"]()
+    _dropout_key(g, modules, p, seed, call)
+    g.x, g.ldx, g.A, g.lda, g.t, g.ldt = x.data_ptr(), x.stride(0), A.data_ptr(), A.stride(0), out.data_ptr(), out.stride(0)
+    g.alpha, g.M, g.K, g.r = alpha, M, K, r
+    e0 = _prof_begin()
+    _lib.call("ovla_lora_dropout_proj", g, _stream())
+    _prof_end(e0, "lora_dropout", 2.0 * M * G * r * K)
+    return out
+
+
+def lora_dropout_backproj(dx, dt, AT, *, modules, p, seed, call):
+    """dx += sum_g keep_g ? inv * (dt_g . A_g) : 0, in place and rounded once (ovla.h: ovla_lora_dropout_backproj): dx bf16 [M, K] (row
+    stride free), dt bf16 [M, G r], AT bf16 [K, G r]."""
+    _chk(dx, name="dx"); _chk(dt, name="dt"); _chk(AT, name="AT")
+    assert dx.dim() == 2 and dt.dim() == 2 and AT.dim() == 2 and dx.stride(1) == 1 and dt.stride(1) == 1 and AT.stride(1) == 1
+    M, K = dx.shape
+    G = len(modules)
+    assert dt.shape[0] == M and AT.shape[0] == K and dt.shape[1] == AT.shape[1] and dt.shape[1] % G == 0
+    g = STRUCTS["ovla_lora_dropout_backproj_args"]()
+    _dropout_key(g, modules, p, seed, call)
+    g.dx, g.ld, g.dt, g.ld_dt, g.AT, g.ld_at = dx.data_ptr(), dx.stride(0), dt.data_ptr(), dt.stride(0), AT.data_ptr(), AT.stride(0)
+    g.M, g.K, g.r = M, K, dt.shape[1] // G
+    e0 = _prof_begin()
+    _lib.call("ovla_lora_dropout_backproj", g, _stream())
+    _prof_end(e0, "lora_dropout", 2.0 * M * dt.shape[1] * K)
+    return dx
 
 
 # ----------------------------------------------------------------------------------------------------------------------

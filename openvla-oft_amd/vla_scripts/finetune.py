@@ -97,6 +97,12 @@ def get_run_id(cfg) -> str:
     return run_id
 
 
+def dropout_seed_for_rank(rank: int) -> int:
+    """The 64-bit Philox key of the lora_dropout masks: the rank in the high word, so every data-parallel rank draws different masks
+    (each rank's nn.Dropout has its own generator state in the reference, too)."""
+    return 7 + (int(rank) << 32)
+
+
 def learning_rate_at(cfg, gradient_step_idx: int) -> float:
     """MultiStepLR(milestones=[num_steps_before_decay], gamma=0.1) + optional linear warm-up 10% -> 100%
     (finetune.py:958-962, 1094-1098).  The step index is the number of optimizer steps already taken."""
@@ -209,7 +215,8 @@ def save_training_checkpoint(run_dir: Path, log_step: int, engine: VLAEngine, da
         if dataset_statistics is not None:
             (ckpt / "dataset_statistics.json").write_text(json.dumps(dataset_statistics))
         exp = {k: v.detach().to("cpu") for k, v in engine.export_trainable("data").items()}
-        save_lora_adapter(ckpt / "lora_adapter", exp, r=engine.cfg.lora_rank, lora_alpha=engine.cfg.lora_alpha)   # peft on-disk format
+        save_lora_adapter(ckpt / "lora_adapter", exp, r=engine.cfg.lora_rank, lora_alpha=engine.cfg.lora_alpha,
+                          lora_dropout=engine.dropout.p)   # peft on-disk format
         for comp, prefix in _COMPONENT_PREFIXES.items():
             if comp == "vision_backbone":
                 continue
@@ -231,7 +238,8 @@ def save_training_checkpoint(run_dir: Path, log_step: int, engine: VLAEngine, da
 def load_training_checkpoint(ckpt: Path, log_step: Optional[int], engine: VLAEngine, load_optimizer: bool = True) -> dict:
     """Resume (finetune.py:134-156 `load_checkpoint(module_name, path, step)` per component + the lora adapter the reference
     re-attaches through its merged checkpoint): reads `{component}--{step}_checkpoint.pt` (`latest` when step is None), the
-    peft adapter directory and, if present, the optimizer state.  Only `weights_only=True` / safetensors loaders are used."""
+    peft adapter directory and, if present, the optimizer state, which also carries the lora_dropout mask stream's `call` counter
+    (`dropout_call` in the result: False when the checkpoint has none).  Only `weights_only=True` / safetensors loaders are used."""
     ckpt = Path(ckpt)
     suffix = "latest_checkpoint" if log_step is None else f"{log_step}_checkpoint"
     sd: Dict[str, torch.Tensor] = {}
@@ -250,13 +258,14 @@ def load_training_checkpoint(ckpt: Path, log_step: Optional[int], engine: VLAEng
                 sd.update({prefix + k: v for k, v in part.items()})
     missing = engine.load_trainable(sd, strict=False)
     opt = ckpt / f"optimizer_state--{suffix}.safetensors"
-    loaded_opt = False
+    loaded_opt = has_call = False
     if load_optimizer and opt.is_file():
         from safetensors.torch import load_file
 
-        engine.load_optimizer_state_dict(load_file(str(opt)))
-        loaded_opt = True
-    return {"missing": missing, "optimizer": loaded_opt, "tensors": len(sd)}
+        osd = load_file(str(opt))
+        engine.load_optimizer_state_dict(osd)
+        loaded_opt, has_call = True, "lora_dropout.call" in osd
+    return {"missing": missing, "optimizer": loaded_opt, "tensors": len(sd), "dropout_call": has_call}
 
 
 def run_validation(engine: VLAEngine, cfg: FinetuneConfig, val_batches: Iterable[dict], log_step: int, log, *, discrete: bool, make_diffusion=None,
@@ -315,7 +324,7 @@ def finetune(cfg: FinetuneConfig, *, model_config: VLAConfig = OPENVLA_7B, state
         state_dict = random_state_dict(model_config, dev, seed=0, lm_head=discrete, film=cfg.use_film, diffusion=cfg.use_diffusion)
     get, has = make_getter(state_dict, dev)
     engine = VLAEngine(model_config, get, dev, lora=True, use_proprio=cfg.use_proprio, head="none" if discrete else ("diffusion" if cfg.use_diffusion else "l1"),
-                       use_film=cfg.use_film, has=has)
+                       use_film=cfg.use_film, has=has, lora_dropout=cfg.lora_dropout, dropout_seed=dropout_seed_for_rank(rank))
     if cfg.use_diffusion:   # DiffusionActionHead.sample_noisy_actions (action_heads.py:167-197), host side
         from ..diffusion import DDIMScheduler, SinusoidalPositionalEncoding
 
@@ -325,6 +334,9 @@ def finetune(cfg: FinetuneConfig, *, model_config: VLAConfig = OPENVLA_7B, state
     if cfg.resume:   # finetune.py:193-209: the trainable components come from the checkpoint directory `vla_path` at `resume_step`
         assert cfg.resume_step is not None, "resume=True needs resume_step"
         info = load_training_checkpoint(Path(cfg.vla_path), cfg.resume_step, engine)
+        if not info["dropout_call"]:   # a checkpoint from before the counter was saved was trained with dropout ignored: there is no mask stream to
+            # continue, only one to start; start it at a position that depends on the step, so two resumes at different steps do not share masks
+            engine.dropout.call = (cfg.resume_step * cfg.grad_accumulation_steps) & 0xFFFFFFFF
         log(f"[finetune] resumed step {cfg.resume_step} from {cfg.vla_path}: {info['tensors']} tensors, optimizer state: {info['optimizer']}, "
             f"{len(info['missing'])} trainable tensors kept at their initial values")
     reducer = GradReducer(engine.stores, world) if world > 1 else None

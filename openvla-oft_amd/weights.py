@@ -116,8 +116,10 @@ def random_state_dict(cfg: VLAConfig, device, seed: int = 0, *, lora: bool = Tru
 PEFT_PREFIX = "base_model.model."
 
 
-def save_lora_adapter(adapter_dir, tensors: Dict[str, torch.Tensor], *, r: int, lora_alpha: int, base_model_name_or_path: str = "openvla/openvla-7b"):
-    """`tensors`: {<module path>.lora_A.weight | .lora_B.weight: tensor} (engine.export_trainable naming)."""
+def save_lora_adapter(adapter_dir, tensors: Dict[str, torch.Tensor], *, r: int, lora_alpha: int, base_model_name_or_path: str = "openvla/openvla-7b",
+                      lora_dropout: float = 0.0):
+    """`tensors`: {<module path>.lora_A.weight | .lora_B.weight: tensor} (engine.export_trainable naming).  `lora_dropout`: the probability the
+    adapter was trained with (it only matters to a run that trains on; load_lora_adapter accepts any value)."""
     import json
     from pathlib import Path
 
@@ -128,7 +130,7 @@ def save_lora_adapter(adapter_dir, tensors: Dict[str, torch.Tensor], *, r: int, 
     lora = {PEFT_PREFIX + k: v.detach().to("cpu").contiguous() for k, v in tensors.items() if ".lora_A." in k or ".lora_B." in k}
     save_file(lora, str(d / "adapter_model.safetensors"))
     cfg = {"peft_type": "LORA", "task_type": None, "base_model_name_or_path": base_model_name_or_path, "r": r, "lora_alpha": lora_alpha,
-           "lora_dropout": 0.0, "bias": "none", "target_modules": "all-linear", "init_lora_weights": "gaussian", "fan_in_fan_out": False,
+           "lora_dropout": float(lora_dropout), "bias": "none", "target_modules": "all-linear", "init_lora_weights": "gaussian", "fan_in_fan_out": False,
            "inference_mode": True, "modules_to_save": None, "use_rslora": False, "use_dora": False}
     (d / "adapter_config.json").write_text(json.dumps(cfg, indent=2, sort_keys=True))
     return d
