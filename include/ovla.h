@@ -650,6 +650,22 @@ int ovla_transpose_bf16(const ovla_transpose_args* a, void* stream);
  * entries' 64x64 tile counts, total_tiles = tile_start[n]. */
 int ovla_transpose_batched(const ovla_transpose_args* table, const int32_t* tile_start, int32_t n, int32_t total_tiles, void* stream);
 
+/* Grouped, strided 2-D device-to-device copy driven by a device table: one launch moves every tensor of one policy (its LoRA factors into
+ * the adapter-slot storage of every adapted linear, its head's and proprio projector's parameter buffers) -- the policy pool's slot swap.
+ * Entry i copies `rows` rows of `row_bytes` bytes from src + k src_ld_bytes to dst + k dst_ld_bytes.  Everything is in BYTES and a multiple
+ * of 2, pointers are 2-byte aligned; rows == 0 is legal and skipped; with rows > 1 both strides are at least row_bytes.  An entry whose
+ * pointers, strides and row_bytes are all multiples of 16 moves 16 bytes per lane (consecutive lanes take consecutive 16-byte pieces of a
+ * row, then of the next row: a wave instruction covers whole 64-byte segments of 16 consecutive rows), any other entry 2 bytes per lane;
+ * both paths are one kernel.  Exactly the destination rectangles are written; stream-ordered, no atomics, no workspace.  Source and
+ * destination rectangles of one table must not overlap each other.
+ *
+ * ovla_copy_table_plan (host only, no device work): validates n HOST entries and writes the n + 1 exclusive prefix sums of their tile counts
+ * to the HOST array tile_start (a tile is at most 16 KiB of one entry: whole rows while a row fits, otherwise 16 KiB pieces of one row).
+ * ovla_copy_table: `table` and `tile_start` are the DEVICE copies of what was planned, total_tiles = tile_start[n] (0: nothing to do). */
+typedef struct { const void* src; void* dst; int64_t src_ld_bytes, dst_ld_bytes, rows, row_bytes; } ovla_copy_entry;
+int ovla_copy_table_plan(const ovla_copy_entry* entries, int32_t n, int32_t* tile_start);
+int ovla_copy_table(const ovla_copy_entry* table, const int32_t* tile_start, int32_t n, int32_t total_tiles, void* stream);
+
 /* self-test hook used by tests/: dumps the MFMA / transposed-LDS-read / LDS-DMA lane layouts the kernels rely on.
  * out: fp32 [4, 64, 16] device;  src: bf16 [512] device holding 0..511. */
 int ovla_selftest_layouts(float* out, const void* src, void* stream);

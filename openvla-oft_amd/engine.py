@@ -17,7 +17,7 @@ from __future__ import annotations
 
 import contextlib
 import math
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Tuple
 
 import os
 
@@ -25,6 +25,7 @@ import torch
 
 from . import _lib, ops
 from .config import VLAConfig, VitConfig
+from .policy_pool import Residency
 
 BF16 = torch.bfloat16
 F32 = torch.float32
@@ -1020,6 +1021,7 @@ class VLAEngine:
         ops.check_device(device.index or 0)
         self.cfg, self.device, self.lora = cfg, device, lora
         self.route, self.n_slots = SlotRoute(), 0   # multi-policy serving (set_adapter_slots / routing)
+        self.pool: Optional[Dict[str, dict]] = None   # the policy pool (init_policy_pool): name -> its tensors in device memory
         lora = lora_predicate(lora, has)
         st = self.store = ParamStore(device)
         # registration order = forward order (the store reverses it into backward order)
@@ -1102,16 +1104,12 @@ class VLAEngine:
             self.llm.fold_norms()       # adapter-free decoder: RMSNorm + RoPE + q|k|v (and RMSNorm + gate|up) become one launch each at inference
 
     # -- adapter slots: several fine-tuned policies on one base model (inference only) ---------------------------------------------------------
-    def set_adapter_slots(self, adapters: List[Dict[str, torch.Tensor]], *, lora_alpha: Optional[List[Optional[float]]] = None):
-        """adapters[s]: policy s's LoRA tensors under the names lora_state_dict() / weights.load_lora_adapter use (`<linear>.lora_A.weight`,
-        `.lora_B.weight`, un-fused per q/k/v and gate/up).  Allocates n = len(adapters) slots on every adapted linear and fills them; an empty
-        list removes the slots.  The model must carry no merged or trainable adapters of its own; all policies must adapt the same linears with
-        one rank and one lora_alpha -- the model configuration's, whose alpha / r scales every slot's projection."""
+    def _check_adapters(self, adapters: List[Dict[str, torch.Tensor]], lora_alpha=None):
+        """What set_adapter_slots and the policy pool check before they change anything: a base model without adapters of its own, every
+        policy with the configuration's lora_alpha and rank, no stray tensors, whole fused groups, one adapted set.
+        -> (the model's LoraLinears, the names of the adapted ones; an empty set for no adapters)."""
         if getattr(self, "lora_merged", False) or any(isinstance(l, LoraLinear) and l.has_lora for l in self.vlm_linears()):
             raise ValueError("adapter slots need a base model built without merged or trainable LoRA adapters")
-        n = len(adapters)
-        if n > MAX_SLOTS:
-            raise ValueError(f"{n} policies: at most {MAX_SLOTS} adapter slots ride in one launch")
         cfg = self.cfg
         for s, a in enumerate(lora_alpha or []):
             if a is not None and float(a) != float(cfg.lora_alpha):
@@ -1135,6 +1133,20 @@ class VLAEngine:
                                          "(mixed ranks are not supported)")
         if any(p != plans[0] for p in plans):
             raise ValueError("the policies adapt different sets of linears")
+        return linears, (plans[0] if plans else frozenset())
+
+    def set_adapter_slots(self, adapters: List[Dict[str, torch.Tensor]], *, lora_alpha: Optional[List[Optional[float]]] = None):
+        """adapters[s]: policy s's LoRA tensors under the names lora_state_dict() / weights.load_lora_adapter use (`<linear>.lora_A.weight`,
+        `.lora_B.weight`, un-fused per q/k/v and gate/up).  Allocates n = len(adapters) slots on every adapted linear and fills them; an empty
+        list removes the slots.  The model must carry no merged or trainable adapters of its own; all policies must adapt the same linears with
+        one rank and one lora_alpha -- the model configuration's, whose alpha / r scales every slot's projection."""
+        n = len(adapters)
+        if n > MAX_SLOTS:
+            raise ValueError(f"{n} policies: at most {MAX_SLOTS} adapter slots ride in one launch")
+        if self.pool is not None:
+            raise ValueError("set_adapter_slots: this engine's slots belong to its policy pool (pool_add / load_slot)")
+        linears, adapted = self._check_adapters(adapters, lora_alpha)
+        cfg, plans = self.cfg, [adapted]
         for l in linears:
             l.clear_slots()
             if n and l.name in plans[0]:
@@ -1143,6 +1155,95 @@ class VLAEngine:
                     l.set_slot(s, torch.cat([sd[rn + ".lora_A.weight"] for rn in l.ref_names], 0), torch.cat([sd[rn + ".lora_B.weight"] for rn in l.ref_names], 0))
         self.n_slots = n
         self.llm.slot_route = self.route if any(getattr(l, "n_slots", 0) for l in self.llm.linears()) else None
+
+    # -- policy pool: any number of registered policies in device memory, `resident` of them in the slot storage -----------------------------
+    def init_policy_pool(self, resident: int, template_adapter: Dict[str, torch.Tensor], *, lora_alpha: Optional[float] = None):
+        """Allocates the slot storage for n = `resident` adapters on every linear that `template_adapter` adapts -- once: the slot count, and with
+        it the K-extension width, the fixed schedules and every captured graph, stays what it is for the life of the model.  Empty slots hold
+        zeros and no row is ever routed to one (policy_pool.Residency knows which are filled).  Registers nothing."""
+        if self.pool is not None:
+            raise ValueError("init_policy_pool: the pool exists already")
+        if not 1 <= int(resident) <= MAX_SLOTS:
+            raise ValueError(f"init_policy_pool: resident = {resident} (1 .. {MAX_SLOTS}: at most {MAX_SLOTS} adapter slots ride in one launch)")
+        if self.n_slots:
+            raise ValueError("init_policy_pool: this engine already carries adapter slots (set_adapter_slots)")
+        linears, adapted = self._check_adapters([template_adapter], [lora_alpha])
+        if not adapted:
+            raise ValueError("init_policy_pool: the template adapter adapts no linear of this model")
+        for l in linears:
+            if l.name in adapted:
+                l.init_slots(int(resident), self.cfg.lora_rank, self.route)
+        self.n_slots = int(resident)
+        self.llm.slot_route = self.route if any(getattr(l, "n_slots", 0) for l in self.llm.linears()) else None
+        self.pool = {}
+        self.pool_state = Residency(int(resident))
+        self._pool_linears = [l for l in linears if l.name in adapted]
+        self._pool_adapted = adapted
+        self._pool_tables: Dict[Tuple[str, int], dict] = {}
+
+    def pool_add(self, name: str, adapter: Dict[str, torch.Tensor], *, lora_alpha: Optional[float] = None, slot_pairs=None):
+        """Registers `name`: validated exactly as set_adapter_slots validates (rank, alpha, the pool's adapted set, stray tensors), then every
+        adapted linear's cat(lora_A) [G r, in] and cat(lora_B) [out, r] are stored in bf16 on the device.  `slot_pairs(s)` -> [(src, dst)]: further
+        tensors that belong to the policy and have to reach slot s with the adapters (the head's and the proprio projector's parameters)."""
+        if self.pool is None:
+            raise ValueError("pool_add: no policy pool (init_policy_pool)")
+        if name in self.pool:
+            raise ValueError(f"pool_add: a policy named {name!r} is already in the pool")
+        _, adapted = self._check_adapters([adapter], [lora_alpha])
+        if adapted != self._pool_adapted:
+            raise ValueError("the policies adapt different sets of linears")
+        dev, r = self.device, self.cfg.lora_rank
+        tensors = {}
+        for l in self._pool_linears:
+            A = torch.cat([adapter[rn + ".lora_A.weight"] for rn in l.ref_names], 0).to(dev, BF16).contiguous()
+            Bm = torch.cat([adapter[rn + ".lora_B.weight"] for rn in l.ref_names], 0).to(dev, BF16).contiguous()
+            if tuple(A.shape) != (l.groups * r, l.in_f) or tuple(Bm.shape) != (l.out_f, r):
+                raise ValueError(f"{l.name}: adapter shapes {tuple(A.shape)} / {tuple(Bm.shape)} do not fit rank {r} "
+                                 f"(want {(l.groups * r, l.in_f)} / {(l.out_f, r)})")
+            tensors[l.name] = (A, Bm)
+        self.pool[name] = dict(tensors=tensors, slot_pairs=slot_pairs)
+
+    def pool_remove(self, name: str):
+        """Forgets `name`: its tensors and its cached copy tables are released, the slot it occupied (if any) is empty and stale."""
+        if self.pool is None or name not in self.pool:
+            raise ValueError(f"pool_remove: unknown policy {name!r}")
+        del self.pool[name]
+        for key in [k for k in self._pool_tables if k[0] == name]:
+            del self._pool_tables[key]
+        self.pool_state.invalidate(name)
+
+    def pool_slot_pairs(self, s: int, name: str):
+        """Every (source, destination) tensor pair of loading `name` into slot s: per adapted linear the G row groups of lora_A into
+        A_slots[slot_a_rows(g, s, n, r)] and lora_B into B_slots[:, s r:(s + 1) r], then the policy's own slot_pairs(s)."""
+        p, n, r = self.pool[name], self.n_slots, self.cfg.lora_rank
+        pairs = []
+        for l in self._pool_linears:
+            A, Bm = p["tensors"][l.name]
+            pairs += [(A[g * r:(g + 1) * r], l.A_slots[slot_a_rows(g, s, n, r)]) for g in range(l.groups)]
+            pairs.append((Bm, l.B_slots[:, s * r:(s + 1) * r]))
+        if p["slot_pairs"] is not None:
+            pairs += list(p["slot_pairs"](s))
+        return pairs
+
+    def load_slot(self, s: int, name: str):
+        """Policy `name` into slot s: ONE ovla_copy_table launch on the current stream (the table of a (policy, slot) pair is built on first use
+        and kept).  The forward that follows is ordered behind it on both tower streams: the side stream forks from the current stream at the
+        head of vision_fwd (side.wait_stream(main)), and a captured graph replays on the current stream."""
+        if self.pool is None or name not in self.pool:
+            raise ValueError(f"load_slot: unknown policy {name!r}")
+        if not 0 <= s < self.n_slots:
+            raise ValueError(f"load_slot: slot {s} of {self.n_slots}")
+        tab = self._pool_tables.get((name, s))
+        if tab is None:
+            pairs = self.pool_slot_pairs(s, name)
+            tab = self._pool_tables[(name, s)] = ops.copy_table_build([ops.copy_entry(a, b) for a, b in pairs], self.device, keep=pairs)
+        ops.copy_table(tab)
+        self.pool_state.names[s] = name
+        return tab
+
+    def pool_bytes(self) -> int:
+        """Device bytes of the registered policies' adapter tensors (the slot storage itself belongs to the linears)."""
+        return sum(t.numel() * t.element_size() for p in (self.pool or {}).values() for ab in p["tensors"].values() for t in ab)
 
     @contextlib.contextmanager
     def routing(self, obs_slot: torch.Tensor, host_slots=None):

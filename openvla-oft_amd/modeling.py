@@ -23,7 +23,8 @@ import torch.nn as nn
 from . import ops
 from .config import VLAConfig
 from .diffusion import DDIMScheduler, SinusoidalPositionalEncoding
-from .engine import ChunkGraph, DiffusionGraph, ActionHead, MlpProjector, ParamStore, SlotProjectors, VLAEngine, build_component
+from .engine import MAX_SLOTS, ChunkGraph, DiffusionGraph, ActionHead, MlpProjector, ParamStore, SlotProjectors, VLAEngine, build_component
+from .policy_pool import split_passes
 from .weights import make_getter
 
 BF16 = torch.bfloat16
@@ -394,6 +395,10 @@ class OpenVLAForActionPrediction(_StoreModule):
         # multi-policy serving (add_policy): name -> dict(lora, head, pp, norm_stats), in adapter-slot order
         self._policies: Dict[str, dict] = {}
         self._policy_gen = 0
+        # policy pool (enable_policy_pool): the slot count, and the slot-resident head / proprio projector objects the forward reads
+        self._pool_resident = 0
+        self._slot_heads: Optional[list] = None
+        self._slot_pps: Optional[list] = None
 
     # -- several fine-tuned policies on one base model ------------------------------------------------------------------------------------
     @property
@@ -411,7 +416,9 @@ class OpenVLAForActionPrediction(_StoreModule):
         and alike in having a head / a proprio projector or not.  The model must carry no merged or trainable adapters.  Adding a policy changes
         the slot count n and with it the K-extension width: outputs of earlier policies are reproducible per (policy, n), not across n.
         Every policy's adapter tensors stay referenced on the host and each call refills all slots of all linears (the slot count changed): with
-        at most 4 policies that is a handful of copies per linear, done once at registration."""
+        at most 4 policies that is a handful of copies per linear, done once at registration.
+        After enable_policy_pool: no limit on the number of policies, the slot count stays the pool's `resident`, nothing is reallocated and no
+        captured graph is dropped; the policy's tensors go to device memory (engine.pool_add) and reach a slot when a batch needs them."""
         if not isinstance(name, str) or not name:
             raise ValueError("add_policy: the policy name must be a non-empty string")
         if name in self._policies:
@@ -423,12 +430,109 @@ class OpenVLAForActionPrediction(_StoreModule):
         for what in ("head", "pp"):
             if len({p[what] is None for p in pols}) > 1:
                 raise ValueError(f"add_policy: either every policy brings its own {'action head' if what == 'head' else 'proprio projector'} or none does")
+        if self._pool_resident:
+            return self._pool_add_policy(name, pol)
         self.engine.set_adapter_slots([p["lora"] for p in pols], lora_alpha=[p["lora_alpha"] for p in pols])   # validates before it changes anything
         self._policies[name] = pol
         self._policy_gen += 1
         for k in [k for k in self._graphs if "policies" in k]:   # captured against the previous slot storage
             del self._graphs[k]
         return self
+
+    # -- the policy pool: any number of registered policies, `resident` of them in the adapter slots at a time ---------------------------------
+    def enable_policy_pool(self, resident: int = 4):
+        """Before the first add_policy: from then on add_policy registers into a pool without a limit on the number of policies (their tensors
+        stay in device memory), remove_policy takes one out again, and predict_action_batch(policy=[...]) copies the up-to-`resident` policies
+        a forward needs into fixed slot storage just before it (one ovla_copy_table launch per policy that is not there yet; least recently
+        used slot first: policy_pool.plan_loads).  The slot count is `resident` (1 .. engine.MAX_SLOTS) from the first add_policy on and never
+        changes: K-extension width, fixed schedules and captured graphs stay valid for the life of the model, and a policy's outputs are
+        reproducible per (policy, resident) whatever else is registered or resident.  A forward costs what n = `resident` slots cost, however
+        few policies are registered.  All policies must be alike in having a head / a proprio projector, with identical shapes."""
+        if self._policies:
+            raise ValueError("enable_policy_pool: call it before the first add_policy (the slot count is fixed from then on)")
+        if self._pool_resident:
+            raise ValueError("enable_policy_pool: the pool is enabled already")
+        if isinstance(resident, bool) or not isinstance(resident, int) or not 1 <= resident <= MAX_SLOTS:
+            raise ValueError(f"enable_policy_pool: resident = {resident!r} (1 .. {MAX_SLOTS}: at most {MAX_SLOTS} adapter slots ride in one launch)")
+        self._pool_resident = resident
+        return self
+
+    @property
+    def policy_pool_resident(self) -> int:
+        """The pool's slot count; 0 without a pool."""
+        return self._pool_resident
+
+    @staticmethod
+    def _store_layout(mod):
+        return None if mod is None else [(p.name, p.shape, p.dtype, p.offset) for p in mod.store.params]
+
+    @staticmethod
+    def _param_pairs(src, dst):
+        """(source, destination) of everything a head's / projector's forward reads: the flat parameter buffers, and the bf16 compute copies of
+        fp32-master linears."""
+        pairs = [(flat, dst.store.flat[dt]) for dt, flat in src.store.flat.items()]
+        for ls, ld in zip(src.comp.linears(), dst.comp.linears()):
+            if ls.master_fp32:
+                pairs.append((ls.Wc, ld.Wc))
+                if ls.bc is not None:
+                    pairs.append((ls.bc, ld.bc))
+        return pairs
+
+    def _pool_add_policy(self, name, pol):
+        eng, head, pp = self.engine, pol["head"], pol["pp"]
+        first = eng.pool is None
+        if not first:   # same head / projector shapes as the slot-resident objects
+            for what, mod, slots in (("action head", head, self._slot_heads), ("proprio projector", pp, self._slot_pps)):
+                if mod is not None and self._store_layout(mod) != self._store_layout(slots[0]):
+                    raise ValueError(f"add_policy: the {what} of {name!r} has other shapes than the pool's (one head / projector shape per pool)")
+        else:
+            eng.init_policy_pool(self._pool_resident, pol["lora"], lora_alpha=pol["lora_alpha"])   # validates before it allocates
+            R = self._pool_resident
+            if head is not None:
+                sd, c = head.state_dict(), head.cfg
+                self._slot_heads = [L1RegressionActionHead(c.llm_dim, c.llm_dim, c.action_dim, num_actions_chunk=c.chunk, device=self.device, state_dict=sd)
+                                    for _ in range(R)]
+            if pp is not None:
+                sd = pp.state_dict()
+                self._slot_pps = [ProprioProjector(pp.llm_dim, pp.in_dim, device=self.device, state_dict=sd) for _ in range(R)]
+            self._policy_gen += 1
+
+        def slot_pairs(s):
+            return (self._param_pairs(head, self._slot_heads[s]) if head is not None else []) + \
+                   (self._param_pairs(pp, self._slot_pps[s]) if pp is not None else [])
+
+        eng.pool_add(name, pol["lora"], lora_alpha=pol["lora_alpha"], slot_pairs=slot_pairs)
+        self._policies[name] = dict(pol, lora=None)   # the pool holds the adapters on the device: no host reference is kept
+        return self
+
+    def remove_policy(self, name: str):
+        """Pool mode: takes `name` out of the pool.  Its slot is stale from here on: a later add_policy under the same name is loaded afresh."""
+        if not self._pool_resident:
+            raise ValueError("remove_policy needs the policy pool (enable_policy_pool): without it the slot layout is the registration order")
+        if name not in self._policies:
+            raise ValueError(f"remove_policy: unknown policy {name!r} (registered: {list(self._policies)})")
+        self.engine.pool_remove(name)
+        del self._policies[name]
+        return self
+
+    @property
+    def policy_pool_stats(self) -> Dict[str, int]:
+        """loads (slot swaps performed), hits (needed policies found resident), passes (forwards) since enable_policy_pool."""
+        st = getattr(self.engine, "pool_state", None)
+        return dict(st.stats) if st is not None else dict(loads=0, hits=0, passes=0)
+
+    @property
+    def policy_pool_bytes(self) -> int:
+        """Device memory the registered policies hold beside the slot storage: adapters (bf16), head and proprio projector parameters with
+        their compute copies.  Gradient and optimizer buffers of heads / projectors that were trained in this process are not counted."""
+        if not self._pool_resident or self.engine.pool is None:
+            return 0
+        total = self.engine.pool_bytes()
+        for p in self._policies.values():
+            for mod, slots in ((p["head"], self._slot_heads), (p["pp"], self._slot_pps)):
+                if mod is not None:
+                    total += sum(a.numel() * a.element_size() for a, _ in self._param_pairs(mod, slots[0]))
+        return total
 
     def policy_norm_stats(self, name: Optional[str] = None) -> dict:
         """The statistics a policy un-normalises with: its own `norm_stats` when add_policy was given some, otherwise the model's (also for None)."""
@@ -583,14 +687,14 @@ class OpenVLAForActionPrediction(_StoreModule):
                         return g, (head_comp, pp_comp, nap_comp)
                     per_slot, keep = None, (head_comp, pp_comp)
                     if policy is not None:
-                        per_slot = [(None if heads is None else heads[s], None if pps is None else pps[s]) for s in range(len(self._policies))]
+                        per_slot = [(None if heads is None else heads[s], None if pps is None else pps[s]) for s in range(eng.n_slots)]
                         keep = (heads, pps)
                     g = ChunkGraph(eng, B, L, pixel_values.shape, head=head_comp, use_proprio=use_proprio, proprio_projector=pp_comp, invariant=invariant,
                                    film=film, discrete=batch and discrete, n_tokens=self.vocab_size, n_bins=self.bin_centers.shape[0], policies=per_slot)
                     return g, keep
 
                 key = self._graph_key(batch, B, L, pixel_values.shape, use_proprio=use_proprio, head_comp=head_comp, pp_comp=pp_comp, film=film,
-                                      discrete=discrete, ddim=ddim, n_policies=len(self._policies) if policy is not None else 0)
+                                      discrete=discrete, ddim=ddim, n_policies=eng.n_slots if policy is not None else 0)
                 g = self._graph_for(key, build)
                 if use_diffusion:
                     # the whole loop from two captured graphs, no host work between the steps (engine.DiffusionGraph): same bits as the loop below
@@ -630,6 +734,33 @@ class OpenVLAForActionPrediction(_StoreModule):
                     elif action_head is not None:
                         pred = action_head.predict_action(hidden)
             normalized = cur.numpy() if use_diffusion else self._decode(pred, bins, hidden)
+        return normalized, hidden
+
+    def _infer_pooled(self, ids, mask, labels, pixel_values, prop, policy, use_proprio):
+        """_infer(batch=True) of a pooled model: per pass of at most `resident` distinct policies (in order of first appearance) plan the
+        residency, load what is missing (engine.load_slot: one launch per policy, on the stream of the forward), route each observation to its
+        policy's slot.  The fixed schedules make an observation's bits independent of its batch, so the split does not show in the results."""
+        eng, st = self.engine, self.engine.pool_state
+        heads = [h.comp for h in self._slot_heads] if self._slot_heads is not None else None
+        pps = [p.comp for p in self._slot_pps] if use_proprio else None
+        passes = split_passes(policy, self._pool_resident)
+        normalized = hidden = None
+        for needed in passes:
+            rows = [b for b, p in enumerate(policy) if p in needed]
+            loads = st.plan(needed)
+            for s, nm in loads:
+                eng.load_slot(s, nm)
+            slot_of = st.commit(loads, needed)
+            whole = len(passes) == 1
+            sub = (lambda t: t) if whole else (lambda t: None if t is None else t[rows])
+            n_p, h_p = self._infer(sub(ids), sub(mask), sub(labels), sub(pixel_values), sub(prop), batch=True,
+                                   policy=([slot_of[policy[b]] for b in rows], heads, pps))
+            if whole:
+                return n_p, h_p
+            if normalized is None:
+                normalized = np.empty((len(policy),) + n_p.shape[1:], dtype=n_p.dtype)
+                hidden = torch.empty((len(policy),) + tuple(h_p.shape[1:]), dtype=h_p.dtype, device=h_p.device)
+            normalized[rows], hidden[rows] = n_p, h_p
         return normalized, hidden
 
     # -- predict_action (:946-1060) -------------------------------------------------------------------------------------
@@ -741,6 +872,10 @@ class OpenVLAForActionPrediction(_StoreModule):
             ids[b, : len(r)], mask[b, : len(r)] = r, True
             labels[b, len(r) - A - 1: len(r)] = ACTION_TOKEN_BEGIN_IDX + 1
             labels[b, len(r) - 1] = STOP_INDEX
+        if policy is not None and self._pool_resident:
+            normalized, hidden = self._infer_pooled(ids, mask, labels, pixel_values, prop, policy, use_proprio)
+            stats = [self.policy_norm_stats(p) for p in policy]
+            return np.stack([self._unnormalize_actions(normalized[b], unnorm_key, stats[b]) for b in range(B)]), hidden
         if policy is not None:   # each observation under its own policy's adapter slot, head, proprio projector and statistics
             names = list(self._policies)
             pols = list(self._policies.values())

@@ -386,6 +386,56 @@ def transpose_batched(tab):
     _lib.check(_lib.lib().ovla_transpose_batched(ptr, tab["tile_start"].data_ptr(), tab["n"], tab["total"], _stream()), "ovla_transpose_batched")
 
 
+def copy_entry(src, dst):
+    """One ovla_copy_table entry (src, dst, src_ld_bytes, dst_ld_bytes, rows, row_bytes) for two tensors of the same dtype and shape, 1-D (one
+    row) or 2-D with unit inner stride (a strided view of a wider tensor is what the table is for)."""
+    assert src.dtype == dst.dtype and src.shape == dst.shape and src.dim() in (1, 2) and src.stride(-1) == 1 and dst.stride(-1) == 1
+    es = src.element_size()
+    if src.dim() == 1:
+        return (src.data_ptr(), dst.data_ptr(), src.numel() * es, dst.numel() * es, 1, src.numel() * es)
+    rows, cols = src.shape
+    if src.stride(0) == cols and dst.stride(0) == cols:   # both contiguous: one long row
+        return (src.data_ptr(), dst.data_ptr(), rows * cols * es, rows * cols * es, 1, rows * cols * es)
+    return (src.data_ptr(), dst.data_ptr(), src.stride(0) * es, dst.stride(0) * es, rows, cols * es)
+
+
+def copy_table_build(entries, device, keep=None):
+    """The device table of ovla_copy_table from [(src, dst, src_ld_bytes, dst_ld_bytes, rows, row_bytes)] (addresses and byte counts; the
+    tensors behind them never move: `keep` holds references).  ovla_copy_table_plan validates the entries and counts the tiles."""
+    T = STRUCTS["ovla_copy_entry"]
+    n = len(entries)
+    arr = (T * max(n, 1))()
+    for i, (src, dst, sld, dld, rows, row_bytes) in enumerate(entries):
+        arr[i].src, arr[i].dst, arr[i].src_ld_bytes, arr[i].dst_ld_bytes, arr[i].rows, arr[i].row_bytes = src, dst, sld, dld, rows, row_bytes
+    starts = (ctypes.c_int32 * (n + 1))()
+    _lib.check(_lib.lib().ovla_copy_table_plan(arr, n, ctypes.cast(starts, ctypes.c_void_p)), "ovla_copy_table_plan")
+    raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
+    tile_start = torch.tensor(list(starts), dtype=torch.int32).to(device)
+    nbytes = sum(e[4] * e[5] for e in entries)
+    return dict(table=raw, tile_start=tile_start, n=n, total=int(starts[n]), nbytes=nbytes, keep=keep)
+
+
+_copy_tables = {}
+
+
+def copy_table(entries, device=None):
+    """ovla_copy_table on the current stream: every entry's rows x row_bytes rectangle, device to device, in ONE launch.  `entries`: a table
+    from copy_table_build, or the entry tuples themselves -- their table is then built on first use and cached by value."""
+    if isinstance(entries, dict):
+        tab = entries
+    else:
+        device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        key = (device, tuple(tuple(int(v) for v in e) for e in entries))
+        tab = _copy_tables.get(key)
+        if tab is None:
+            if len(_copy_tables) >= 64:   # by-value tables are for tools and tests; the engine keeps its own per (policy, slot)
+                _copy_tables.pop(next(iter(_copy_tables)))
+            tab = _copy_tables[key] = copy_table_build(key[1], device)
+    ptr = ctypes.cast(ctypes.c_void_p(tab["table"].data_ptr()), ctypes.POINTER(STRUCTS["ovla_copy_entry"]))
+    _lib.check(_lib.lib().ovla_copy_table(ptr, tab["tile_start"].data_ptr(), tab["n"], tab["total"], _stream()), "ovla_copy_table")
+    return tab
+
+
 def colsum(x, out):
     """out[n] += sum_m x[m,n]  (fp32 accumulate)."""
     _chk(x); _chk(out, torch.float32)

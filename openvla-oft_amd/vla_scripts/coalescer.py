@@ -15,7 +15,11 @@ One worker thread owns every call of `batch_fn`, so a non-re-entrant engine need
   * `submit_group(items)` (a pre-formed batch, `/act_batch`) goes through the same worker as one call of its own and is never merged,
     split or retried: it succeeds or fails as a whole;
   * an exception that escapes the worker loop itself fails every pending future instead of leaving its caller blocked;
-  * `close()` lets the worker drain what is queued, then joins it.
+  * `close()` lets the worker drain what is queued, then joins it;
+  * `key_fn` and `max_keys` (both or neither): a coalesced batch holds at most `max_keys` distinct `key_fn(item)` values.  Collection stops
+    at the first queued request whose key would be one too many; that request stays at the head of the queue and leads the next batch, so
+    the order of arrival is kept.  (The server's key is the payload's policy and the limit its number of resident adapter slots: a batch then
+    never needs a second forward pass.)  Pre-formed groups are not examined.
 """
 from __future__ import annotations
 
@@ -35,7 +39,11 @@ class _Entry:
 
 class RequestCoalescer:
     def __init__(self, batch_fn: Callable[[List[Any], Optional[int]], Sequence[Any]], *, coalesce_ms: float, max_batch: int = 8,
-                 buckets: Sequence[int] = (1, 2, 4, 8)):
+                 buckets: Sequence[int] = (1, 2, 4, 8), key_fn: Optional[Callable[[Any], Any]] = None, max_keys: Optional[int] = None):
+        if (key_fn is None) != (max_keys is None):
+            raise ValueError("RequestCoalescer: key_fn and max_keys go together")
+        if max_keys is not None and max_keys < 1:
+            raise ValueError("max_keys must be at least 1")
         if coalesce_ms <= 0:
             raise ValueError("RequestCoalescer needs coalesce_ms > 0 (at 0 the server does not coalesce at all)")
         if max_batch < 1:
@@ -43,6 +51,7 @@ class RequestCoalescer:
         self.batch_fn = batch_fn
         self.window = coalesce_ms / 1000.0
         self.max_batch = int(max_batch)
+        self.key_fn, self.max_keys = key_fn, max_keys
         self.buckets = tuple(sorted(int(b) for b in buckets))
         self.calls = 0                     # batch_fn invocations (statistics for tools / tests)
         self._queue = collections.deque()
@@ -101,10 +110,16 @@ class RequestCoalescer:
             if taken[0].group:
                 return taken
             deadline = taken[0].t + self.window
+            keys = {self.key_fn(taken[0].items[0])} if self.key_fn is not None else None
             while len(taken) < self.max_batch:
                 if self._queue:
                     if self._queue[0].group:      # order of arrival is kept: the group runs next, on its own
                         break
+                    if keys is not None:
+                        k = self.key_fn(self._queue[0].items[0])
+                        if k not in keys and len(keys) >= self.max_keys:   # one key too many: it leads the next batch
+                            break
+                        keys.add(k)
                     taken.append(self._queue.popleft())
                     continue
                 left = deadline - time.monotonic()

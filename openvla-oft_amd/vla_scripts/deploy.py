@@ -23,6 +23,11 @@ Differences, all deliberate:
     (every policy's adapters ride in the same launches: OpenVLAForActionPrediction.add_policy / predict_action_batch(policy=...)), coalesced
     or not.  The coalescer knows nothing of it: the name travels inside the item.  An unknown or missing name answers "error" like any
     malformed payload.  With no policies configured a payload without "policy" is served exactly as before.
+  * `resident_policies > 0` (not in the reference): the policies go into the model's policy pool (enable_policy_pool) -- any number of them
+    registered, `resident_policies` (1 .. 4) in the adapter slots at a time, swapped in by one copy launch each just before a forward that
+    needs them.  The coalescer then forms batches of at most that many distinct policies (key_fn / max_keys), so a coalesced forward never
+    splits; an `/act_batch` group that names more is split into passes by predict_action_batch.  At 0 (the default) nothing changes: at most
+    4 policies, registered once.
 """
 from __future__ import annotations
 
@@ -103,6 +108,7 @@ class DeployConfig:
     coalesce_ms: float = 0.0            # > 0: merge /act requests that arrive within this window into one batched forward (not in the reference)
     max_batch: int = 8                  # most requests merged into one forward
     batch_buckets: tuple = (1, 2, 4, 8)  # a merged batch runs at the smallest of these that holds it: bounds the number of captured graphs
+    resident_policies: int = 0          # > 0: `policies` go into a policy pool with this many adapter slots (any number of policies; not in the reference)
     # fmt: on
 
 
@@ -111,6 +117,10 @@ class OpenVLAServer:
         self.cfg = cfg
         self.vla = vla if vla is not None else U.get_vla(cfg)
         self.policies = tuple(policies) if policies else ()
+        resident = int(getattr(cfg, "resident_policies", 0) or 0)
+        if resident > 0 and not getattr(self.vla, "policy_pool_resident", 0):
+            self.vla.enable_policy_pool(resident)   # before the first add_policy: the slot count is fixed from there on
+        resident = getattr(self.vla, "policy_pool_resident", 0) if resident > 0 else 0   # a model handed in with its pool keeps its own slot count
         for name, spec in (policies or {}).items():   # head, proprio projector and statistics come with each policy
             if name in self.vla.policies:
                 continue
@@ -144,7 +154,8 @@ class OpenVLAServer:
             # one captured graph per (batch bucket, 8-token text-length bucket): room for 4 text buckets per batch bucket before the least
             # recently used graph is evicted and recaptured (task prompts of varied length would otherwise thrash captures)
             self.vla.max_batch_graphs = max(getattr(self.vla, "max_batch_graphs", 8), 4 * len(buckets))
-            self._coalescer = RequestCoalescer(self._run_batch, coalesce_ms=cfg.coalesce_ms, max_batch=getattr(cfg, "max_batch", 8), buckets=buckets)
+            keyed = dict(key_fn=lambda item: item[0].get("policy"), max_keys=resident) if resident > 0 and self.policies else {}
+            self._coalescer = RequestCoalescer(self._run_batch, coalesce_ms=cfg.coalesce_ms, max_batch=getattr(cfg, "max_batch", 8), buckets=buckets, **keyed)
 
     # -- coalescing mode: the worker thread of self._coalescer is the only thread that touches the engine ---------------------------------
     def _norm_stats(self, policy: Optional[str]) -> dict:
