@@ -237,6 +237,38 @@ typedef struct {
 } ovla_select_by_slot_args;
 int ovla_select_by_slot(const ovla_select_by_slot_args* a, void* stream);
 
+/* Per-policy FiLM: every observation's gamma / beta vectors from ITS OWN policy's scale / shift Linears (prismatic/models/film_vit_wrapper.py:53-54,
+ * 65-72: `gamma = self.scale(average_language_embedding)`, `beta = self.shift(...)` in every tower block; a fine-tune saves them inside
+ * `vision_backbone--{step}_checkpoint.pt`, experiments/robot/openvla_utils.py:311-349), for all n_linears Linears of both towers in ONE launch:
+ *     out_j[b, c] = bf16( bias_j[slot(b)][c] + sum_k W_j[slot(b)][c, k] * avg[b, k] )        b < n_obs, fp32 sums, one rounding
+ * with slot(b) = obs_slot[b] (DEVICE int32 [n_obs], clamped to [0, n) by the kernel as ovla_lora_route clamps: no index formed from it leaves a
+ * buffer; obs_slot_host, optional, is validated before anything is launched).  Linear j is one ovla_film_linear:
+ *     W bf16 [n][out_f][D] (16-byte base), bias bf16 [n][out_f], out bf16 [rows >= n_obs][out_f] (row stride out_f), out_f >= 1,
+ *     item_start = sum over the Linears before j of ceil(out_f / OVLA_FILM_ITEM_COLS)   (a wave computes OVLA_FILM_ITEM_COLS columns at a time)
+ * `table` is the DEVICE array of the n_linears descriptors, `table_host` the same array in HOST memory (validated: pointers, out_f, alignment,
+ * item_start).  avg bf16 [>= n_obs, D] with row stride ld_avg (elements; % 8, 16-byte base).  D % 8 == 0 (any such D whose row fits in LDS),
+ * 1 <= n <= OVLA_MAX_SLOTS, 1 <= n_obs <= OVLA_FILM_MAX_OBS.
+ *  - Only the slots some observation is routed to are read: an unused slot's weights may be stale or NaN.  Rows >= n_obs of every out are not
+ *    written.  A row's arithmetic sees its own avg row and its own slot's weights only (selected by address, never multiplied by 0 / 1).
+ *  - Batch-invariant by construction: a lane adds its 16-byte k-vectors l, l + 64, ... in order, the 64 lane sums meet in one fixed exchange tree;
+ *    the bits of out_j[b, :] depend on avg[b, :], the weights of slot(b), D and out_f -- not on n_obs, b's position, the other observations or n.
+ *  - Each weight row is streamed once per used slot and group of 8 observations of that slot (16-byte loads straight to registers, 4 rows per
+ *    wave in flight, the group's avg rows staged in LDS); no atomics, no cross-workgroup communication; stream-ordered and capturable.
+ * Every argument check returns OVLA_EINVAL before any launch. */
+#define OVLA_MAX_SLOTS 4
+#define OVLA_FILM_MAX_OBS 64
+#define OVLA_FILM_ITEM_COLS 4
+typedef struct { const void* W; const void* bias; void* out; int32_t out_f; int32_t item_start; } ovla_film_linear;
+typedef struct {
+  const void* table;                 /* device ovla_film_linear [n_linears] */
+  const void* table_host;            /* the same descriptors in host memory */
+  const void* avg; int64_t ld_avg;   /* bf16 [>= n_obs, D] */
+  const int32_t* obs_slot;           /* device int32 [n_obs] */
+  const int32_t* obs_slot_host;      /* optional host copy, validated */
+  int32_t n_linears, n_obs, n, D;
+} ovla_film_vectors_args;
+int ovla_film_vectors(const ovla_film_vectors_args* a, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * LoRA dropout (FinetuneConfig.lora_dropout, finetune.py:119 -> LoraConfig, :862-871): peft puts an independent nn.Dropout(p) in front of the
  * lora_A of every adapted nn.Linear, active in training mode only:  y = W x + s B_g(A_g(dropout_g(x))).  A fused q|k|v or gate|up linear

@@ -93,6 +93,9 @@ OVLA_DEV float act_grad(float z, int act) {
 // elementwise.hip and the fused head tail of head_optim.hip -- goes through this function, so they agree bit for bit by construction).
 OVLA_DEV float ln_affine(float x, float mean, float rstd, float w, float b) { return __builtin_fmaf((x - mean) * rstd, w, b); }
 
+// multi-policy serving: the adapter slot an observation is routed to, read from a device array and clamped, so that no index formed from it leaves a buffer
+OVLA_DEV int clamp_slot(int s, int n) { return s < 0 ? 0 : (s >= n ? n - 1 : s); }
+
 OVLA_DEV float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -123,4 +126,11 @@ void ovla_set_error(const char* fmt, ...);
   } while (0)
 
 static inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+// the optional host copy of a device obs_slot array: an entry outside [0, n) is refused before anything is launched
+static inline int check_host_slots(const int32_t* host, int n_obs, int n, const char* who) {
+  if (!host) return OVLA_OK;
+  for (int i = 0; i < n_obs; ++i)
+    OVLA_REQUIRE(host[i] >= 0 && host[i] < n, "%s: obs_slot[%d] = %d is outside [0, %d)", who, i, host[i], n);
+  return OVLA_OK;
+}
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }

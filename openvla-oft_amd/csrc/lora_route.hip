@@ -6,8 +6,6 @@
 
 namespace {
 
-OVLA_DEV int clamp_slot(int s, int n) { return s < 0 ? 0 : (s >= n ? n - 1 : s); }
-
 // One thread per 16-byte vector (8 bf16 columns) of the routed width G*n*r; r % 8 == 0, so a vector lies inside one slot's column block.
 // Foreign vectors are OVERWRITTEN with +0 (never multiplied: a NaN / Inf of another adapter's projection must not reach the row); the row's
 // own vectors and the columns >= G*n*r are not touched.
@@ -37,12 +35,6 @@ __global__ __launch_bounds__(256) void select_by_slot_kernel(const U* __restrict
   dst[idx] = src[(int64_t)s * slot_stride + idx];
 }
 
-int check_host_slots(const int32_t* host, int n_obs, int n, const char* who) {
-  if (!host) return OVLA_OK;
-  for (int i = 0; i < n_obs; ++i)
-    OVLA_REQUIRE(host[i] >= 0 && host[i] < n, "%s: obs_slot[%d] = %d is outside [0, %d)", who, i, host[i], n);
-  return OVLA_OK;
-}
 }  // namespace
 
 extern "C" int ovla_lora_route(const ovla_lora_route_args* a, void* stream_) {

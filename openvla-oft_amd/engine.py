@@ -231,6 +231,81 @@ class SlotProjectors:
         return out, None
 
 
+def film_linear_names(towers) -> List[str]:
+    """The FiLM Linears of both towers in table order: towers = [(prefix, used blocks, dim)], per block `scale` then `shift`
+    (film_vit_wrapper.py:53-54).  The order of ovla_film_vectors' descriptor table and of FilmSlots.names."""
+    return [f"{prefix}blocks.{i}.{kind}" for prefix, blocks, _ in towers for i in range(blocks) for kind in ("scale", "shift")]
+
+
+def fill_film_slot(W_slots, b_slots, s: int, W, b):
+    """Writes policy s's Linear (W [dim, D], b [dim]) into the slot storage of one FiLM Linear: W_slots [n, dim, D], b_slots [n, dim].  THE layout
+    ovla_film_vectors reads: out[b] = b_slots[slot(b)] + W_slots[slot(b)] . avg[b]."""
+    W_slots[s] = W.to(W_slots.device, W_slots.dtype)
+    b_slots[s] = b.to(b_slots.device, b_slots.dtype)
+
+
+def check_film_tensors(film, towers, D: int, device, who: str) -> Dict[str, torch.Tensor]:
+    """A policy's FiLM tensors against towers = [(prefix, used blocks, dim)]: the exact key set `<film_linear_names>.{weight,bias}`, shapes
+    (dim, D) / (dim,), finite.  -> the tensors in bf16 (RNE from what was given) on `device`.  Raises before anything is changed."""
+    if not isinstance(film, dict):
+        raise ValueError(f"{who}: `film` must be a dict of the policy's FiLM tensors (vision_backbone.featurizer.blocks.0.scale.weight, ...)")
+    dims = {nm: dim for prefix, blocks, dim in towers for nm in film_linear_names([(prefix, blocks, dim)])}
+    want = {f"{nm}.{leaf}" for nm in dims for leaf in ("weight", "bias")}
+    missing, stray = sorted(want - set(film)), sorted(set(film) - want)
+    if missing or stray:
+        raise ValueError(f"{who}: the FiLM tensors must be exactly the scale / shift Linears of the towers' used blocks: "
+                         f"{len(missing)} missing (e.g. {missing[:2]}), {len(stray)} unknown (e.g. {stray[:2]})")
+    out = {}
+    for nm, dim in dims.items():
+        for leaf, shape in (("weight", (dim, D)), ("bias", (dim,))):
+            t = film[f"{nm}.{leaf}"]
+            if tuple(t.shape) != shape:
+                raise ValueError(f"{who}: {nm}.{leaf} has shape {tuple(t.shape)}, the model's is {shape}")
+            if not bool(torch.isfinite(t.float()).all()):
+                raise ValueError(f"{who}: {nm}.{leaf} holds non-finite values")
+            out[f"{nm}.{leaf}"] = t.detach().to(device, torch.float32).to(BF16).contiguous()
+    return out
+
+
+class FilmSlots:
+    """Per-policy FiLM of both towers (multi-policy serving; inference only): per FiLM Linear the n policies' weights W_slots [n, dim, D] and
+    biases b_slots [n, dim] in bf16 (the reference evaluates the backbone after `.to(torch.bfloat16)`: RNE from the fp32 checkpoint tensors), the
+    gamma / beta output buffers [MAX_OBS, dim] that ONE ovla_film_vectors launch per forward fills for the observations of the batch, and
+    the launch's device table, built once per slot allocation.  Empty slots hold zeros and no observation is routed to one."""
+
+    MAX_OBS = ops.FILM_MAX_OBS
+
+    def __init__(self, towers, n: int, D: int, device):
+        if not 1 <= n <= MAX_SLOTS:
+            raise ValueError(f"FilmSlots: {n} slots (1 .. {MAX_SLOTS} supported)")
+        self.n, self.D = n, D
+        self.names = film_linear_names(towers)
+        dims = [dim for _, blocks, dim in towers for _ in range(2 * blocks)]
+        self.W_slots = {nm: torch.zeros((n, dim, D), dtype=BF16, device=device) for nm, dim in zip(self.names, dims)}
+        self.b_slots = {nm: torch.zeros((n, dim), dtype=BF16, device=device) for nm, dim in zip(self.names, dims)}
+        self.out = {nm: torch.zeros((self.MAX_OBS, dim), dtype=BF16, device=device) for nm, dim in zip(self.names, dims)}
+        self.table = ops.film_table([(self.W_slots[nm], self.b_slots[nm], self.out[nm]) for nm in self.names], device)
+
+    def set_slot(self, s: int, film: Dict[str, torch.Tensor]):
+        """Policy s from checked tensors (check_film_tensors)."""
+        for nm in self.names:
+            fill_film_slot(self.W_slots[nm], self.b_slots[nm], s, film[nm + ".weight"], film[nm + ".bias"])
+
+    def slot_pairs(self, s: int, film: Dict[str, torch.Tensor]):
+        """(source, destination) of loading checked tensors into slot s: what the policy pool's copy table moves."""
+        return [pr for nm in self.names for pr in ((film[nm + ".weight"], self.W_slots[nm][s]), (film[nm + ".bias"], self.b_slots[nm][s]))]
+
+    def launch(self, avg, route: "SlotRoute"):
+        """gamma / beta of every block of both towers for the route's observations: ONE launch on the current stream."""
+        if route.n_obs > self.MAX_OBS:
+            raise ValueError(f"per-policy FiLM: {route.n_obs} observations in one forward (at most {self.MAX_OBS})")
+        ops.film_vectors(self.table, avg, route.obs_slot, host_slots=route.host_slots)
+
+    def vectors(self, prefix: str, i: int, n_obs: int):
+        """(gamma, beta) [n_obs, dim] of block i of the tower `prefix`: views of the launch's outputs."""
+        return self.out[f"{prefix}blocks.{i}.scale"][:n_obs], self.out[f"{prefix}blocks.{i}.shift"][:n_obs]
+
+
 def launch_tn(probs):
     """The weight-gradient TN problems of one linear, or of a tn_queue, in launches of at most ops.TN_MAX_GROUP (more than one launch only
     with dropout's per-group dA problems on a fused linear: G dB + G dA instead of G + 1)."""
@@ -531,10 +606,11 @@ class VitTower:
         # only blocks 0 .. depth-2 are ever used: the forward returns the output of block depth-2
         # (get_intermediate_layers(n={depth-2})); the last block's output is discarded (film_vit_wrapper.py:124-137)
         self.film = film
+        self.film_slots: Optional[FilmSlots] = None   # film == "per_policy": the engine's FilmSlots once slots are allocated (VLAEngine._alloc_film_slots)
         for i in range(vc.depth - 1):
             p = f"{prefix}blocks.{i}."
             fl = None
-            if film:   # film_vit_wrapper.py:53-54: fp32 nn.Linear(llm_dim, vision_dim) pairs, trained in full
+            if film and film != "per_policy":   # film_vit_wrapper.py:53-54: fp32 nn.Linear(llm_dim, vision_dim) pairs, trained in full
                 fl = (FullLinear(store, p + "scale", get(p + "scale.weight").float(), get(p + "scale.bias").float(), master_fp32=True),
                       FullLinear(store, p + "shift", get(p + "shift.weight").float(), get(p + "shift.bias").float(), master_fp32=True))
             blk = dict(film=fl, ln1_w=get(p + "norm1.weight"), ln1_b=get(p + "norm1.bias"), ln2_w=get(p + "norm2.weight"), ln2_b=get(p + "norm2.bias"),
@@ -580,12 +656,17 @@ class VitTower:
         T = vc.n_patches + vc.n_prefix
         H, hd = vc.heads, vc.head_dim
         saved = []
-        for blk in self.blocks:
+        for i, blk in enumerate(self.blocks):
             h1, mean1, rstd1 = ops.norm_fwd(x, blk["ln1_w"], blk["ln1_b"], eps=vc.eps, rms=False, save_stats=train)
             qkv, s_qkv = blk["qkv"].fwd(h1)
             o, lse = ops.attn_fwd(qkv[:, : vc.dim], qkv[:, vc.dim: 2 * vc.dim], qkv[:, 2 * vc.dim:], B, T, H, hd)
             fsv = None
-            if blk["film"] is not None:
+            if self.film == "per_policy":
+                # the same modulation with each observation's OWN policy's gamma / beta: views of what the forward's one ovla_film_vectors
+                # launch wrote (VLAEngine.vision_fwd) instead of two M = 8 GEMMs per block
+                gamma, beta = self.film_slots.vectors(self.prefix, i, pixels.shape[0])
+                x2, s_proj = blk["proj"].fwd(o, residual=x, colscale=blk["ls1"], film=(gamma, beta, n_img * T))
+            elif blk["film"] is not None:
                 # x = (x + ls1 * attn(...)) * (1 + gamma) + beta, gamma/beta = Linear(mean language embedding) per SAMPLE
                 # (both images of a sample share them): fused into the proj GEMM's epilogue
                 gamma, s_sc = blk["film"][0].fwd(film_avg)
@@ -1025,9 +1106,16 @@ class VLAEngine:
         lora = lora_predicate(lora, has)
         st = self.store = ParamStore(device)
         # registration order = forward order (the store reverses it into backward order)
-        self.use_film = use_film
-        self.dino = VitTower(st, "vision_backbone.featurizer.", cfg.dino, get, cfg, lora, film=use_film)
-        self.siglip = VitTower(st, "vision_backbone.fused_featurizer.", cfg.siglip, get, cfg, lora, film=use_film)
+        if use_film not in (False, True, "per_policy"):
+            raise ValueError(f'use_film = {use_film!r} (False, True or "per_policy")')
+        # "per_policy": the towers carry FiLM SLOT storage (FilmSlots, allocated with the adapter slots) and no FiLM Linears of their own;
+        # every observation is modulated by its own policy's scale / shift Linears.  Inference only.
+        self.film_per_policy = use_film == "per_policy"
+        self.film_slots: Optional[FilmSlots] = None
+        self.use_film = bool(use_film)
+        tower_film = "per_policy" if self.film_per_policy else bool(use_film)
+        self.dino = VitTower(st, "vision_backbone.featurizer.", cfg.dino, get, cfg, lora, film=tower_film)
+        self.siglip = VitTower(st, "vision_backbone.fused_featurizer.", cfg.siglip, get, cfg, lora, film=tower_film)
         s = cfg.lora_scale
 
         def L(name):
@@ -1135,17 +1223,46 @@ class VLAEngine:
             raise ValueError("the policies adapt different sets of linears")
         return linears, (plans[0] if plans else frozenset())
 
-    def set_adapter_slots(self, adapters: List[Dict[str, torch.Tensor]], *, lora_alpha: Optional[List[Optional[float]]] = None):
+    def _film_towers(self):
+        return [(t.prefix, len(t.blocks), t.vc.dim) for t in (self.dino, self.siglip)]
+
+    def _alloc_film_slots(self, n: int):
+        """FiLM slot storage for n policies on both towers (n = 0 removes it); the towers read their blocks' gamma / beta from it."""
+        self.film_slots = FilmSlots(self._film_towers(), n, self.cfg.llm_dim, self.device) if n else None
+        self.dino.film_slots = self.siglip.film_slots = self.film_slots
+
+    def _check_film(self, film, n: int, who: str):
+        """`film` (one dict per policy, or None) against the engine's mode, before anything changes -> the checked bf16 device tensors per policy."""
+        if not self.film_per_policy:
+            if film is not None and any(f is not None for f in film):
+                raise ValueError(f"{who}: FiLM tensors were given, but the model was not built with use_film=\"per_policy\" "
+                                 "(a model without FiLM has no place for them; a model with its own FiLM Linears serves one policy)")
+            return None
+        if n == 0 and not film:
+            return []
+        if film is None or len(film) != n or any(f is None for f in film):
+            raise ValueError(f"{who}: a model built with use_film=\"per_policy\" needs every policy's FiLM tensors (`film`)")
+        return [check_film_tensors(f, self._film_towers(), self.cfg.llm_dim, self.device, f"{who}: policy {s}") for s, f in enumerate(film)]
+
+    def set_adapter_slots(self, adapters: List[Dict[str, torch.Tensor]], *, lora_alpha: Optional[List[Optional[float]]] = None, film=None):
         """adapters[s]: policy s's LoRA tensors under the names lora_state_dict() / weights.load_lora_adapter use (`<linear>.lora_A.weight`,
         `.lora_B.weight`, un-fused per q/k/v and gate/up).  Allocates n = len(adapters) slots on every adapted linear and fills them; an empty
         list removes the slots.  The model must carry no merged or trainable adapters of its own; all policies must adapt the same linears with
-        one rank and one lora_alpha -- the model configuration's, whose alpha / r scales every slot's projection."""
+        one rank and one lora_alpha -- the model configuration's, whose alpha / r scales every slot's projection.
+        `film` (an engine built with use_film="per_policy": required; any other engine: refused): film[s] is policy s's FiLM tensors under
+        `vision_backbone.{featurizer,fused_featurizer}.blocks.{i}.{scale,shift}.{weight,bias}` for the towers' used blocks, exactly; they go to
+        slot s of the FiLM slot storage (FilmSlots) in bf16."""
         n = len(adapters)
         if n > MAX_SLOTS:
             raise ValueError(f"{n} policies: at most {MAX_SLOTS} adapter slots ride in one launch")
         if self.pool is not None:
             raise ValueError("set_adapter_slots: this engine's slots belong to its policy pool (pool_add / load_slot)")
         linears, adapted = self._check_adapters(adapters, lora_alpha)
+        film = self._check_film(film, n, "set_adapter_slots")   # every policy's FiLM tensors (a per-policy-FiLM engine), validated before anything changes
+        if self.film_per_policy:
+            self._alloc_film_slots(n)
+            for s in range(n):
+                self.film_slots.set_slot(s, film[s])
         cfg, plans = self.cfg, [adapted]
         for l in linears:
             l.clear_slots()
@@ -1157,7 +1274,7 @@ class VLAEngine:
         self.llm.slot_route = self.route if any(getattr(l, "n_slots", 0) for l in self.llm.linears()) else None
 
     # -- policy pool: any number of registered policies in device memory, `resident` of them in the slot storage -----------------------------
-    def init_policy_pool(self, resident: int, template_adapter: Dict[str, torch.Tensor], *, lora_alpha: Optional[float] = None):
+    def init_policy_pool(self, resident: int, template_adapter: Dict[str, torch.Tensor], *, lora_alpha: Optional[float] = None, film=None):
         """Allocates the slot storage for n = `resident` adapters on every linear that `template_adapter` adapts -- once: the slot count, and with
         it the K-extension width, the fixed schedules and every captured graph, stays what it is for the life of the model.  Empty slots hold
         zeros and no row is ever routed to one (policy_pool.Residency knows which are filled).  Registers nothing."""
@@ -1170,6 +1287,9 @@ class VLAEngine:
         linears, adapted = self._check_adapters([template_adapter], [lora_alpha])
         if not adapted:
             raise ValueError("init_policy_pool: the template adapter adapts no linear of this model")
+        self._check_film([film], 1, "init_policy_pool")   # (the template's FiLM tensors are validated, nothing of them is stored)
+        if self.film_per_policy:
+            self._alloc_film_slots(int(resident))
         for l in linears:
             if l.name in adapted:
                 l.init_slots(int(resident), self.cfg.lora_rank, self.route)
@@ -1181,9 +1301,10 @@ class VLAEngine:
         self._pool_adapted = adapted
         self._pool_tables: Dict[Tuple[str, int], dict] = {}
 
-    def pool_add(self, name: str, adapter: Dict[str, torch.Tensor], *, lora_alpha: Optional[float] = None, slot_pairs=None):
-        """Registers `name`: validated exactly as set_adapter_slots validates (rank, alpha, the pool's adapted set, stray tensors), then every
-        adapted linear's cat(lora_A) [G r, in] and cat(lora_B) [out, r] are stored in bf16 on the device.  `slot_pairs(s)` -> [(src, dst)]: further
+    def pool_add(self, name: str, adapter: Dict[str, torch.Tensor], *, lora_alpha: Optional[float] = None, slot_pairs=None, film=None):
+        """Registers `name`: validated exactly as set_adapter_slots validates (rank, alpha, the pool's adapted set, stray tensors, and on a
+        per-policy-FiLM engine its `film` tensors), then every adapted linear's cat(lora_A) [G r, in] and cat(lora_B) [out, r] -- and the FiLM
+        tensors -- are stored in bf16 on the device.  `slot_pairs(s)` -> [(src, dst)]: further
         tensors that belong to the policy and have to reach slot s with the adapters (the head's and the proprio projector's parameters)."""
         if self.pool is None:
             raise ValueError("pool_add: no policy pool (init_policy_pool)")
@@ -1192,6 +1313,7 @@ class VLAEngine:
         _, adapted = self._check_adapters([adapter], [lora_alpha])
         if adapted != self._pool_adapted:
             raise ValueError("the policies adapt different sets of linears")
+        film = self._check_film([film], 1, f"pool_add({name!r})")   # per-policy FiLM: checked, bf16, on the device
         dev, r = self.device, self.cfg.lora_rank
         tensors = {}
         for l in self._pool_linears:
@@ -1201,7 +1323,7 @@ class VLAEngine:
                 raise ValueError(f"{l.name}: adapter shapes {tuple(A.shape)} / {tuple(Bm.shape)} do not fit rank {r} "
                                  f"(want {(l.groups * r, l.in_f)} / {(l.out_f, r)})")
             tensors[l.name] = (A, Bm)
-        self.pool[name] = dict(tensors=tensors, slot_pairs=slot_pairs)
+        self.pool[name] = dict(tensors=tensors, slot_pairs=slot_pairs, film=None if film is None else film[0])
 
     def pool_remove(self, name: str):
         """Forgets `name`: its tensors and its cached copy tables are released, the slot it occupied (if any) is empty and stale."""
@@ -1221,6 +1343,8 @@ class VLAEngine:
             A, Bm = p["tensors"][l.name]
             pairs += [(A[g * r:(g + 1) * r], l.A_slots[slot_a_rows(g, s, n, r)]) for g in range(l.groups)]
             pairs.append((Bm, l.B_slots[:, s * r:(s + 1) * r]))
+        if p["film"] is not None:   # the policy's scale / shift Linears into slot s of every FiLM Linear: the same launch
+            pairs += self.film_slots.slot_pairs(s, p["film"])
         if p["slot_pairs"] is not None:
             pairs += list(p["slot_pairs"](s))
         return pairs
@@ -1242,8 +1366,10 @@ class VLAEngine:
         return tab
 
     def pool_bytes(self) -> int:
-        """Device bytes of the registered policies' adapter tensors (the slot storage itself belongs to the linears)."""
-        return sum(t.numel() * t.element_size() for p in (self.pool or {}).values() for ab in p["tensors"].values() for t in ab)
+        """Device bytes of the registered policies' adapter and FiLM tensors (the slot storage itself belongs to the linears / FilmSlots)."""
+        pols = list((self.pool or {}).values())
+        return sum(t.numel() * t.element_size() for p in pols for ab in p["tensors"].values() for t in ab) + \
+            sum(t.numel() * t.element_size() for p in pols for t in (p["film"] or {}).values())
 
     @contextlib.contextmanager
     def routing(self, obs_slot: torch.Tensor, host_slots=None):
@@ -1315,6 +1441,9 @@ class VLAEngine:
         The discarded last block of each tower is not held by this engine and is absent."""
         from .weights import vision_backbone_keys_to_reference
 
+        if self.film_per_policy:
+            raise RuntimeError("vision_backbone_state_dict: a per-policy-FiLM engine holds no FiLM Linears of its own (each policy's live in slot "
+                               "storage): there is no single wrapped backbone to export")
         sd = {**self.dino.export_frozen(), **self.siglip.export_frozen()}
         sd.update({k: v for k, v in self.export_trainable("data").items() if k.startswith("vision_backbone.")})
         return vision_backbone_keys_to_reference(sd)
@@ -1405,6 +1534,17 @@ class VLAEngine:
 
         # The towers are independent until the feature concat: SigLIP runs on a second HIP stream beside DINOv2, so the
         # tails of one tower's mid-sized GEMMs and its latency-bound small kernels overlap with the other's work.
+        if self.film_per_policy:
+            # every block's gamma / beta of both towers, each observation under its own policy's Linears: ONE launch on the current stream,
+            # ahead of the fork, so both tower streams are ordered behind it
+            if train:
+                raise RuntimeError("a per-policy-FiLM engine is inference-only: the FiLM Linears live in frozen slot storage, there is nothing to train")
+            if self.film_slots is None or self.route.obs_slot is None:
+                raise RuntimeError("per-policy FiLM: the forward must run inside engine.routing(obs_slot) on an engine with policies "
+                                   "(set_adapter_slots(..., film=[...]) or the policy pool): without an assignment no observation has FiLM Linears")
+            if self.route.n_obs != B or film_avg is None:
+                raise RuntimeError(f"per-policy FiLM: the route covers {self.route.n_obs} observations, the forward has {B}")
+            self.film_slots.launch(film_avg, self.route)
         side = self._side_stream()
         if side is not None:
             main = torch.cuda.current_stream(self.device)
@@ -1539,6 +1679,8 @@ class VLAEngine:
                     proprio_projector=None, noisy_action_projector=None, cached_patches=None, film_avg=None, sel=None):
         """Device-only part of forward(): ids / lab int64 [B, L] and text_lens int32 [B] already on the device; launches
         kernels and allocates, never synchronises or reads host memory -- the part a hipGraph can capture (ChunkGraph)."""
+        if train and self.film_per_policy:
+            raise RuntimeError("a per-policy-FiLM engine is inference-only: the FiLM Linears live in frozen slot storage, there is nothing to train")
         self.dropout.begin_forward(train)
         try:
             return self._forward_dev(ids, lab, text_lens, pixel_values, proprio, noisy_actions, timestep_emb, train, proprio_projector,
@@ -1814,7 +1956,9 @@ class ChunkGraph(_StaticInputs):
     `policies` (multi-policy serving, an engine with adapter slots): [(L1 head component or None, proprio projector component or None)] in slot
     order.  The graph then routes every slotted linear by the static `obs_slot` buffer that load(slots=...) writes, runs EVERY policy's head and
     proprio projector on all B observations and picks each observation's own with one ovla_select_by_slot each: the assignment is data, so one
-    capture serves every assignment of the same policy set."""
+    capture serves every assignment of the same policy set.  With `film=True` on a per-policy-FiLM engine the graph also holds the ragged
+    language average and the ONE ovla_film_vectors launch that turns it into every block's gamma / beta under each observation's own policy;
+    load(slots=...) rewrites only `obs_slot`."""
 
     def __init__(self, engine: "VLAEngine", B: int, L: int, pixel_shape, *, head=None, use_proprio: bool = True, proprio_projector=None,
                  invariant: bool = False, film: bool = False, discrete: bool = False, n_tokens: Optional[int] = None, n_bins: Optional[int] = None,
@@ -1825,8 +1969,11 @@ class ChunkGraph(_StaticInputs):
         if policies is not None:
             if len(policies) != engine.n_slots or not policies:
                 raise ValueError(f"ChunkGraph: {len(policies)} policies for an engine with {engine.n_slots} adapter slots")
-            if film or head is not None or proprio_projector is not None:
-                raise ValueError("ChunkGraph(policies=...): heads and proprio projectors come per policy; FiLM is not supported")
+            if head is not None or proprio_projector is not None:
+                raise ValueError("ChunkGraph(policies=...): heads and proprio projectors come per policy")
+            if film != engine.film_per_policy:
+                raise ValueError("ChunkGraph(policies=..., film=...): FiLM with per-request policies goes with an engine built with "
+                                 "use_film=\"per_policy\", and such an engine with film=True (its own FiLM Linears serve one policy)")
             self.slot_heads = [h for h, _ in policies] if all(h is not None for h, _ in policies) else None
             self.obs_slot = torch.zeros(B, dtype=torch.int32, device=dev)
             if use_proprio:

@@ -59,10 +59,12 @@ def platform_model_config(model_config: VLAConfig = OPENVLA_7B, num_images: Opti
     return dataclasses.replace(model_config, **kw)
 
 
-def get_vla(cfg: Any, model_config: VLAConfig = OPENVLA_7B) -> OpenVLAForActionPrediction:
+def get_vla(cfg: Any, model_config: VLAConfig = OPENVLA_7B, *, film_per_policy: bool = False) -> OpenVLAForActionPrediction:
     """Loads the HF-layout checkpoint shards of `cfg.pretrained_checkpoint` (safetensors) into the HIP engine.  Action / proprio
     dimensions and the un-normalisation rule follow prismatic.vla.constants (the active platform), like get_action_head /
-    get_proprio_projector / normalize_proprio below and finetune()."""
+    get_proprio_projector / normalize_proprio below and finetune().
+    `film_per_policy` (with cfg.use_film): a BASE model for multi-policy serving -- no FiLM backbone checkpoint is read, the towers carry FiLM
+    slot storage (OpenVLAForActionPrediction(use_film="per_policy")) and every get_policy brings its fine-tune's scale / shift Linears."""
     model_config = platform_model_config(model_config, getattr(cfg, "num_images_in_input", None))
     ckpt = Path(cfg.pretrained_checkpoint)
     if not ckpt.is_dir():
@@ -75,9 +77,9 @@ def get_vla(cfg: Any, model_config: VLAConfig = OPENVLA_7B) -> OpenVLAForActionP
     if not sd:
         raise ValueError(f"no *.safetensors shards in {ckpt}")
     use_film = bool(getattr(cfg, "use_film", False))
-    if use_film:
+    if use_film and not film_per_policy:
         sd.update(_film_vision_backbone(cfg, model_config))
-    vla = OpenVLAForActionPrediction(model_config, sd, device=DEVICE, use_film=use_film)
+    vla = OpenVLAForActionPrediction(model_config, sd, device=DEVICE, use_film="per_policy" if use_film and film_per_policy else use_film)
     vla.vision_backbone.set_num_images_in_input(cfg.num_images_in_input)
     stats = ckpt / "dataset_statistics.json"
     if stats.is_file():                                                     # openvla_utils.py:352-377
@@ -127,14 +129,24 @@ def get_policy(cfg: Any, vla: OpenVLAForActionPrediction, name: str, checkpoint_
     """Registers the fine-tune output directory `checkpoint_dir` (finetune.py:584-675: `lora_adapter/`, `action_head--*_checkpoint.pt`,
     `proprio_projector--*_checkpoint.pt`, `dataset_statistics.json`) as policy `name` of the base model `vla` (vla.add_policy), read with the
     loaders above.  The head is loaded when cfg.use_l1_regression, the proprio projector when cfg.use_proprio; without a head the policy uses
-    the discrete token path.  Returns vla."""
-    from ...weights import load_lora_adapter
+    the discrete token path.  With cfg.use_film (a base model built with use_film="per_policy") the directory's
+    `vision_backbone--*_checkpoint.pt` is read as the reference's FiLM evaluation path reads it (openvla_utils.py:311-349) and ONLY its scale /
+    shift tensors are taken, as the policy's `film`; the adapters come from `lora_adapter/` as before.  Returns vla."""
+    from ...weights import load_lora_adapter, vision_backbone_keys_from_reference
 
     d = Path(checkpoint_dir)
     if not d.is_dir():
         raise ValueError(f"`{d}` is not a fine-tune output directory")
-    if getattr(cfg, "use_diffusion", False) or getattr(cfg, "use_film", False):
-        raise ValueError("get_policy: diffusion heads and FiLM are not supported for per-request policies")
+    if getattr(cfg, "use_diffusion", False):
+        raise ValueError("get_policy: diffusion heads are not supported for per-request policies")
+    film = None
+    if getattr(cfg, "use_film", False):
+        part = vision_backbone_keys_from_reference(load_component_state_dict(find_checkpoint_file(str(d), "vision_backbone")))
+        eng = vla.engine
+        unused = tuple(f"{t.prefix}blocks.{t.vc.depth - 1}." for t in (eng.dino, eng.siglip))   # each tower's last block is never run
+        film = {k: v for k, v in part.items() if (".scale." in k or ".shift." in k) and not k.startswith(unused)}
+        if not film:
+            raise ValueError(f"policy {name!r}: the vision_backbone checkpoint in `{d}` holds no FiLM scale / shift tensors")
     lora, acfg = load_lora_adapter(d / "lora_adapter")
     if acfg.get("r") is not None and int(acfg["r"]) != vla.cfg.lora_rank:
         raise ValueError(f"policy {name!r}: adapter rank {acfg['r']} differs from the model configuration's {vla.cfg.lora_rank}")
@@ -144,7 +156,7 @@ def get_policy(cfg: Any, vla: OpenVLAForActionPrediction, name: str, checkpoint_
     pp = get_proprio_projector(sub, vla.llm_dim, C.PROPRIO_DIM) if getattr(cfg, "use_proprio", False) else None
     stats = d / "dataset_statistics.json"
     norm_stats = json.loads(stats.read_text()) if stats.is_file() else None
-    return vla.add_policy(name, lora, action_head=head, proprio_projector=pp, norm_stats=norm_stats, lora_alpha=acfg.get("lora_alpha"))
+    return vla.add_policy(name, lora, action_head=head, proprio_projector=pp, norm_stats=norm_stats, lora_alpha=acfg.get("lora_alpha"), film=film)
 
 
 class PrismaticProcessor:

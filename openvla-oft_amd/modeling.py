@@ -365,7 +365,11 @@ class OpenVLAForActionPrediction(_StoreModule):
     """prismatic/extern/hf/modeling_prismatic.py:720-1087 over the HIP engine."""
 
     def __init__(self, cfg: VLAConfig, state_dict: Dict[str, torch.Tensor], *, device=None, lora: Optional[bool] = None,
-                 norm_stats: Optional[dict] = None, use_film: Optional[bool] = None, lora_dropout: float = 0.0, dropout_seed: int = 0):
+                 norm_stats: Optional[dict] = None, use_film=None, lora_dropout: float = 0.0, dropout_seed: int = 0):
+        """`use_film`: None (True iff the state dict carries FiLM scale / shift Linears), False, True (the model's own FiLM Linears, trained and
+        evaluated as the reference's FiLMedPrismaticVisionBackbone), or "per_policy": a BASE model for multi-policy serving whose towers carry
+        FiLM slot storage and no FiLM Linears of their own -- every add_policy brings its `film` tensors, every observation of
+        predict_action_batch(policy=[...]) is modulated by its own policy's.  Inference only."""
         self.cfg = cfg
         self.device = _device(device)
         get, has = make_getter(state_dict, self.device)
@@ -402,12 +406,17 @@ class OpenVLAForActionPrediction(_StoreModule):
 
     # -- several fine-tuned policies on one base model ------------------------------------------------------------------------------------
     @property
+    def film_per_policy(self) -> bool:
+        """True for a base model built with use_film="per_policy": every policy brings its own FiLM Linears."""
+        return bool(getattr(self.engine, "film_per_policy", False))
+
+    @property
     def policies(self) -> Tuple[str, ...]:
         """Names of the registered policies, in adapter-slot order."""
         return tuple(self._policies)
 
     def add_policy(self, name: str, lora_state_dict: Dict[str, torch.Tensor], *, action_head=None, proprio_projector=None,
-                   norm_stats: Optional[dict] = None, lora_alpha: Optional[float] = None):
+                   norm_stats: Optional[dict] = None, lora_alpha: Optional[float] = None, film: Optional[Dict[str, torch.Tensor]] = None):
         """Registers one fine-tune's outputs (finetune.py:584-675: `lora_adapter/`, `action_head--*.pt`, `proprio_projector--*.pt`,
         `dataset_statistics.json`) as a policy of this BASE model: its adapters go into the next adapter slot of every adapted linear
         (engine.set_adapter_slots; tensor names as lora_state_dict() emits and weights.load_lora_adapter returns), its L1 head, proprio projector
@@ -418,21 +427,31 @@ class OpenVLAForActionPrediction(_StoreModule):
         Every policy's adapter tensors stay referenced on the host and each call refills all slots of all linears (the slot count changed): with
         at most 4 policies that is a handful of copies per linear, done once at registration.
         After enable_policy_pool: no limit on the number of policies, the slot count stays the pool's `resident`, nothing is reallocated and no
-        captured graph is dropped; the policy's tensors go to device memory (engine.pool_add) and reach a slot when a batch needs them."""
+        captured graph is dropped; the policy's tensors go to device memory (engine.pool_add) and reach a slot when a batch needs them.
+        `film`: the policy's FiLM scale / shift Linears (the scale / shift tensors of its `vision_backbone--*_checkpoint.pt`) under the engine's
+        names `vision_backbone.{featurizer,fused_featurizer}.blocks.{i}.{scale,shift}.{weight,bias}`, for exactly the towers' used blocks.
+        Required for every policy of a model built with use_film="per_policy", refused on any other model.  A refused policy changes nothing."""
         if not isinstance(name, str) or not name:
             raise ValueError("add_policy: the policy name must be a non-empty string")
         if name in self._policies:
             raise ValueError(f"add_policy: a policy named {name!r} is already registered")
         if action_head is not None and hasattr(action_head, "noise_scheduler"):
             raise ValueError("add_policy: per-policy diffusion heads are not supported (L1 head, or none for the discrete token path)")
-        pol = dict(lora=dict(lora_state_dict), head=action_head, pp=proprio_projector, norm_stats=norm_stats, lora_alpha=lora_alpha)
+        if film is not None and not self.film_per_policy:
+            raise ValueError("add_policy: `film` was given, but the model was not built with use_film=\"per_policy\" (a model without FiLM has no "
+                             "place for FiLM tensors; a model with its own FiLM Linears serves one policy)")
+        if film is None and self.film_per_policy:
+            raise ValueError("add_policy: a model built with use_film=\"per_policy\" needs every policy's FiLM tensors (`film`)")
+        pol = dict(lora=dict(lora_state_dict), head=action_head, pp=proprio_projector, norm_stats=norm_stats, lora_alpha=lora_alpha,
+                   film=None if film is None else dict(film))
         pols = list(self._policies.values()) + [pol]
         for what in ("head", "pp"):
             if len({p[what] is None for p in pols}) > 1:
                 raise ValueError(f"add_policy: either every policy brings its own {'action head' if what == 'head' else 'proprio projector'} or none does")
         if self._pool_resident:
             return self._pool_add_policy(name, pol)
-        self.engine.set_adapter_slots([p["lora"] for p in pols], lora_alpha=[p["lora_alpha"] for p in pols])   # validates before it changes anything
+        self.engine.set_adapter_slots([p["lora"] for p in pols], lora_alpha=[p["lora_alpha"] for p in pols],
+                                      film=[p["film"] for p in pols] if self.film_per_policy else None)   # validates before it changes anything
         self._policies[name] = pol
         self._policy_gen += 1
         for k in [k for k in self._graphs if "policies" in k]:   # captured against the previous slot storage
@@ -486,7 +505,7 @@ class OpenVLAForActionPrediction(_StoreModule):
                 if mod is not None and self._store_layout(mod) != self._store_layout(slots[0]):
                     raise ValueError(f"add_policy: the {what} of {name!r} has other shapes than the pool's (one head / projector shape per pool)")
         else:
-            eng.init_policy_pool(self._pool_resident, pol["lora"], lora_alpha=pol["lora_alpha"])   # validates before it allocates
+            eng.init_policy_pool(self._pool_resident, pol["lora"], lora_alpha=pol["lora_alpha"], film=pol["film"])   # validates before it allocates
             R = self._pool_resident
             if head is not None:
                 sd, c = head.state_dict(), head.cfg
@@ -501,8 +520,8 @@ class OpenVLAForActionPrediction(_StoreModule):
             return (self._param_pairs(head, self._slot_heads[s]) if head is not None else []) + \
                    (self._param_pairs(pp, self._slot_pps[s]) if pp is not None else [])
 
-        eng.pool_add(name, pol["lora"], lora_alpha=pol["lora_alpha"], slot_pairs=slot_pairs)
-        self._policies[name] = dict(pol, lora=None)   # the pool holds the adapters on the device: no host reference is kept
+        eng.pool_add(name, pol["lora"], lora_alpha=pol["lora_alpha"], slot_pairs=slot_pairs, film=pol["film"])
+        self._policies[name] = dict(pol, lora=None, film=None)   # the pool holds the adapters (and FiLM tensors) on the device: no host reference is kept
         return self
 
     def remove_policy(self, name: str):
@@ -804,8 +823,11 @@ class OpenVLAForActionPrediction(_StoreModule):
         `policy` (a model with add_policy): one registered policy name per observation.  Each observation runs under its own policy's LoRA
         adapters (all of them in the same launches: engine.LoraLinear adapter slots), L1 head, proprio projector and un-normalisation statistics
         (`unnorm_key` is looked up in the policy's own norm_stats when it has them); without per-policy heads the discrete token path with the
-        shared lm_head.  `pad_to` repeats observation 0's policy.  FiLM models and diffusion heads are not supported with `policy`."""
+        shared lm_head.  `pad_to` repeats observation 0's policy.  On a model built with use_film="per_policy" (pass use_film=True) each observation's
+        towers are modulated by its own policy's FiLM Linears (one ovla_film_vectors launch per forward), and `policy` is required.  A model with
+        its own FiLM Linears and diffusion heads are not supported with `policy`."""
         cfg = self.cfg
+        per_policy_film = bool(getattr(self.engine, "film_per_policy", False))
         if use_film != self.engine.use_film:
             raise ValueError(f"use_film={use_film} but the model was built with use_film={self.engine.use_film}")
         B, A = len(prompts), cfg.num_action_tokens
@@ -813,10 +835,16 @@ class OpenVLAForActionPrediction(_StoreModule):
             raise ValueError("predict_action_batch: no observations")
         if pixel_values.shape[0] != B:
             raise ValueError(f"predict_action_batch: {B} prompts but pixel_values holds {pixel_values.shape[0]} observations")
+        if policy is None and per_policy_film:
+            raise ValueError("predict_action_batch: a model built with use_film=\"per_policy\" has no FiLM Linears of its own: name each "
+                             "observation's policy (policy=[...])")
         if policy is not None:
             policy = list(policy)
-            if self.engine.use_film or noisy_action_projector is not None or hasattr(action_head, "noise_scheduler"):
-                raise ValueError("predict_action_batch(policy=...): FiLM models and diffusion heads are not supported with per-request policies")
+            if self.engine.use_film and not per_policy_film:
+                raise ValueError("predict_action_batch(policy=...): a model with its own FiLM Linears serves one policy; per-request policies with FiLM "
+                                 "need a base model built with use_film=\"per_policy\" (add_policy(..., film=...))")
+            if noisy_action_projector is not None or hasattr(action_head, "noise_scheduler"):
+                raise ValueError("predict_action_batch(policy=...): diffusion heads are not supported with per-request policies")
             if action_head is not None or proprio_projector is not None:
                 raise ValueError("predict_action_batch(policy=...): the action head and the proprio projector come from each observation's policy")
             if len(policy) != B:

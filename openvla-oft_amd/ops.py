@@ -825,6 +825,51 @@ def select_by_slot(src, obs_slot, *, rows_per_obs, rows=None, out=None, host_slo
     return out
 
 
+FILM_ITEM_COLS = 4   # OVLA_FILM_ITEM_COLS (ovla.h)
+FILM_MAX_OBS = 64    # OVLA_FILM_MAX_OBS
+
+
+def film_table(linears, device):
+    """The descriptor table of ovla_film_vectors from [(W_slots bf16 [n, out_f, D], b_slots bf16 [n, out_f], out bf16 [rows, out_f])], built once
+    per slot allocation (the tensors never move: the table keeps them).  Table order = list order; item_start is the running sum of
+    ceil(out_f / FILM_ITEM_COLS).  -> dict(table (device bytes), host (the ctypes array), n_linears, n, D, rows)."""
+    T = STRUCTS["ovla_film_linear"]
+    assert linears, "film_table: no linears"
+    n, _, D = linears[0][0].shape
+    rows = min(o.shape[0] for _, _, o in linears)
+    arr = (T * len(linears))()
+    start = 0
+    for j, (W, b, out) in enumerate(linears):
+        _chk(W, name="W_slots"); _chk(b, name="b_slots"); _chk(out, name="out")
+        out_f = W.shape[1]
+        assert W.shape == (n, out_f, D) and b.shape == (n, out_f) and out.dim() == 2 and out.shape[1] == out_f
+        assert W.is_contiguous() and b.is_contiguous() and out.is_contiguous()
+        arr[j].W, arr[j].bias, arr[j].out, arr[j].out_f, arr[j].item_start = W.data_ptr(), b.data_ptr(), out.data_ptr(), out_f, start
+        start += (out_f + FILM_ITEM_COLS - 1) // FILM_ITEM_COLS
+    raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
+    return dict(table=raw, host=arr, n_linears=len(linears), n=n, D=D, rows=rows, keep=list(linears))
+
+
+def film_vectors(tab, avg, obs_slot, *, host_slots=None):
+    """Per-policy FiLM vectors, ONE launch on the current stream (ovla.h: ovla_film_vectors): for every linear of `tab` (film_table) and every
+    observation b < n_obs, out[b] = bf16(bias[slot(b)] + W[slot(b)] . avg[b]).  avg bf16 [>= n_obs, D] (unit inner stride); obs_slot device
+    int32 [n_obs]; host_slots (optional, the same values on the host): an entry outside [0, n) raises before anything is launched."""
+    _chk(avg, name="avg"); _chk(obs_slot, torch.int32, "obs_slot")
+    assert avg.dim() == 2 and avg.stride(1) == 1 and avg.shape[1] == tab["D"] and obs_slot.is_contiguous()
+    n_obs = obs_slot.numel()
+    assert n_obs <= avg.shape[0] and n_obs <= tab["rows"], "film_vectors: more observations than avg / out rows"
+    hs = _host_slots(obs_slot, host_slots)
+    g = STRUCTS["ovla_film_vectors_args"]()
+    g.table, g.table_host = tab["table"].data_ptr(), ctypes.cast(tab["host"], ctypes.c_void_p).value
+    g.avg, g.ld_avg, g.obs_slot = avg.data_ptr(), avg.stride(0), obs_slot.data_ptr()
+    g.obs_slot_host = ctypes.cast(hs, ctypes.c_void_p).value if hs is not None else None
+    g.n_linears, g.n_obs, g.n, g.D = tab["n_linears"], n_obs, tab["n"], tab["D"]
+    e0 = _prof_begin()
+    _lib.call("ovla_film_vectors", g, _stream())
+    _prof_end(e0, "film_vectors", 2.0 * n_obs * tab["D"] * sum(W.shape[1] for W, _, _ in tab["keep"]))
+    return tab
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 def _dropout_key(g, modules, p, seed, call):
     """The mask-contract fields shared by the three LoRA-dropout argument structs (ovla.h "LoRA dropout")."""

@@ -28,6 +28,10 @@ Differences, all deliberate:
     needs them.  The coalescer then forms batches of at most that many distinct policies (key_fn / max_keys), so a coalesced forward never
     splits; an `/act_batch` group that names more is split into passes by predict_action_batch.  At 0 (the default) nothing changes: at most
     4 policies, registered once.
+  * `policies` with `use_film` (not in the reference): the base model is built with use_film="per_policy" (get_vla(cfg, film_per_policy=True)) -- or
+    handed in built that way -- and every policy brings its own FiLM scale / shift Linears (get_policy reads them from the fine-tune's
+    vision-backbone checkpoint; a dict spec passes `film=`).  Payloads name their policy as above; one routed launch per forward gives each
+    observation its own policy's FiLM.
 """
 from __future__ import annotations
 
@@ -115,8 +119,12 @@ class DeployConfig:
 class OpenVLAServer:
     def __init__(self, cfg, *, vla=None, processor=None, action_head=None, proprio_projector=None, noisy_action_projector=None, policies=None):
         self.cfg = cfg
-        self.vla = vla if vla is not None else U.get_vla(cfg)
         self.policies = tuple(policies) if policies else ()
+        film_policies = bool(self.policies) and bool(getattr(cfg, "use_film", False))   # every policy brings its own FiLM Linears
+        self.vla = vla if vla is not None else U.get_vla(cfg, film_per_policy=film_policies)
+        if film_policies and not getattr(self.vla, "film_per_policy", False):
+            raise ValueError("OpenVLAServer(policies=...) with cfg.use_film needs a base model built with use_film=\"per_policy\" "
+                             "(a model with its own FiLM Linears serves one policy)")
         resident = int(getattr(cfg, "resident_policies", 0) or 0)
         if resident > 0 and not getattr(self.vla, "policy_pool_resident", 0):
             self.vla.enable_policy_pool(resident)   # before the first add_policy: the slot count is fixed from there on
