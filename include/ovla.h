@@ -669,6 +669,44 @@ int ovla_ddim_prepare(const ovla_ddim_prepare_args* a, void* stream);
 typedef struct { float* sample; const void* eps; const float* coef; int32_t* step; int32_t n_steps, n; } ovla_ddim_step_args;
 int ovla_ddim_step(const ovla_ddim_step_args* a, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Diffusion noise (DiffusionActionHead.sample_noisy_actions, prismatic/models/action_heads.py:167-197: per training batch N(0, 1) noise of
+ * the chunk's shape, one uniform timestep per sample, noise_scheduler.add_noise, the sinusoidal timestep embedding).  ONE launch draws all
+ * four for B samples of n = chunk * action_dim elements; nothing comes from or goes to the host, and the position of the stream is the
+ * 32-bit `call` the caller advances once per draw and checkpoints.  THE NOISE CONTRACT (identical in csrc/diffusion_noise.hip and in the
+ * numpy restatement tests/diffusion_noise_reference.py); every output is a pure function of (seed, call, stream, sample b, element i):
+ *   generator   Philox4x32-10 as in "LoRA dropout" above: counter (c0, c1, c2, c3), key (seed_lo, seed_hi).
+ *   streams     c2 = stream: 0 training noise, 1 the timestep draw, 2 the sampler's start noise.  The `stream` argument selects the NOISE stream
+ *               and must be 0 or 2; 1 is refused (the timestep draw always uses it), so is every other value.
+ *   timestep    o = philox(0, b, 1, call);  t_b = umulhi(o[0], T) = floor(o[0] * T / 2^32) in [0, T);  timesteps[b] = t_b.
+ *   embedding   temb[b, :] = temb_table[t_b, :], an exact copy (temb_table bf16 [T, D] contiguous: the host's time encoder of float(t) rounded
+ *               to bf16, row by row).
+ *   noise       elements 4 j .. 4 j + 3 of sample b come from o = philox(j, b, stream, call): two Box-Muller pairs in fp32,
+ *               (o[0], o[1]) -> elements 4 j, 4 j + 1 and (o[2], o[3]) -> 4 j + 2, 4 j + 3.  For a pair (w_a, w_b):
+ *                   u1 = ((w_a >> 8) + 1) * 2^-24 in (0, 1],   u2 = (w_b >> 8) * 2^-24 in [0, 1)        (both exact in fp32)
+ *                   r = sqrtf(-2 logf(u1)),   z_even = r * cos(2 pi u2),   z_odd = r * sin(2 pi u2)
+ *               with cos / sin of 2 pi u2 evaluated as sincospif(2 u2) (exact argument reduction).  |z| <= sqrt(48 ln 2) = 5.77.
+ *               noise[b, i] = bf16_rne(z_i).  A tail (n % 4 != 0) discards the unused values of the last call.
+ *   noisy       noisy[b, i] = bf16_rne(ab[t_b][0] * float(actions[b, i]) + ab[t_b][1] * float(noise[b, i])): add_noise in fp32 on the bf16-rounded
+ *               noise, two multiplies and one add each rounded on its own (no FMA contraction).  ab fp32 [T, 2] contiguous, row t =
+ *               (alphas_cumprod[t]^1/2, (1 - alphas_cumprod[t])^1/2) built by the host with the scheduler's own expressions.
+ *   indexing    b and i are the logical sample and element; nothing depends on B, on a row stride or on launch geometry.
+ * actions / noise / noisy bf16 [B, n] and temb bf16 [B, D] each with its own row stride in elements (>= n, >= D; elements past a row's
+ * extent are neither read nor written); timesteps int32 [B].  Stream-ordered and capturable, no atomics, no workspace; launches nothing on
+ * OVLA_EINVAL. */
+typedef struct {
+  const void* actions; int64_t ld_actions;
+  const float* ab;                   /* fp32 [T, 2] */
+  const void* temb_table;            /* bf16 [T, D] */
+  void* noise; int64_t ld_noise;
+  void* noisy; int64_t ld_noisy;
+  void* temb; int64_t ld_temb;
+  int32_t* timesteps;
+  uint32_t seed_lo, seed_hi, call, stream;
+  int32_t B, n, D, T;
+} ovla_diffusion_noise_args;
+int ovla_diffusion_noise(const ovla_diffusion_noise_args* a, void* stream);
+
 /* fp32 -> bf16 convert with scale (publishes .grad views), and fill */
 typedef struct { const float* src; void* dst; int64_t n; float scale; } ovla_cvt_args;
 int ovla_cvt_f32_to_bf16(const ovla_cvt_args* a, void* stream);

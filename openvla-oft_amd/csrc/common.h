@@ -96,6 +96,23 @@ OVLA_DEV float ln_affine(float x, float mean, float rstd, float w, float b) { re
 // multi-policy serving: the adapter slot an observation is routed to, read from a device array and clamped, so that no index formed from it leaves a buffer
 OVLA_DEV int clamp_slot(int s, int n) { return s < 0 ? 0 : (s >= n ? n - 1 : s); }
 
+// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11): counter c, key k -> four 32-bit words.  The one
+// generator of the library: the lora_dropout masks (lora_dropout.hip) and the diffusion noise (diffusion_noise.hip) are functions of its output.
+OVLA_DEV void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t (&o)[4]) {
+#pragma unroll
+  for (int round = 0; round < 10; ++round) {
+    const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+    const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+    c0 = h1 ^ c1 ^ k0;
+    c1 = l1;
+    c2 = h0 ^ c3 ^ k1;
+    c3 = l0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
+}
+
 OVLA_DEV float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -16,23 +16,7 @@ struct MaskKey {
   float inv;
 };
 
-// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11): counter c, key k -> four 32-bit words.
-OVLA_DEV void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t (&o)[4]) {
-#pragma unroll
-  for (int round = 0; round < 10; ++round) {
-    const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-    const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-    c0 = h1 ^ c1 ^ k0;
-    c1 = l1;
-    c2 = h0 ^ c3 ^ k1;
-    c3 = l0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
-}
-
-// The 8 keep bits of the vector that starts at column k (k % 8 == 0) of row m of a [*, K] matrix: bit e = column k + e is kept.
+// The 8 keep bits (generator: common.h philox4x32_10) of the vector that starts at column k (k % 8 == 0) of row m of a [*, K] matrix: bit e = column k + e is kept.
 OVLA_DEV uint32_t keep_bits(const MaskKey& mk, uint32_t module, int m, int k, int K) {
   const uint64_t q = (uint64_t)m * (uint64_t)(K >> 3) + (uint64_t)(k >> 3);
   uint32_t o[4];

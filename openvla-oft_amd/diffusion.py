@@ -68,6 +68,12 @@ class DDIMScheduler:
             rows.append(torch.stack([(1 - a_t) ** 0.5, a_t ** 0.5, a_prev ** 0.5, (1 - a_prev) ** 0.5]))
         return torch.stack(rows).to(torch.float32).contiguous()
 
+    def add_noise_coefficients(self) -> torch.Tensor:
+        """fp32 [num_train_timesteps, 2]: per training timestep the two factors of `add_noise`, (alphas_cumprod[t]^1/2,
+        (1 - alphas_cumprod[t])^1/2), from its very expressions -- the table ovla_diffusion_noise reads (ops.diffusion_noise)."""
+        ac = self.alphas_cumprod
+        return torch.stack([ac ** 0.5, (1 - ac) ** 0.5], dim=1).to(torch.float32).contiguous()
+
 
 class SinusoidalPositionalEncoding:
     def __init__(self, dim: int):

@@ -215,6 +215,32 @@ class DropoutState:
         self.active = False
 
 
+class DiffusionNoiseState:
+    """The engine-level state of the diffusion objective's device noise (ovla.h "Diffusion noise"): 64-bit seed, the 32-bit `call` counter that
+    advances once per draw (VLAEngine.draw_diffusion) and is checkpointed with the optimizer state, and the device tables of the head's T
+    training timesteps -- `ab` / `temb_table` for ovla_diffusion_noise, `coef` / `step_temb` (rows in the sampler's order) for the DDIM loop of
+    VLAEngine.sample_actions.  The tables are the host scheduler's and time encoder's own numbers, built once."""
+
+    def __init__(self, num_diffusion_steps: int, seed: int = 0):
+        if int(num_diffusion_steps) < 1:
+            raise ValueError(f"num_diffusion_steps = {num_diffusion_steps}")
+        self.T, self.seed, self.call = int(num_diffusion_steps), int(seed) & 0xFFFFFFFFFFFFFFFF, 0
+        self.ab = self.temb_table = self.coef = self.step_temb = None
+
+    def tables(self, D: int, device):
+        if self.ab is None:
+            from .diffusion import DDIMScheduler, SinusoidalPositionalEncoding
+
+            sched, enc = DDIMScheduler(num_train_timesteps=self.T), SinusoidalPositionalEncoding(D)
+            sched.set_timesteps(self.T)
+            rows = [enc(torch.tensor([float(t)])).to(BF16).reshape(1, D) for t in range(self.T)]   # row t: what the host path encodes for timestep t
+            self.ab = sched.add_noise_coefficients().to(device)
+            self.temb_table = torch.cat(rows).contiguous().to(device)
+            self.coef = sched.step_coefficients().to(device)
+            self.step_temb = torch.cat([rows[int(t)] for t in sched.timesteps]).contiguous().to(device)
+        return self
+
+
 class SlotProjectors:
     """Every registered policy's proprio projector on all B observations, then each observation's own row (ovla_select_by_slot): n small
     forwards instead of data-dependent grouping, which a captured graph could not hold.  Quacks like MlpProjector.fwd for patches_dev."""
@@ -1095,10 +1121,14 @@ class VLAEngine:
     (see weights.py for the state-dict naming)."""
 
     def __init__(self, cfg: VLAConfig, get, device, *, lora: bool = True, use_proprio: bool = True, head: str = "l1", use_film: bool = False,
-                 has=None, lora_dropout: float = 0.0, dropout_seed: int = 0):
+                 has=None, lora_dropout: float = 0.0, dropout_seed: int = 0, num_diffusion_steps: Optional[int] = None, diffusion_seed: int = 0):
         if head not in ("l1", "diffusion", "none"):
             raise ValueError(head)
         self.dropout = DropoutState(lora_dropout, dropout_seed)
+        # device noise of the diffusion objective (draw_diffusion / sample_actions): only an engine told the head's T carries the state
+        if num_diffusion_steps is not None and head != "diffusion":
+            raise ValueError("num_diffusion_steps belongs to the diffusion head")
+        self.diffusion = DiffusionNoiseState(num_diffusion_steps, diffusion_seed) if num_diffusion_steps is not None else None
         ops.check_device(device.index or 0)
         self.cfg, self.device, self.lora = cfg, device, lora
         self.route, self.n_slots = SlotRoute(), 0   # multi-policy serving (set_adapter_slots / routing)
@@ -1491,11 +1521,15 @@ class VLAEngine:
                 out[f"store{i}.{tag}.exp_avg"] = st.exp_avg[dt]
                 out[f"store{i}.{tag}.exp_avg_sq"] = st.exp_avg_sq[dt]
         out["lora_dropout.call"] = torch.tensor([self.dropout.call], dtype=torch.int64)   # the mask stream's position: a resumed run draws the masks the uninterrupted one would
+        if self.diffusion is not None:   # ... and the noise and timesteps the uninterrupted one would
+            out["diffusion_noise.call"] = torch.tensor([self.diffusion.call], dtype=torch.int64)
         return out
 
     def load_optimizer_state_dict(self, sd: Dict[str, torch.Tensor]):
         if "lora_dropout.call" in sd:
             self.dropout.call = int(sd["lora_dropout.call"].item()) & 0xFFFFFFFF
+        if "diffusion_noise.call" in sd and self.diffusion is not None:
+            self.diffusion.call = int(sd["diffusion_noise.call"].item()) & 0xFFFFFFFF
         for i, st in enumerate(self.stores):
             if not st.exp_avg:
                 st.init_optimizer()
@@ -1831,6 +1865,68 @@ class VLAEngine:
         target = tgt_src.to(self.device, BF16).reshape(B * cfg.chunk, cfg.action_dim).contiguous()
         pred, loss_sum, _ = self.head.fwd(ah, target=target, mse=diffusion is not None, train=False)
         return loss_sum, pred.numel(), pred
+
+    # -- the diffusion objective on the device ------------------------------------------------------------------------------
+    def _diffusion_state(self, who: str) -> DiffusionNoiseState:
+        if self.diffusion is None or self.head is None or self.noisy is None:
+            raise RuntimeError(f"{who} needs an engine built with head='diffusion' and num_diffusion_steps")
+        return self.diffusion.tables(self.cfg.llm_dim, self.device)
+
+    def _actions_dev(self, actions) -> torch.Tensor:
+        """Ground-truth chunks bf16 [B, chunk * action_dim] on the device; a host tensor goes up from pinned memory without blocking."""
+        B = actions.shape[0]
+        if not actions.is_cuda:
+            a = actions.to(BF16).reshape(B, -1).contiguous()
+            return a.pin_memory().to(self.device, non_blocking=True) if _ASYNC_UPLOAD else a.to(self.device)
+        return actions.to(self.device, BF16).reshape(B, -1)
+
+    def draw_diffusion(self, actions) -> Dict[str, torch.Tensor]:
+        """DiffusionActionHead.sample_noisy_actions (action_heads.py:167-197) in one launch on the device: the `diffusion` argument of
+        train_step_fwd_bwd / eval_step -- dict(noise, noisy_actions bf16 [B, chunk, action_dim], timestep_emb bf16 [B, D], timesteps int32 [B]),
+        all device tensors, a pure function of (seed, call) by ovla.h "Diffusion noise".  Advances `call` by one; reads nothing back."""
+        st = self._diffusion_state("draw_diffusion")
+        a = self._actions_dev(actions)
+        shape = (a.shape[0], self.cfg.chunk, self.cfg.action_dim)
+        noise, noisy, temb, ts = ops.diffusion_noise(a, st.ab, st.temb_table, seed=st.seed, call=st.call, stream=0)
+        st.call = (st.call + 1) & 0xFFFFFFFF
+        return dict(noise=noise.view(shape), noisy_actions=noisy.view(shape), timestep_emb=temb, timesteps=ts)
+
+    def sample_actions(self, batch: dict, start_noise=None) -> torch.Tensor:
+        """The reverse diffusion of a whole batch (finetune.py:454-540, the sampled-L1 metrics of the diffusion objective) as eager launches with
+        no host round trip: per DDIM step ovla_ddim_prepare, the forward on the cached patches, the noise-predicting head, ovla_ddim_step; the
+        step index and the sample live on the device (DiffusionGraph's step, uncaptured), the rounding points are those of the host loop of
+        OpenVLAForActionPrediction._infer.  Inference mode (no dropout, adapters unmerged), no gradients.  Start noise: `start_noise`
+        [B, chunk, action_dim], else stream 2 of the noise generator at the current `call` (not advanced: every draw_diffusion moves it on).
+        -> bf16 [B, chunk, action_dim] on the device."""
+        st = self._diffusion_state("sample_actions")
+        cfg, dev = self.cfg, self.device
+        B = batch["input_ids"].shape[0]
+        n = B * cfg.chunk * cfg.action_dim
+        with torch.no_grad():
+            if start_noise is None:
+                zeros = torch.zeros((B, cfg.chunk * cfg.action_dim), dtype=BF16, device=dev)
+                start = ops.diffusion_noise(zeros, st.ab, st.temb_table, seed=st.seed, call=st.call, stream=2)[0]
+            else:
+                start = torch.as_tensor(start_noise).to(BF16).to(dev)
+            assert start.numel() == n, f"start noise of {start.numel()} elements for {n}"
+            sample = start.reshape(-1).to(F32).contiguous()       # bf16-rounded values held in fp32, as the host loop holds them
+            step = torch.zeros(1, dtype=torch.int32, device=dev)
+            temb = torch.empty((B, cfg.llm_dim), dtype=BF16, device=dev)
+            noisy = torch.empty(n, dtype=BF16, device=dev)
+            lens = self.check_right_padding(batch["attention_mask"])
+            ids = batch["input_ids"].to(dev, torch.int64).contiguous()
+            lab = batch["labels"].to(dev, torch.int64).contiguous()
+            lens_dev = lens.to(torch.int32).to(dev)
+            cached = None
+            for _ in range(st.T):
+                ops.ddim_prepare(step, st.step_temb, temb, sample, noisy)
+                out = self.forward_dev(ids, lab, lens_dev, batch["pixel_values"], proprio=batch.get("proprio"), noisy_actions=noisy, timestep_emb=temb,
+                                       train=False, cached_patches=cached, sel="actions")
+                cached = out["patches"]                           # vision features reused across the steps
+                ah, _ = self.action_hidden(out)
+                eps = self.head.fwd(ah)[0]
+                ops.ddim_step(sample, eps, st.coef, step)
+            return sample.to(BF16).view(B, cfg.chunk, cfg.action_dim)
 
     def train_step_discrete(self, batch: dict, loss_scale: float = 1.0, proprio_projector=None, backward: bool = True):
         """run_forward_pass's discrete branch (finetune.py:357-378) + backward: `loss = output.loss`, the LlamaForCausalLM

@@ -1012,6 +1012,34 @@ def ddim_step(sample, eps, coef, step):
     return sample
 
 
+def diffusion_noise(actions, ab, temb_table, *, seed, call, stream=0, noise=None, noisy=None, temb=None, timesteps=None):
+    """sample_noisy_actions in one launch (ovla.h "Diffusion noise": ovla_diffusion_noise): actions bf16 [B, n] (row stride free), ab fp32 [T, 2]
+    (DDIMScheduler.add_noise_coefficients()), temb_table bf16 [T, D] -> (noise bf16 [B, n], noisy bf16 [B, n], temb bf16 [B, D], timesteps int32
+    [B]), every one a pure function of (seed, call, stream, sample, element).  `stream`: 0 training noise, 2 the sampler's start noise.  Outputs
+    given by the caller may have row strides of their own."""
+    _chk(actions, name="actions"), _chk(ab, torch.float32, "ab"), _chk(temb_table, name="temb_table")
+    assert actions.dim() == 2 and actions.stride(1) == 1 and ab.dim() == 2 and ab.shape[1] == 2 and ab.is_contiguous()
+    assert temb_table.dim() == 2 and temb_table.is_contiguous() and temb_table.shape[0] == ab.shape[0]
+    (B, n), (T, D), dev = actions.shape, temb_table.shape, actions.device
+    noise = torch.empty((B, n), dtype=BF16, device=dev) if noise is None else noise
+    noisy = torch.empty((B, n), dtype=BF16, device=dev) if noisy is None else noisy
+    temb = torch.empty((B, D), dtype=BF16, device=dev) if temb is None else temb
+    timesteps = torch.empty(B, dtype=torch.int32, device=dev) if timesteps is None else timesteps
+    for t, name, cols in ((noise, "noise", n), (noisy, "noisy", n), (temb, "temb", D)):
+        _chk(t, name=name)
+        assert t.dim() == 2 and t.shape == (B, cols) and t.stride(1) == 1, f"{name}: expected [{B}, {cols}] with unit column stride"
+    _chk(timesteps, torch.int32, "timesteps")
+    assert timesteps.shape == (B,) and timesteps.is_contiguous()
+    g = STRUCTS["ovla_diffusion_noise_args"]()
+    g.actions, g.ld_actions, g.ab, g.temb_table = actions.data_ptr(), actions.stride(0), ab.data_ptr(), temb_table.data_ptr()
+    g.noise, g.ld_noise, g.noisy, g.ld_noisy, g.temb, g.ld_temb = noise.data_ptr(), noise.stride(0), noisy.data_ptr(), noisy.stride(0), temb.data_ptr(), temb.stride(0)
+    g.timesteps = timesteps.data_ptr()
+    g.seed_lo, g.seed_hi, g.call, g.stream = int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF, int(call) & 0xFFFFFFFF, int(stream) & 0xFFFFFFFF
+    g.B, g.n, g.D, g.T = B, n, D, T
+    _lib.call("ovla_diffusion_noise", g, _stream())
+    return noise, noisy, temb, timesteps
+
+
 def head_out_fwd(x, W, b, target=None, loss_sum=None, mse=False, out=None):
     rows, dim = x.shape
     adim = W.shape[0]

@@ -103,6 +103,12 @@ def dropout_seed_for_rank(rank: int) -> int:
     return 7 + (int(rank) << 32)
 
 
+def diffusion_seed_for_rank(rank: int) -> int:
+    """The 64-bit Philox key of the device diffusion noise (finetune(diffusion_noise="device")): the rank in the high word like
+    dropout_seed_for_rank, another low word, so the noise shares no generator output with the lora_dropout masks."""
+    return 0xD1FF + (int(rank) << 32)
+
+
 def learning_rate_at(cfg, gradient_step_idx: int) -> float:
     """MultiStepLR(milestones=[num_steps_before_decay], gamma=0.1) + optional linear warm-up 10% -> 100%
     (finetune.py:958-962, 1094-1098).  The step index is the number of optimizer steps already taken."""
@@ -239,7 +245,8 @@ def load_training_checkpoint(ckpt: Path, log_step: Optional[int], engine: VLAEng
     """Resume (finetune.py:134-156 `load_checkpoint(module_name, path, step)` per component + the lora adapter the reference
     re-attaches through its merged checkpoint): reads `{component}--{step}_checkpoint.pt` (`latest` when step is None), the
     peft adapter directory and, if present, the optimizer state, which also carries the lora_dropout mask stream's `call` counter
-    (`dropout_call` in the result: False when the checkpoint has none).  Only `weights_only=True` / safetensors loaders are used."""
+    (`dropout_call` in the result: False when the checkpoint has none) and, for an engine with device diffusion noise, that stream's
+    (`diffusion_call`).  Only `weights_only=True` / safetensors loaders are used."""
     ckpt = Path(ckpt)
     suffix = "latest_checkpoint" if log_step is None else f"{log_step}_checkpoint"
     sd: Dict[str, torch.Tensor] = {}
@@ -258,20 +265,29 @@ def load_training_checkpoint(ckpt: Path, log_step: Optional[int], engine: VLAEng
                 sd.update({prefix + k: v for k, v in part.items()})
     missing = engine.load_trainable(sd, strict=False)
     opt = ckpt / f"optimizer_state--{suffix}.safetensors"
-    loaded_opt = has_call = False
+    loaded_opt = has_call = has_noise_call = False
     if load_optimizer and opt.is_file():
         from safetensors.torch import load_file
 
         osd = load_file(str(opt))
         engine.load_optimizer_state_dict(osd)
-        loaded_opt, has_call = True, "lora_dropout.call" in osd
-    return {"missing": missing, "optimizer": loaded_opt, "tensors": len(sd), "dropout_call": has_call}
+        loaded_opt, has_call, has_noise_call = True, "lora_dropout.call" in osd, "diffusion_noise.call" in osd
+    return {"missing": missing, "optimizer": loaded_opt, "tensors": len(sd), "dropout_call": has_call, "diffusion_call": has_noise_call}
+
+
+def sampled_l1_metrics(engine: VLAEngine, batch: dict) -> Dict[str, float]:
+    """finetune.py:410-448 for the diffusion objective: a chunk sampled by the whole reverse diffusion (VLAEngine.sample_actions, no host round
+    trip between its steps) against the ground truth -- L1 of chunk step 0 and of the rest.  The two `.item()` are the only synchronisation."""
+    pred = engine.sample_actions(batch).float()
+    gt = batch["actions"].to(pred.device, torch.bfloat16).float().reshape(pred.shape)
+    return {"curr_action_l1_loss": torch.nn.L1Loss()(gt[:, 0], pred[:, 0]).item(), "next_actions_l1_loss": torch.nn.L1Loss()(gt[:, 1:], pred[:, 1:]).item()}
 
 
 def run_validation(engine: VLAEngine, cfg: FinetuneConfig, val_batches: Iterable[dict], log_step: int, log, *, discrete: bool, make_diffusion=None,
-                   metric_fn=None) -> Dict[str, float]:
-    """finetune.py:678-760: the training loss (and, for the discrete objective, the token metrics) on the validation loader without
-    gradients, cut short after `cfg.val_time_limit` seconds, averaged over the batches seen, logged with a `val/` prefix."""
+                   metric_fn=None, sample_l1: bool = False) -> Dict[str, float]:
+    """finetune.py:678-760: the training loss (and, for the discrete objective, the token metrics; with `sample_l1`, the diffusion objective's
+    sampled L1 of every batch, :735) on the validation loader without gradients, cut short after `cfg.val_time_limit` seconds, averaged over
+    the batches seen, logged with a `val/` prefix."""
     import time
 
     start, rows = time.time(), []
@@ -282,6 +298,8 @@ def run_validation(engine: VLAEngine, cfg: FinetuneConfig, val_batches: Iterable
         m = {"loss_value": loss_sum.item() / count}
         if metric_fn is not None:
             m.update(metric_fn(batch, pred))
+        if sample_l1:
+            m.update(sampled_l1_metrics(engine, batch))
         m["loss"] = m["loss_value"]
         rows.append(m)
         if time.time() - start > cfg.val_time_limit:
@@ -296,11 +314,20 @@ def run_validation(engine: VLAEngine, cfg: FinetuneConfig, val_batches: Iterable
 
 def finetune(cfg: FinetuneConfig, *, model_config: VLAConfig = OPENVLA_7B, state_dict: Optional[Dict[str, torch.Tensor]] = None,
              dataset: Optional[Iterable[dict]] = None, dataset_statistics: Optional[dict] = None, log=print, tokenizer=None,
-             val_dataset=None) -> Dict[str, list]:
+             val_dataset=None, diffusion_noise: str = "host") -> Dict[str, list]:
     """finetune.py:763-1154.  Returns the logged metric history.  Data source, in this order: `dataset` (any iterable of collated
     batches); an episode store at `cfg.data_root_dir / cfg.dataset_name` (prismatic/vla/datasets/rlds_free.py: the reference's
     RLDSDataset + RLDSBatchTransform + collator, finetune.py:981-1016, with the frames augmented and normalised on the device --
-    needs `tokenizer(text) -> ids` or tokenizer files under `cfg.vla_path`); otherwise seeded synthetic batches of the recipe's shape."""
+    needs `tokenizer(text) -> ids` or tokenizer files under `cfg.vla_path`); otherwise seeded synthetic batches of the recipe's shape.
+    `diffusion_noise` (diffusion objective only): "host" draws noise and timesteps from a CPU torch.Generator, which waits for the device on
+    every step and whose state no checkpoint holds; "device" draws them in one launch (VLAEngine.draw_diffusion) from a counter saved with the
+    optimizer state, so a resumed run continues the uninterrupted one's noise, and every `cfg.diffusion_sample_freq` batches (and on every
+    validation batch) samples a chunk (VLAEngine.sample_actions) for `curr_action_l1_loss` / `next_actions_l1_loss` (finetune.py:1053, :410-448)."""
+    if diffusion_noise not in ("host", "device"):
+        raise ValueError(f'diffusion_noise = {diffusion_noise!r} ("host" or "device")')
+    device_noise = diffusion_noise == "device"
+    if device_noise and not cfg.use_diffusion:
+        raise ValueError('diffusion_noise="device" needs cfg.use_diffusion: the other objectives draw no noise')
     assert cfg.use_lora, "Only LoRA fine-tuning is supported. Please set --use_lora=True!"
     assert not (cfg.use_l1_regression and cfg.use_diffusion), "Cannot do both L1 regression and diffusion. Please pick one of them!"
     discrete = not (cfg.use_l1_regression or cfg.use_diffusion)    # next-token cross entropy on the action tokens (finetune.py:357-378)
@@ -324,7 +351,8 @@ def finetune(cfg: FinetuneConfig, *, model_config: VLAConfig = OPENVLA_7B, state
         state_dict = random_state_dict(model_config, dev, seed=0, lm_head=discrete, film=cfg.use_film, diffusion=cfg.use_diffusion)
     get, has = make_getter(state_dict, dev)
     engine = VLAEngine(model_config, get, dev, lora=True, use_proprio=cfg.use_proprio, head="none" if discrete else ("diffusion" if cfg.use_diffusion else "l1"),
-                       use_film=cfg.use_film, has=has, lora_dropout=cfg.lora_dropout, dropout_seed=dropout_seed_for_rank(rank))
+                       use_film=cfg.use_film, has=has, lora_dropout=cfg.lora_dropout, dropout_seed=dropout_seed_for_rank(rank),
+                       **(dict(num_diffusion_steps=cfg.num_diffusion_steps, diffusion_seed=diffusion_seed_for_rank(rank)) if device_noise else {}))
     if cfg.use_diffusion:   # DiffusionActionHead.sample_noisy_actions (action_heads.py:167-197), host side
         from ..diffusion import DDIMScheduler, SinusoidalPositionalEncoding
 
@@ -337,6 +365,8 @@ def finetune(cfg: FinetuneConfig, *, model_config: VLAConfig = OPENVLA_7B, state
         if not info["dropout_call"]:   # a checkpoint from before the counter was saved was trained with dropout ignored: there is no mask stream to
             # continue, only one to start; start it at a position that depends on the step, so two resumes at different steps do not share masks
             engine.dropout.call = (cfg.resume_step * cfg.grad_accumulation_steps) & 0xFFFFFFFF
+        if device_noise and not info["diffusion_call"]:   # the same rule for the noise stream of a checkpoint written with host noise
+            engine.diffusion.call = (cfg.resume_step * cfg.grad_accumulation_steps) & 0xFFFFFFFF
         log(f"[finetune] resumed step {cfg.resume_step} from {cfg.vla_path}: {info['tensors']} tensors, optimizer state: {info['optimizer']}, "
             f"{len(info['missing'])} trainable tensors kept at their initial values")
     reducer = GradReducer(engine.stores, world) if world > 1 else None
@@ -386,7 +416,12 @@ def finetune(cfg: FinetuneConfig, *, model_config: VLAConfig = OPENVLA_7B, state
 
         metric_tok = ActionTokenizer(type("Vocab", (), {"vocab_size": model_config.vocab - model_config.pad_to_multiple_of})())
         history.update({k: [] for k in ("curr_action_accuracy", "curr_action_l1_loss", "next_actions_accuracy", "next_actions_l1_loss")})
+    if device_noise:
+        history.update({"curr_action_l1_loss": [], "next_actions_l1_loss": []})
+
     def make_diffusion(batch):   # DiffusionActionHead.sample_noisy_actions (action_heads.py:167-197)
+        if device_noise:
+            return engine.draw_diffusion(batch["actions"])
         gt = batch["actions"].to("cpu", torch.float32)
         noise = torch.randn(gt.shape, generator=noise_gen).to(torch.bfloat16).float()
         tsteps = torch.randint(0, cfg.num_diffusion_steps, (gt.shape[0],), generator=noise_gen)
@@ -405,6 +440,9 @@ def finetune(cfg: FinetuneConfig, *, model_config: VLAConfig = OPENVLA_7B, state
         if not cfg.use_proprio:
             batch = {**batch, "proprio": None}
         diffusion = make_diffusion(batch) if cfg.use_diffusion else None
+        if device_noise and batch_idx % cfg.diffusion_sample_freq == 0:   # finetune.py:1053: before the step, with the parameters the loss sees
+            for k, v in sampled_l1_metrics(engine, batch).items():
+                history[k].append(v)
         if discrete:
             loss_sum, count, pred_ids = engine.train_step_discrete(batch, loss_scale=1.0 / cfg.grad_accumulation_steps)
         else:
@@ -431,7 +469,7 @@ def finetune(cfg: FinetuneConfig, *, model_config: VLAConfig = OPENVLA_7B, state
             if cfg.use_val_set and log_step > 0 and log_step % cfg.val_freq == 0:   # finetune.py:1128-1144
                 history["val"].append((log_step, run_validation(engine, cfg, val_dataset(), log_step, log if rank == 0 else (lambda *_: None), discrete=discrete,
                                                                 make_diffusion=make_diffusion if cfg.use_diffusion else None,
-                                                                metric_fn=token_metrics if discrete else None)))
+                                                                metric_fn=token_metrics if discrete else None, sample_l1=device_noise)))
             if gradient_step_idx > 0 and log_step % cfg.save_freq == 0:
                 save_training_checkpoint(run_dir, log_step, engine, dataset_statistics, rank, cfg.save_latest_checkpoint_only)
                 if world > 1:
