@@ -651,6 +651,29 @@ typedef struct {
 int ovla_adamw(const ovla_adamw_args* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Weight EMA: the exponential moving average of a flat parameter buffer, kept in an fp32 shadow and updated right after the optimizer
+ * step (vla-scripts/finetune.py:952 is where the reference builds its optimizer; the reference has NO EMA -- this extends that call site with
+ * the update of diffusers' EMAModel, its `s.sub_(omd * (s - p))` form, which Diffusion Policy evaluates on).  THE EMA CONTRACT (identical in
+ * csrc/ema.hip and in the numpy restatement tests/ema_reference.py), with s = shadow[i] and omd = one_minus_decay:
+ *     shadow[i] = s - omd * (s - float(param[i]))                      i in [0, n)
+ *   arithmetic  three fp32 operations -- subtract, multiply, subtract -- each rounded on its own (no FMA contraction).  A bf16 parameter is
+ *               widened exactly (its 16 bits become the upper half of the fp32).  omd = 0 keeps a shadow whose difference to the parameter is finite; omd = 1 gives
+ *               s - (s - p), the parameter up to the rounding of the difference.
+ *   purity      the result is a pure function of (shadow[i], param[i], omd): nothing depends on n, on launch geometry or on which lane holds
+ *               the element.  The body moves 16 bytes per lane and instruction, the last n % 8 (bf16) or n % 4 (fp32) elements one per lane.
+ *   memory      param is never written; exactly shadow[0 .. n) is written.  Stream-ordered and capturable, no atomics, no workspace.
+ *   refusals    OVLA_EINVAL before any launch: a null pointer, n < 0, param or shadow not 16-byte aligned, one_minus_decay outside [0, 1] or
+ *               NaN.  n == 0 is legal and launches nothing.
+ * The decay schedule (warm-up) is the caller's: vla_scripts/finetune.py `ema_decay_at`. */
+typedef struct {
+  const void* param;      /* bf16 or fp32 [n] (is_bf16) */
+  float* shadow;          /* fp32 [n], in/out */
+  int64_t n; int32_t is_bf16;
+  float one_minus_decay;  /* in [0, 1] */
+} ovla_ema_update_args;
+int ovla_ema_update(const ovla_ema_update_args* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * DDIM sampling on the device (prismatic/extern/hf/modeling_prismatic.py:793-877 `_run_diffusion_prediction`: per step, timestep
  * embedding + noisy actions in, `noise_scheduler.step(noise_pred, t, curr_noisy_actions).prev_sample` out).  The loop's step index k is a
  * DEVICE int32 that both kernels read and ovla_ddim_step advances, so one sampling step has no host-dependent argument and can be replayed

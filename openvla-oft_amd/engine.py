@@ -101,6 +101,8 @@ class ParamStore:
         self.exp_avg_sq: Dict[torch.dtype, torch.Tensor] = {}
         self.step = 0
         self.finalized = False
+        self.ema_shadow: Optional[Dict[torch.dtype, torch.Tensor]] = None   # weight EMA (enable_ema): one fp32 shadow per flat buffer
+        self.ema_step = 0
 
     def add(self, name: str, init: torch.Tensor) -> Param:
         assert not self.finalized and init.dtype in (BF16, F32)
@@ -147,6 +149,42 @@ class ParamStore:
         for dtype, flat in self.flat.items():
             ops.adamw(flat, self.exp_avg[dtype], self.exp_avg_sq[dtype], self.flat_grad[dtype], step=self.step, lr=lr, beta1=beta1,
                       beta2=beta2, eps=eps, weight_decay=weight_decay, grad_scale=grad_scale)
+
+    # -- weight EMA (ovla.h "Weight EMA"): the reference has none; diffusers' EMAModel, which Diffusion Policy evaluates on ------------------------
+    def enable_ema(self):
+        """One fp32 shadow per flat buffer, initialised exactly from the current parameters (bf16 widened, fp32 copied); ema_step = 0."""
+        self.ema_shadow = {}
+        for dtype, flat in self.flat.items():
+            shadow = torch.empty(flat.numel(), dtype=F32, device=self.device)
+            if dtype == BF16:
+                ops.cvt_bf16_to_f32(flat, shadow)
+            else:
+                shadow.copy_(flat)
+            self.ema_shadow[dtype] = shadow
+        self.ema_step = 0
+
+    def ema_update(self, decay: float):
+        """shadow <- shadow - (1 - decay) (shadow - param), one launch per dtype; 1 - decay is formed in double and rounded to fp32 once."""
+        if self.ema_shadow is None:
+            raise RuntimeError("ema_update without enable_ema()")
+        self.ema_step += 1
+        for dtype, flat in self.flat.items():
+            ops.ema_update(flat, self.ema_shadow[dtype], 1.0 - float(decay))
+
+    def ema_swap_in(self) -> Dict[torch.dtype, torch.Tensor]:
+        """Writes the averaged weights over the live ones -- bf16_rne(shadow) into the bf16 buffer, shadow into the fp32 one -- and returns
+        copies of the live buffers for ema_restore."""
+        stash = {dtype: flat.clone() for dtype, flat in self.flat.items()}
+        for dtype, flat in self.flat.items():
+            if dtype == BF16:
+                ops.cvt_f32_to_bf16(self.ema_shadow[dtype], flat)
+            else:
+                flat.copy_(self.ema_shadow[dtype])
+        return stash
+
+    def ema_restore(self, stash: Dict[torch.dtype, torch.Tensor]):
+        for dtype, flat in self.flat.items():
+            flat.copy_(stash[dtype])
 
     def num_trainable(self):
         return sum(p.numel for p in self.params)
@@ -1189,8 +1227,62 @@ class VLAEngine:
             self.reducer.reset()
 
     def adamw_step(self, lr: float, **kw):
+        self._not_in_ema_scope("adamw_step")
         for st in self.stores:
             st.adamw_step(lr, **kw)
+
+    # -- weight EMA: fp32 shadows of every store's flat buffers, updated after the optimizer step, swapped in for evaluation and export -----------
+    _ema_scope = False   # true while ema_weights() holds the averaged weights in the flat buffers
+
+    @property
+    def ema_enabled(self) -> bool:
+        return self.store.ema_shadow is not None
+
+    @property
+    def ema_step(self) -> int:
+        """The number of EMA updates taken (the same in every store)."""
+        return self.store.ema_step
+
+    @property
+    def in_ema_scope(self) -> bool:
+        return self._ema_scope
+
+    def _not_in_ema_scope(self, who: str):
+        if self._ema_scope:
+            raise RuntimeError(f"{who} inside ema_weights(): the flat buffers hold the averaged weights, not the ones being trained")
+
+    def enable_ema(self):
+        self._not_in_ema_scope("enable_ema")
+        for st in self.stores:
+            st.enable_ema()
+
+    def ema_update(self, decay: float):
+        """One EMA update of every store with this decay (the schedule is the caller's: vla_scripts/finetune.py ema_decay_at).  Stream-ordered
+        launches only, nothing is read back."""
+        self._not_in_ema_scope("ema_update")
+        if not 0.0 <= float(decay) <= 1.0:
+            raise ValueError(f"ema decay = {decay} is outside [0, 1]")
+        for st in self.stores:
+            st.ema_update(decay)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Scope in which the flat buffers hold the averaged weights: eval_step, sample_actions, export_trainable("data"),
+        vision_backbone_state_dict() and save_training_checkpoint see them with no change of their own.  On exit the live bits come back
+        exactly; the derived copies are re-derived on both sides.  Training entry points and ema_update raise inside, and so does nesting."""
+        if not self.ema_enabled:
+            raise RuntimeError("ema_weights() without enable_ema()")
+        self._not_in_ema_scope("ema_weights")
+        stash = [st.ema_swap_in() for st in self.stores]
+        self._ema_scope = True
+        try:
+            self.refresh_derived()
+            yield self
+        finally:
+            for st, live in zip(self.stores, stash):
+                st.ema_restore(live)
+            self._ema_scope = False
+            self.refresh_derived()
 
     def num_trainable(self):
         return sum(st.num_trainable() for st in self.stores)
@@ -1523,6 +1615,11 @@ class VLAEngine:
         out["lora_dropout.call"] = torch.tensor([self.dropout.call], dtype=torch.int64)   # the mask stream's position: a resumed run draws the masks the uninterrupted one would
         if self.diffusion is not None:   # ... and the noise and timesteps the uninterrupted one would
             out["diffusion_noise.call"] = torch.tensor([self.diffusion.call], dtype=torch.int64)
+        if self.ema_enabled:   # the averaged weights and the position of their decay schedule
+            out["ema.step"] = torch.tensor([self.ema_step], dtype=torch.int64)
+            for i, st in enumerate(self.stores):
+                for dt, shadow in st.ema_shadow.items():
+                    out[f"ema.store{i}.{'bf16' if dt == BF16 else 'f32'}.shadow"] = shadow
         return out
 
     def load_optimizer_state_dict(self, sd: Dict[str, torch.Tensor]):
@@ -1541,6 +1638,23 @@ class VLAEngine:
                     if src.numel() != buf.numel():
                         raise ValueError(f"optimizer state store{i}.{tag}.{kind}: {src.numel()} elements, model has {buf.numel()}")
                     buf.copy_(src.to(buf.device, buf.dtype))
+        if self.ema_enabled:
+            self.load_ema_state_dict(sd)
+
+    def load_ema_state_dict(self, sd: Dict[str, torch.Tensor]) -> bool:
+        """Restores the shadows and the EMA step from the `ema.` entries of an optimizer state dict into an engine with EMA enabled.
+        False, and nothing changes, when `sd` has none (written by a run without EMA)."""
+        if "ema.step" not in sd:
+            return False
+        self._not_in_ema_scope("load_ema_state_dict")
+        for i, st in enumerate(self.stores):
+            st.ema_step = int(sd["ema.step"].item())
+            for dt, shadow in st.ema_shadow.items():
+                src = sd[f"ema.store{i}.{'bf16' if dt == BF16 else 'f32'}.shadow"]
+                if src.numel() != shadow.numel() or src.dtype != F32:
+                    raise ValueError(f"EMA shadow of store{i}: {src.numel()} {src.dtype} elements, model has {shadow.numel()} fp32")
+                shadow.copy_(src.to(shadow.device))
+        return True
 
     def num_patches_total(self, num_images: int, use_proprio: bool, use_diffusion: bool = False) -> int:
         """NUM_PATCHES of finetune.py:935-941."""
@@ -1822,6 +1936,7 @@ class VLAEngine:
         """One run_forward_pass (finetune.py:280-451) + backward.  L1 branch by default; with
         `diffusion = dict(noise, noisy_actions, timestep_emb)` the noise-prediction MSE branch (:402-407).
         Gradients accumulate in the flat buffers.  Returns (loss_sum fp32[1] device, element count, predictions)."""
+        self._not_in_ema_scope("train_step_fwd_bwd")
         cfg = self.cfg
         head = action_head if action_head is not None else self.head
         kw = {}
@@ -1934,6 +2049,8 @@ class VLAEngine:
         frozen lm_head applied ONLY to the rows whose shifted label counts (the action tokens and the stop token: A + 1 rows per
         sample instead of all S).  Returns (loss_sum fp32[1] device, token count, predicted ids int64 [B, L - 1] on the host
         layout of `output.logits[:, num_patches:-1].argmax(2)` with -1 where no row was evaluated)."""
+        if backward:
+            self._not_in_ema_scope("train_step_discrete")
         if self.lm_head is None:
             raise RuntimeError("the discrete objective needs language_model.lm_head.weight in the checkpoint")
         labels = batch["labels"].to("cpu", torch.int64)

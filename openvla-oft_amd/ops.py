@@ -1106,6 +1106,16 @@ def adamw(param, exp_avg, exp_avg_sq, grad, *, step, lr, beta1=0.9, beta2=0.999,
     _lib.call("ovla_adamw", g, _stream())
 
 
+def ema_update(param, shadow, one_minus_decay):
+    """shadow <- shadow - omd * (shadow - float(param)) in place (ovla.h "Weight EMA"); `one_minus_decay` is a Python float that the argument
+    struct rounds to fp32 once."""
+    assert shadow.dtype == torch.float32 and param.dtype in (BF16, torch.float32) and shadow.numel() == param.numel()
+    assert param.is_contiguous() and shadow.is_contiguous()
+    g = STRUCTS["ovla_ema_update_args"]()
+    g.param, g.shadow, g.n, g.is_bf16, g.one_minus_decay = param.data_ptr(), shadow.data_ptr(), param.numel(), int(param.dtype == BF16), one_minus_decay
+    _lib.call("ovla_ema_update", g, _stream())
+
+
 def cvt_f32_to_bf16(src, dst=None, scale=1.0):
     if dst is None:
         dst = torch.empty(src.shape, dtype=BF16, device=src.device)

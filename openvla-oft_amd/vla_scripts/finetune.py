@@ -15,6 +15,7 @@ What differs from the reference, deliberately:
 """
 from __future__ import annotations
 
+import contextlib
 import json
 import os
 from dataclasses import dataclass
@@ -119,6 +120,19 @@ def learning_rate_at(cfg, gradient_step_idx: int) -> float:
     return lr
 
 
+def ema_decay_at(k: int, *, max_decay: float, power: Optional[float] = 0.75, inv_gamma: float = 1.0, update_after: int = 0) -> float:
+    """The decay of the k-th EMA update (k counts from 1), in double precision: the warm-up of diffusers' EMAModel.get_decay, which Diffusion
+    Policy trains with -- 0 while step = k - update_after - 1 <= 0 (the shadow goes all the way to the parameters), then
+    min(max_decay, 1 - (1 + step / inv_gamma) ** -power); `power=None` is the constant decay max_decay.  diffusers is not installed here:
+    restated from its published formula, PARITY UNPINNED against the library.  The reference (vla-scripts/finetune.py) has no EMA."""
+    step = k - update_after - 1
+    if step <= 0:
+        return 0.0
+    if power is None:
+        return float(max_decay)
+    return min(float(max_decay), 1.0 - (1.0 + step / inv_gamma) ** (-power))
+
+
 def run_diffusion_sampling(vla, action_head, noisy_action_projector, proprio_projector, batch, batch_size, num_patches, actions_shape, device_id,
                            current_action_mask, next_actions_mask, use_proprio, use_film) -> torch.Tensor:
     """finetune.py:454-540: reverse diffusion for the whole batch -- start from N(0, 1) noise, and for every DDIM timestep predict the
@@ -209,12 +223,18 @@ _COMPONENT_PREFIXES = {"proprio_projector": "proprio_projector.", "noisy_action_
 
 
 def save_training_checkpoint(run_dir: Path, log_step: int, engine: VLAEngine, dataset_statistics: Optional[dict], rank: int,
-                             latest_only: bool = False, save_optimizer: bool = True) -> Path:
+                             latest_only: bool = False, save_optimizer: bool = True, into: Optional[Path] = None) -> Path:
     """finetune.py:584-675: `{component}--{step}_checkpoint.pt` (+ `lora_adapter/` in peft's format, `dataset_statistics.json`).
     The LoRA merge of the reference (:663-675) is the separate merge_lora_weights_and_save step.  Beyond the reference:
     `optimizer_state--{step}_checkpoint.safetensors` (AdamW moments + step counters), so a resumed run continues the same
-    trajectory instead of restarting the moments from zero."""
+    trajectory instead of restarting the moments from zero.
+    With weight EMA enabled (VLAEngine.enable_ema) that file also carries the shadows and the EMA step, and rank 0 writes a second complete
+    fine-tune output directory `ckpt / "ema"` with the averaged weights (inside engine.ema_weights(), no optimizer state; `into` names it): every
+    loader takes it as it takes `ckpt`, and as a sub-directory it leaves find_checkpoint_file's one-match rule for the live files alone.  Called
+    inside an ema_weights() scope, this writes the averaged weights as `ckpt` and no sub-directory."""
     ckpt = run_dir if latest_only else Path(str(run_dir) + f"--{log_step}_chkpt")
+    if into is not None:
+        ckpt = Path(into)
     suffix = "latest_checkpoint" if latest_only else f"{log_step}_checkpoint"
     if rank == 0:
         (ckpt / "lora_adapter").mkdir(parents=True, exist_ok=True)
@@ -238,6 +258,9 @@ def save_training_checkpoint(run_dir: Path, log_step: int, engine: VLAEngine, da
 
             save_file({k: v.detach().to("cpu").contiguous() for k, v in engine.optimizer_state_dict().items()},
                       str(ckpt / f"optimizer_state--{suffix}.safetensors"))
+        if engine.ema_enabled and not engine.in_ema_scope:
+            with engine.ema_weights():
+                save_training_checkpoint(run_dir, log_step, engine, dataset_statistics, rank, latest_only, save_optimizer=False, into=ckpt / "ema")
     return ckpt
 
 
@@ -273,6 +296,20 @@ def load_training_checkpoint(ckpt: Path, log_step: Optional[int], engine: VLAEng
         engine.load_optimizer_state_dict(osd)
         loaded_opt, has_call, has_noise_call = True, "lora_dropout.call" in osd, "diffusion_noise.call" in osd
     return {"missing": missing, "optimizer": loaded_opt, "tensors": len(sd), "dropout_call": has_call, "diffusion_call": has_noise_call}
+
+
+def load_ema_state(ckpt: Path, log_step: Optional[int], engine: VLAEngine) -> bool:
+    """Reads the weight-EMA shadows and step of a checkpoint's optimizer-state file into an engine that has EMA enabled (the resume load runs
+    before enable_ema, so it cannot).  False -- and nothing is changed -- when the file is absent or holds no `ema.` entry."""
+    suffix = "latest_checkpoint" if log_step is None else f"{log_step}_checkpoint"
+    opt = Path(ckpt) / f"optimizer_state--{suffix}.safetensors"
+    if not opt.is_file():
+        return False
+    from safetensors import safe_open
+
+    with safe_open(str(opt), framework="pt", device="cpu") as f:
+        ema = {k: f.get_tensor(k) for k in f.keys() if k.startswith("ema.")}
+    return engine.load_ema_state_dict(ema)
 
 
 def sampled_l1_metrics(engine: VLAEngine, batch: dict) -> Dict[str, float]:
@@ -314,7 +351,8 @@ def run_validation(engine: VLAEngine, cfg: FinetuneConfig, val_batches: Iterable
 
 def finetune(cfg: FinetuneConfig, *, model_config: VLAConfig = OPENVLA_7B, state_dict: Optional[Dict[str, torch.Tensor]] = None,
              dataset: Optional[Iterable[dict]] = None, dataset_statistics: Optional[dict] = None, log=print, tokenizer=None,
-             val_dataset=None, diffusion_noise: str = "host") -> Dict[str, list]:
+             val_dataset=None, diffusion_noise: str = "host", ema_decay: Optional[float] = None, ema_power: Optional[float] = 0.75,
+             ema_inv_gamma: float = 1.0, ema_update_after: int = 0) -> Dict[str, list]:
     """finetune.py:763-1154.  Returns the logged metric history.  Data source, in this order: `dataset` (any iterable of collated
     batches); an episode store at `cfg.data_root_dir / cfg.dataset_name` (prismatic/vla/datasets/rlds_free.py: the reference's
     RLDSDataset + RLDSBatchTransform + collator, finetune.py:981-1016, with the frames augmented and normalised on the device --
@@ -322,7 +360,16 @@ def finetune(cfg: FinetuneConfig, *, model_config: VLAConfig = OPENVLA_7B, state
     `diffusion_noise` (diffusion objective only): "host" draws noise and timesteps from a CPU torch.Generator, which waits for the device on
     every step and whose state no checkpoint holds; "device" draws them in one launch (VLAEngine.draw_diffusion) from a counter saved with the
     optimizer state, so a resumed run continues the uninterrupted one's noise, and every `cfg.diffusion_sample_freq` batches (and on every
-    validation batch) samples a chunk (VLAEngine.sample_actions) for `curr_action_l1_loss` / `next_actions_l1_loss` (finetune.py:1053, :410-448)."""
+    validation batch) samples a chunk (VLAEngine.sample_actions) for `curr_action_l1_loss` / `next_actions_l1_loss` (finetune.py:1053, :410-448).
+    `ema_decay` in [0, 1) switches on the weight EMA the reference lacks (diffusers' EMAModel; Diffusion Policy evaluates on it): fp32 shadows of
+    the trainable buffers, updated on the device after every optimizer step (not per micro-batch) with the decay ema_decay_at(k, max_decay=ema_decay,
+    power=ema_power, inv_gamma=ema_inv_gamma, update_after=ema_update_after).  Validation -- its sampled L1 included, under the same `val/` keys
+    -- runs on the averaged weights, the training-time sampling stays on the live ones; every checkpoint holds the shadows (optimizer-state
+    file, so a resumed run continues shadow and schedule) and an `ema/` sub-directory that serves and merges like any fine-tune output.  The
+    shadows are rank-local: the parameters are identical on every rank after the all-reduced step, so the shadows are too, and nothing is
+    communicated.  With `ema_decay=None` nothing of this runs."""
+    if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:
+        raise ValueError(f"ema_decay = {ema_decay} is outside [0, 1)")
     if diffusion_noise not in ("host", "device"):
         raise ValueError(f'diffusion_noise = {diffusion_noise!r} ("host" or "device")')
     device_noise = diffusion_noise == "device"
@@ -369,6 +416,12 @@ def finetune(cfg: FinetuneConfig, *, model_config: VLAConfig = OPENVLA_7B, state
             engine.diffusion.call = (cfg.resume_step * cfg.grad_accumulation_steps) & 0xFFFFFFFF
         log(f"[finetune] resumed step {cfg.resume_step} from {cfg.vla_path}: {info['tensors']} tensors, optimizer state: {info['optimizer']}, "
             f"{len(info['missing'])} trainable tensors kept at their initial values")
+    if ema_decay is not None:
+        engine.enable_ema()
+        if cfg.resume:   # the shadows are allocated after the load: read the optimizer-state file's ema.* entries now, if it has them
+            resumed_ema = load_ema_state(Path(cfg.vla_path), cfg.resume_step, engine)
+            log(f"[finetune] weight EMA continues at update {engine.ema_step}" if resumed_ema else
+                "[finetune] the checkpoint holds no EMA state (trained without ema_decay): the shadow starts at the loaded parameters, ema_step = 0")
     reducer = GradReducer(engine.stores, world) if world > 1 else None
     engine.attach_reducer(reducer, overlap=cfg.grad_accumulation_steps == 1 and os.environ.get("OVLA_DP_OVERLAP", "1") != "0")   # overlap only when every backward ends a step
     if dataset is None and (Path(cfg.data_root_dir) / cfg.dataset_name).is_dir():
@@ -418,6 +471,8 @@ def finetune(cfg: FinetuneConfig, *, model_config: VLAConfig = OPENVLA_7B, state
         history.update({k: [] for k in ("curr_action_accuracy", "curr_action_l1_loss", "next_actions_accuracy", "next_actions_l1_loss")})
     if device_noise:
         history.update({"curr_action_l1_loss": [], "next_actions_l1_loss": []})
+    if ema_decay is not None:
+        history["ema_decay"] = []
 
     def make_diffusion(batch):   # DiffusionActionHead.sample_noisy_actions (action_heads.py:167-197)
         if device_noise:
@@ -454,6 +509,9 @@ def finetune(cfg: FinetuneConfig, *, model_config: VLAConfig = OPENVLA_7B, state
                 reducer.all_reduce()
             lr = learning_rate_at(cfg, gradient_step_idx)
             engine.adamw_step(lr, grad_scale=1.0 / world)
+            if ema_decay is not None:
+                decay = ema_decay_at(engine.ema_step + 1, max_decay=ema_decay, power=ema_power, inv_gamma=ema_inv_gamma, update_after=ema_update_after)
+                engine.ema_update(decay)
             engine.refresh_derived()
             engine.zero_grad()
             if log_step % cfg.wandb_log_freq == 0:
@@ -461,15 +519,18 @@ def finetune(cfg: FinetuneConfig, *, model_config: VLAConfig = OPENVLA_7B, state
                 if engine.head is not None:
                     engine.head.check_fused_tail()      # (the host is synchronised here anyway: raises if a fused-tail grid barrier timed out)
                 history["learning_rate"].append(lr)
+                if ema_decay is not None:
+                    history["ema_decay"].append(decay)
                 if discrete:
                     for k, v in token_metrics(batch, pred_ids).items():
                         history[k].append(v)
                 if rank == 0:
                     log(f"step {log_step}: loss {history['loss_value'][-1]:.5f} lr {lr:.2e}")
             if cfg.use_val_set and log_step > 0 and log_step % cfg.val_freq == 0:   # finetune.py:1128-1144
-                history["val"].append((log_step, run_validation(engine, cfg, val_dataset(), log_step, log if rank == 0 else (lambda *_: None), discrete=discrete,
-                                                                make_diffusion=make_diffusion if cfg.use_diffusion else None,
-                                                                metric_fn=token_metrics if discrete else None, sample_l1=device_noise)))
+                with engine.ema_weights() if ema_decay is not None else contextlib.nullcontext():   # validation sees the averaged weights
+                    history["val"].append((log_step, run_validation(engine, cfg, val_dataset(), log_step, log if rank == 0 else (lambda *_: None), discrete=discrete,
+                                                                    make_diffusion=make_diffusion if cfg.use_diffusion else None,
+                                                                    metric_fn=token_metrics if discrete else None, sample_l1=device_noise)))
             if gradient_step_idx > 0 and log_step % cfg.save_freq == 0:
                 save_training_checkpoint(run_dir, log_step, engine, dataset_statistics, rank, cfg.save_latest_checkpoint_only)
                 if world > 1:
