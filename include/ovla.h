@@ -674,6 +674,74 @@ typedef struct {
 int ovla_ema_update(const ovla_ema_update_args* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Gradient-norm clipping and the non-finite step guard: torch.nn.utils.clip_grad_norm_(trainable_params, max_norm) in front of the optimizer
+ * step (the reference's own loop, vla-scripts/finetune.py:952-1100, never clips; its family -- the native Prismatic trainer's max_grad_norm --
+ * does), plus a guard the reference lacks: a step whose gradient norm is NaN or Inf changes nothing.  Three kernels, all stream-ordered and
+ * capturable; the norm is complete at a kernel boundary: no atomics, no grid barrier, no spin-wait, no cooperative launch, and no host value
+ * depends on the data.  THE CLIP CONTRACT (identical in csrc/grad_clip.hip and in the numpy restatement tests/grad_clip_reference.py):
+ *
+ * ovla_grad_sumsq: slots[slot] = sum over i in [0, n) of q_i, in double, where
+ *     r_i = grad[i] * grad_scale               one fp32 multiply; for a bf16 parameter buffer (is_bf16) rounded to bf16 (RNE) after it:
+ *                                              the gradient exactly as ovla_adamw forms it
+ *     q_i = (double)r_i * (double)r_i          exact (48 significant bits)
+ *   order       FIXED.  Chunk c covers elements [c C, min(n, (c + 1) C)), C = OVLA_GRAD_SUMSQ_CHUNK, and is reduced by one workgroup of
+ *               L = OVLA_GRAD_SUMSQ_LANES lanes.  Element c C + o belongs to lane (o / 4) % L; a lane starts at 0.0 and adds its q in ascending
+ *               o (trip k = o / (4 L) outermost, then the four elements of its 16-byte group).  The L lane sums s[0 .. L) are paired by THE TREE:
+ *               within each run of 64 consecutive lanes, for h = 32, 16, 8, 4, 2, 1: s[t] += s[t + h] for t < h; then the four run totals
+ *               w0 .. w3 give (w0 + w1) + (w2 + w3).  The chunk's partial is stored as a double in workspace[c].  A second launch of one
+ *               workgroup sums the P = ceil(n / C) partials: lane t starts at 0.0 and adds workspace[t], workspace[t + L], ... in ascending
+ *               index, then THE TREE again.  Every addition is a double addition rounded to nearest.
+ *   purity      a pure function of (grad[0 .. n), n, grad_scale, is_bf16): nothing depends on the grid, on the workspace's or the slots'
+ *               previous contents or on which hardware lane holds an element.  Full 16-byte groups are loaded 16 bytes per lane, the last
+ *               n % 4 elements one by one by the lane that owns their group.
+ *   memory      reads exactly grad[0 .. n); writes workspace[0 .. P) and slots[slot], nothing else.
+ *   refusals    OVLA_EINVAL before any launch: a null pointer, n < 0, slot < 0, grad not 16-byte aligned, slots or workspace not 8-byte
+ *               aligned, workspace_bytes < 8 P.  n == 0 is legal and writes 0.0. */
+#define OVLA_GRAD_SUMSQ_CHUNK 8192
+#define OVLA_GRAD_SUMSQ_LANES 256
+typedef struct {
+  const float* grad;        /* fp32 [n] */
+  int64_t n; int32_t is_bf16;
+  float grad_scale;
+  double* slots; int32_t slot;
+  double* workspace; int64_t workspace_bytes;   /* >= 8 * ceil(n / OVLA_GRAD_SUMSQ_CHUNK) */
+} ovla_grad_sumsq_args;
+int ovla_grad_sumsq(const ovla_grad_sumsq_args* a, void* stream);
+
+/* ovla_grad_clip_coef: one launch, one lane, ordinary stores.  total = slots[0] + slots[1] + ... + slots[n_slots - 1] in index order, in
+ * double, starting from 0.0; state->n_steps += 1; then
+ *   total not finite and skip_nonfinite:   skip = 1, coef = 1, norm = (float)sqrt(total) (NaN or Inf as computed), n_skipped += 1
+ *   otherwise:                             skip = 0, norm = (float)sqrt(total),
+ *                                          coef = fminf(1.f, max_norm / (norm + 1e-6f)) in fp32 (clip_grad_norm_'s formula; a NaN quotient
+ *                                          gives 1 by fminf), n_clipped += 1 if coef < 1
+ * max_norm = +inf is legal ("guard only": coef is 1 for every finite norm).  OVLA_EINVAL before the launch: a null pointer, n_slots < 1,
+ * max_norm <= 0 or NaN.  The state is device memory the caller zeroes once; only this kernel writes it. */
+typedef struct { float coef; float norm; int32_t skip; int32_t n_steps, n_clipped, n_skipped; } ovla_grad_clip_state;
+typedef struct {
+  const double* slots; int32_t n_slots;
+  float max_norm;
+  int32_t skip_nonfinite;
+  void* state;              /* device ovla_grad_clip_state, in/out */
+} ovla_grad_clip_coef_args;
+int ovla_grad_clip_coef(const ovla_grad_clip_coef_args* a, void* stream);
+
+/* ovla_adamw_clipped: ovla_adamw behind the clip state.  Every workgroup reads state->skip and returns at once when it is set: param,
+ * exp_avg and exp_avg_sq keep their bits.  Otherwise the gradient entering the update is
+ *     bf16:  bfround(bfround(grad[i] * grad_scale) * coef)        fp32:  (grad[i] * grad_scale) * coef
+ * (what grad.mul_(clip_coef) leaves in a .grad of the parameter's dtype), and from there on the element update IS ovla_adamw's: both
+ * kernels call one function (csrc/adamw_elem.h).  With coef == 1.0f the result is bit-identical to ovla_adamw.  The fields before
+ * clip_state are those of ovla_adamw_args, with the same meaning and the same refusals; a null clip_state is refused too. */
+typedef struct {
+  void* param; void* exp_avg; void* exp_avg_sq;
+  const float* grad;
+  int64_t n; int32_t is_bf16; int32_t step;
+  double lr, beta1, beta2, eps, weight_decay;
+  float grad_scale;
+  const void* clip_state;   /* device ovla_grad_clip_state written by ovla_grad_clip_coef earlier on the stream */
+} ovla_adamw_clipped_args;
+int ovla_adamw_clipped(const ovla_adamw_clipped_args* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * DDIM sampling on the device (prismatic/extern/hf/modeling_prismatic.py:793-877 `_run_diffusion_prediction`: per step, timestep
  * embedding + noisy actions in, `noise_scheduler.step(noise_pred, t, curr_noisy_actions).prev_sample` out).  The loop's step index k is a
  * DEVICE int32 that both kernels read and ovla_ddim_step advances, so one sampling step has no host-dependent argument and can be replayed

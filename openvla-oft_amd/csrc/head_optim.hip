@@ -1,6 +1,7 @@
 // head_optim.hip -- the N = ACTION_DIM tail of the L1 / diffusion action head (forward + loss, backward) and the fused
 // AdamW step.  Reference: prismatic/models/action_heads.py:69-81, vla-scripts/finetune.py:400,407,952.
 #include "common.h"
+#include "adamw_elem.h"
 #include <math.h>
 
 namespace {
@@ -370,32 +371,13 @@ __global__ __launch_bounds__(256) void head_out_bwd_kernel(const bf16_bits* __re
   }
 }
 
-struct AdamScalars {
-  float decay, w1, beta2, w2, bc2_sqrt, eps, step_size, grad_scale;
-};
-
-// lerp as ATen's vectorised CPU kernel computes it (aten/src/ATen/native/cpu/LerpKernel.cpp):
-// fmadd(|w| < 0.5 ? w : w - 1, b - a, |w| < 0.5 ? a : b)
-OVLA_DEV float aten_lerp(float a, float b, float w) {
-  return fabsf(w) < 0.5f ? __builtin_fmaf(w, b - a, a) : __builtin_fmaf(w - 1.f, b - a, b);
-}
-
+// AdamScalars, adam_scalars(), aten_lerp and the element update: adamw_elem.h (shared with ovla_adamw_clipped, grad_clip.hip)
 __global__ __launch_bounds__(256) void adamw_bf16_kernel(bf16_bits* __restrict__ p, bf16_bits* __restrict__ m, bf16_bits* __restrict__ v,
                                                          const float* __restrict__ g, int64_t n, AdamScalars s) {
 #pragma clang fp contract(off)  // keep ATen's operation order and roundings: no fused multiply-adds the reference lacks
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     const float grad = bfround(g[i] * s.grad_scale);          // what autograd would have stored in the bf16 .grad
-    float pp = bfround(bf2f(p[i]) * s.decay);                  // param.mul_(1 - lr*wd)
-    const float mm = bfround(aten_lerp(bf2f(m[i]), grad, s.w1));  // exp_avg.lerp_(grad, 1-beta1)
-    float vv = bfround(bf2f(v[i]) * s.beta2);                  // exp_avg_sq.mul_(beta2)
-    vv = bfround(vv + (s.w2 * grad) * grad);                   //   .addcmul_(grad, grad, value=1-beta2): self + value*t1*t2
-    float d = bfround(sqrtf(vv));                              // exp_avg_sq.sqrt()
-    d = bfround(d / s.bc2_sqrt);                               //   / bias_correction2_sqrt
-    d = bfround(d + s.eps);                                    //   .add_(eps)
-    pp = bfround(pp + (s.step_size * mm) / d);                 // param.addcdiv_(exp_avg, denom, value=-step_size): self + value*t1/t2
-    p[i] = f2bf(pp);
-    m[i] = f2bf(mm);
-    v[i] = f2bf(vv);
+    adamw_elem_bf16(p, m, v, i, grad, s);
   }
 }
 
@@ -404,15 +386,7 @@ __global__ __launch_bounds__(256) void adamw_f32_kernel(float* __restrict__ p, f
 #pragma clang fp contract(off)
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     const float grad = g[i] * s.grad_scale;
-    float pp = p[i] * s.decay;
-    const float mm = aten_lerp(m[i], grad, s.w1);
-    float vv = v[i] * s.beta2;
-    vv = vv + (s.w2 * grad) * grad;
-    const float d = sqrtf(vv) / s.bc2_sqrt + s.eps;
-    pp = pp + (s.step_size * mm) / d;
-    p[i] = pp;
-    m[i] = mm;
-    v[i] = vv;
+    adamw_elem_f32(p, m, v, i, grad, s);
   }
 }
 
@@ -620,18 +594,7 @@ extern "C" int ovla_head_out_bwd(const ovla_head_out_bwd_args* a, void* stream_)
 extern "C" int ovla_adamw(const ovla_adamw_args* a, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   OVLA_REQUIRE(a && a->param && a->exp_avg && a->exp_avg_sq && a->grad && a->n > 0 && a->step >= 1, "ovla_adamw: bad arguments");
-  // scalars exactly as torch/optim/adamw.py computes them (Python floats = double), then narrowed to the fp32 opmath type
-  const double bc1 = 1.0 - pow(a->beta1, (double)a->step);
-  const double bc2 = 1.0 - pow(a->beta2, (double)a->step);
-  AdamScalars s;
-  s.decay = (float)(1.0 - a->lr * a->weight_decay);
-  s.w1 = (float)(1.0 - a->beta1);
-  s.beta2 = (float)a->beta2;
-  s.w2 = (float)(1.0 - a->beta2);
-  s.bc2_sqrt = (float)sqrt(bc2);
-  s.eps = (float)a->eps;
-  s.step_size = (float)(-(a->lr / bc1));
-  s.grad_scale = a->grad_scale;
+  const AdamScalars s = adam_scalars(*a);
   int64_t blocks = (a->n + 255) / 256;
   if (blocks > 8192) blocks = 8192;
   if (a->is_bf16)

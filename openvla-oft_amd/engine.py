@@ -141,14 +141,21 @@ class ParamStore:
         for g in self.flat_grad.values():
             g.zero_()
 
-    def adamw_step(self, lr: float, *, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.01, grad_scale=1.0):
-        """torch.optim.AdamW(trainable_params, lr) of vla-scripts/finetune.py:952 as one fused launch per dtype."""
+    def adamw_step(self, lr: float, *, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.01, grad_scale=1.0, clip_state=None):
+        """torch.optim.AdamW(trainable_params, lr) of vla-scripts/finetune.py:952 as one fused launch per dtype.  With `clip_state` (the device
+        state VLAEngine.adamw_step filled, ovla.h "Gradient-norm clipping") the launches are ovla_adamw_clipped: the gradient is scaled by the
+        state's coefficient, and a step the state marks as skipped writes nothing.  `step` advances either way -- the host never learns of a
+        skip -- so a skipped step consumes its step number in the bias correction (and, in the driver, in the LR schedule)."""
         if not self.exp_avg:
             self.init_optimizer()
         self.step += 1
         for dtype, flat in self.flat.items():
-            ops.adamw(flat, self.exp_avg[dtype], self.exp_avg_sq[dtype], self.flat_grad[dtype], step=self.step, lr=lr, beta1=beta1,
-                      beta2=beta2, eps=eps, weight_decay=weight_decay, grad_scale=grad_scale)
+            if clip_state is None:
+                ops.adamw(flat, self.exp_avg[dtype], self.exp_avg_sq[dtype], self.flat_grad[dtype], step=self.step, lr=lr, beta1=beta1,
+                          beta2=beta2, eps=eps, weight_decay=weight_decay, grad_scale=grad_scale)
+            else:
+                ops.adamw_clipped(flat, self.exp_avg[dtype], self.exp_avg_sq[dtype], self.flat_grad[dtype], clip_state, step=self.step, lr=lr,
+                                  beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay, grad_scale=grad_scale)
 
     # -- weight EMA (ovla.h "Weight EMA"): the reference has none; diffusers' EMAModel, which Diffusion Policy evaluates on ------------------------
     def enable_ema(self):
@@ -1228,8 +1235,63 @@ class VLAEngine:
 
     def adamw_step(self, lr: float, **kw):
         self._not_in_ema_scope("adamw_step")
+        clip = self._grad_clip
+        if clip is None:
+            for st in self.stores:
+                st.adamw_step(lr, **kw)
+            return
+        # the global norm of the gradients as AdamW will see them (after the reducer, times grad_scale, in the parameter's precision): one
+        # sum-of-squares per flat buffer, one coefficient launch, then the clipped AdamW launches.  Nothing is read back.
+        grad_scale = kw.get("grad_scale", 1.0)
+        slot = 0
         for st in self.stores:
-            st.adamw_step(lr, **kw)
+            for dt, grad in st.flat_grad.items():
+                ops.grad_sumsq(grad, clip["slots"], slot, clip["workspace"], is_bf16=dt == BF16, grad_scale=grad_scale)
+                slot += 1
+        ops.grad_clip_coef(clip["slots"], clip["state"], clip["max_norm"], clip["skip_nonfinite"])
+        for st in self.stores:
+            st.adamw_step(lr, clip_state=clip["state"], **kw)
+
+    # -- gradient-norm clipping and the non-finite step guard (ovla.h "Gradient-norm clipping") ---------------------------------------------------
+    _grad_clip: Optional[dict] = None
+
+    @property
+    def grad_clip_enabled(self) -> bool:
+        return self._grad_clip is not None
+
+    def enable_grad_clip(self, max_norm: float = math.inf, skip_nonfinite: bool = True):
+        """From now on adamw_step clips the global gradient norm (every store, both dtypes) to `max_norm` as torch's clip_grad_norm_ does, and,
+        with `skip_nonfinite`, leaves parameters and moments untouched on a step whose norm is NaN or Inf.  max_norm = inf: guard only.
+        Allocates one double slot per (store, dtype) flat buffer -- in `stores` order, bf16 before fp32 --, the device state and the partials
+        workspace.  A skipped step still advances ParamStore.step: it consumes its step number in the bias correction and the LR schedule, and
+        an EMA update after it averages the unchanged parameters.  The zero padding of the flat buffers contributes nothing to the norm.
+        Data parallel: the norm is taken where adamw_step reads the gradients, after the reducer; every rank holds the same reduced bits and
+        computes the same coefficient, nothing is communicated."""
+        max_norm = float(max_norm)
+        if not max_norm > 0.0:
+            raise ValueError(f"max_norm = {max_norm} (a positive number, or inf for the non-finite guard alone)")
+        bufs = [g for st in self.stores for g in st.flat_grad.values()]
+        self._grad_clip = dict(max_norm=max_norm, skip_nonfinite=bool(skip_nonfinite),
+                               slots=torch.zeros(len(bufs), dtype=torch.float64, device=self.device), state=ops.grad_clip_state(self.device),
+                               workspace=torch.zeros(max(1, max(ops.grad_sumsq_workspace_elems(g.numel()) for g in bufs)), dtype=torch.float64,
+                                                     device=self.device))
+
+    def grad_clip_stats(self) -> Dict[str, float]:
+        """The state of the last adamw_step and the counters, {norm, coef, skipped, clipped, steps}.  The feature's ONLY readback: it waits for
+        the device, so call it where the host synchronises anyway (the driver does at its logging steps)."""
+        if self._grad_clip is None:
+            raise RuntimeError("grad_clip_stats without enable_grad_clip()")
+        s = ops.read_grad_clip_state(self._grad_clip["state"])
+        return {"norm": s["norm"], "coef": s["coef"], "skipped": s["skipped"], "clipped": s["clipped"], "steps": s["steps"]}
+
+    def load_grad_clip_state_dict(self, sd: Dict[str, torch.Tensor]) -> bool:
+        """Restores the three counters from the `grad_clip.` entries of an optimizer state dict into an engine with the feature enabled.
+        False, and nothing changes, when `sd` has none (written by a run without it: the counters stay where they are, 0 in a fresh engine)."""
+        if self._grad_clip is None or "grad_clip.steps" not in sd:
+            return False
+        counters = [int(sd[f"grad_clip.{k}"].item()) for k in ("steps", "clipped", "skipped")]
+        self._grad_clip["state"][3:6].copy_(torch.tensor(counters, dtype=torch.int32))
+        return True
 
     # -- weight EMA: fp32 shadows of every store's flat buffers, updated after the optimizer step, swapped in for evaluation and export -----------
     _ema_scope = False   # true while ema_weights() holds the averaged weights in the flat buffers
@@ -1620,6 +1682,10 @@ class VLAEngine:
             for i, st in enumerate(self.stores):
                 for dt, shadow in st.ema_shadow.items():
                     out[f"ema.store{i}.{'bf16' if dt == BF16 else 'f32'}.shadow"] = shadow
+        if self.grad_clip_enabled:   # the counters of the clip / skip statistics (read back here: a checkpoint waits for the device anyway)
+            stats = self.grad_clip_stats()
+            for k in ("steps", "clipped", "skipped"):
+                out[f"grad_clip.{k}"] = torch.tensor([stats[k]], dtype=torch.int64)
         return out
 
     def load_optimizer_state_dict(self, sd: Dict[str, torch.Tensor]):
@@ -1640,6 +1706,8 @@ class VLAEngine:
                     buf.copy_(src.to(buf.device, buf.dtype))
         if self.ema_enabled:
             self.load_ema_state_dict(sd)
+        if self.grad_clip_enabled:
+            self.load_grad_clip_state_dict(sd)
 
     def load_ema_state_dict(self, sd: Dict[str, torch.Tensor]) -> bool:
         """Restores the shadows and the EMA step from the `ema.` entries of an optimizer state dict into an engine with EMA enabled.

@@ -1116,6 +1116,60 @@ def ema_update(param, shadow, one_minus_decay):
     _lib.call("ovla_ema_update", g, _stream())
 
 
+# -- gradient-norm clipping and the non-finite step guard (ovla.h "Gradient-norm clipping") ---------------------------------------------------
+GRAD_SUMSQ_CHUNK = 8192   # OVLA_GRAD_SUMSQ_CHUNK: elements one workgroup reduces to one partial
+
+
+def grad_sumsq_workspace_elems(n: int) -> int:
+    """Doubles of workspace ovla_grad_sumsq needs for n elements (one partial per chunk)."""
+    return (int(n) + GRAD_SUMSQ_CHUNK - 1) // GRAD_SUMSQ_CHUNK
+
+
+def grad_clip_state(device):
+    """A zeroed device ovla_grad_clip_state as six 32-bit words: (coef, norm) fp32, then skip, n_steps, n_clipped, n_skipped int32."""
+    assert ctypes.sizeof(STRUCTS["ovla_grad_clip_state"]) == 24
+    return torch.zeros(6, dtype=torch.int32, device=device)
+
+
+def read_grad_clip_state(state) -> dict:
+    """The state on the host (this synchronises): {norm, coef, skip, steps, clipped, skipped}."""
+    raw = state.detach().cpu().contiguous().numpy().tobytes()
+    s = STRUCTS["ovla_grad_clip_state"].from_buffer_copy(raw)
+    return {"norm": float(s.norm), "coef": float(s.coef), "skip": int(s.skip), "steps": int(s.n_steps), "clipped": int(s.n_clipped),
+            "skipped": int(s.n_skipped)}
+
+
+def grad_sumsq(grad, slots, slot, workspace, *, is_bf16, grad_scale=1.0, n=None):
+    """slots[slot] <- sum of squares, in double and in the contract's fixed order, of the first n (default: all) elements of the flat fp32
+    gradient buffer `grad` as AdamW sees them (times grad_scale, rounded to bf16 for a bf16 parameter buffer)."""
+    assert grad.dtype == torch.float32 and slots.dtype == torch.float64 and workspace.dtype == torch.float64
+    assert grad.is_contiguous() and slots.is_contiguous() and workspace.is_contiguous() and 0 <= slot < slots.numel()
+    g = STRUCTS["ovla_grad_sumsq_args"]()
+    g.grad, g.n, g.is_bf16, g.grad_scale = grad.data_ptr(), grad.numel() if n is None else n, int(is_bf16), grad_scale
+    g.slots, g.slot, g.workspace, g.workspace_bytes = slots.data_ptr(), slot, workspace.data_ptr(), workspace.numel() * 8
+    _lib.call("ovla_grad_sumsq", g, _stream())
+
+
+def grad_clip_coef(slots, state, max_norm, skip_nonfinite=True, n_slots=None):
+    """state <- norm over slots[0 .. n_slots), clip coefficient, skip flag and counters (one tiny launch, nothing read back)."""
+    assert slots.dtype == torch.float64 and slots.is_contiguous() and state.dtype == torch.int32 and state.numel() == 6 and state.is_contiguous()
+    g = STRUCTS["ovla_grad_clip_coef_args"]()
+    g.slots, g.n_slots, g.max_norm, g.skip_nonfinite, g.state = slots.data_ptr(), slots.numel() if n_slots is None else n_slots, max_norm, int(skip_nonfinite), state.data_ptr()
+    _lib.call("ovla_grad_clip_coef", g, _stream())
+
+
+def adamw_clipped(param, exp_avg, exp_avg_sq, grad, state, *, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.01, grad_scale=1.0):
+    """ops.adamw on the gradient scaled by the state's coefficient; changes nothing when the state says skip."""
+    g = STRUCTS["ovla_adamw_clipped_args"]()
+    g.param, g.exp_avg, g.exp_avg_sq, g.grad = param.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), grad.data_ptr()
+    g.n, g.is_bf16, g.step = param.numel(), int(param.dtype == BF16), step
+    g.lr, g.beta1, g.beta2, g.eps, g.weight_decay, g.grad_scale = lr, beta1, beta2, eps, weight_decay, grad_scale
+    g.clip_state = state.data_ptr()
+    assert grad.dtype == torch.float32 and exp_avg.dtype == param.dtype and exp_avg_sq.dtype == param.dtype
+    assert state.dtype == torch.int32 and state.numel() == 6
+    _lib.call("ovla_adamw_clipped", g, _stream())
+
+
 def cvt_f32_to_bf16(src, dst=None, scale=1.0):
     if dst is None:
         dst = torch.empty(src.shape, dtype=BF16, device=src.device)

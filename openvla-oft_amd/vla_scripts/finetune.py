@@ -17,6 +17,7 @@ from __future__ import annotations
 
 import contextlib
 import json
+import math
 import os
 from dataclasses import dataclass
 from pathlib import Path
@@ -312,6 +313,20 @@ def load_ema_state(ckpt: Path, log_step: Optional[int], engine: VLAEngine) -> bo
     return engine.load_ema_state_dict(ema)
 
 
+def load_grad_clip_state(ckpt: Path, log_step: Optional[int], engine: VLAEngine) -> bool:
+    """Reads the `grad_clip.` counters of a checkpoint's optimizer-state file into an engine that has gradient clipping enabled (the resume
+    load runs before enable_grad_clip).  False -- and nothing is changed -- when the file is absent or holds none."""
+    suffix = "latest_checkpoint" if log_step is None else f"{log_step}_checkpoint"
+    opt = Path(ckpt) / f"optimizer_state--{suffix}.safetensors"
+    if not opt.is_file():
+        return False
+    from safetensors import safe_open
+
+    with safe_open(str(opt), framework="pt", device="cpu") as f:
+        sd = {k: f.get_tensor(k) for k in f.keys() if k.startswith("grad_clip.")}
+    return engine.load_grad_clip_state_dict(sd)
+
+
 def sampled_l1_metrics(engine: VLAEngine, batch: dict) -> Dict[str, float]:
     """finetune.py:410-448 for the diffusion objective: a chunk sampled by the whole reverse diffusion (VLAEngine.sample_actions, no host round
     trip between its steps) against the ground truth -- L1 of chunk step 0 and of the rest.  The two `.item()` are the only synchronisation."""
@@ -352,7 +367,8 @@ def run_validation(engine: VLAEngine, cfg: FinetuneConfig, val_batches: Iterable
 def finetune(cfg: FinetuneConfig, *, model_config: VLAConfig = OPENVLA_7B, state_dict: Optional[Dict[str, torch.Tensor]] = None,
              dataset: Optional[Iterable[dict]] = None, dataset_statistics: Optional[dict] = None, log=print, tokenizer=None,
              val_dataset=None, diffusion_noise: str = "host", ema_decay: Optional[float] = None, ema_power: Optional[float] = 0.75,
-             ema_inv_gamma: float = 1.0, ema_update_after: int = 0) -> Dict[str, list]:
+             ema_inv_gamma: float = 1.0, ema_update_after: int = 0, max_grad_norm: Optional[float] = None,
+             skip_nonfinite_steps: bool = True) -> Dict[str, list]:
     """finetune.py:763-1154.  Returns the logged metric history.  Data source, in this order: `dataset` (any iterable of collated
     batches); an episode store at `cfg.data_root_dir / cfg.dataset_name` (prismatic/vla/datasets/rlds_free.py: the reference's
     RLDSDataset + RLDSBatchTransform + collator, finetune.py:981-1016, with the frames augmented and normalised on the device --
@@ -367,7 +383,18 @@ def finetune(cfg: FinetuneConfig, *, model_config: VLAConfig = OPENVLA_7B, state
     -- runs on the averaged weights, the training-time sampling stays on the live ones; every checkpoint holds the shadows (optimizer-state
     file, so a resumed run continues shadow and schedule) and an `ema/` sub-directory that serves and merges like any fine-tune output.  The
     shadows are rank-local: the parameters are identical on every rank after the all-reduced step, so the shadows are too, and nothing is
-    communicated.  With `ema_decay=None` nothing of this runs."""
+    communicated.  With `ema_decay=None` nothing of this runs.
+    `max_grad_norm` clips the global norm of the gradients (every trainable tensor, after the all-reduce and the 1 / world scaling, in the
+    parameter's precision) as torch.nn.utils.clip_grad_norm_ does, and `skip_nonfinite_steps` makes a step whose norm is NaN or Inf a no-op for
+    parameters and AdamW moments -- both on the device, in front of the fused AdamW (VLAEngine.enable_grad_clip), with no readback: the
+    host does not learn of a skip, so a skipped step still consumes its step number in the bias correction and the LR schedule, and the EMA
+    update after it averages the unchanged parameters.  `max_grad_norm=None` with the guard on means the guard alone (max_norm = inf); with the
+    guard off as well nothing of this runs.  When it runs, the logging steps read the statistics back (the host waits there anyway) and the
+    history gains `grad_norm`, `grad_clip_coef` (both of that step) and `skipped_steps` (the running count); the optimizer-state file gains
+    the counters `grad_clip.steps / clipped / skipped`, which a resumed run continues."""
+    if max_grad_norm is not None and not float(max_grad_norm) > 0.0:   # NaN fails the comparison too
+        raise ValueError(f"max_grad_norm = {max_grad_norm} (a positive number, or None)")
+    grad_clip = max_grad_norm is not None or bool(skip_nonfinite_steps)
     if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:
         raise ValueError(f"ema_decay = {ema_decay} is outside [0, 1)")
     if diffusion_noise not in ("host", "device"):
@@ -422,6 +449,12 @@ def finetune(cfg: FinetuneConfig, *, model_config: VLAConfig = OPENVLA_7B, state
             resumed_ema = load_ema_state(Path(cfg.vla_path), cfg.resume_step, engine)
             log(f"[finetune] weight EMA continues at update {engine.ema_step}" if resumed_ema else
                 "[finetune] the checkpoint holds no EMA state (trained without ema_decay): the shadow starts at the loaded parameters, ema_step = 0")
+    if grad_clip:
+        engine.enable_grad_clip(math.inf if max_grad_norm is None else float(max_grad_norm), skip_nonfinite=bool(skip_nonfinite_steps))
+        if cfg.resume:   # allocated after the load, like the EMA shadows: read the optimizer-state file's grad_clip.* counters now
+            resumed_clip = load_grad_clip_state(Path(cfg.vla_path), cfg.resume_step, engine)
+            log(f"[finetune] gradient clipping continues its counters: {engine.grad_clip_stats()}" if resumed_clip else
+                "[finetune] the checkpoint holds no grad_clip counters: they start at 0")
     reducer = GradReducer(engine.stores, world) if world > 1 else None
     engine.attach_reducer(reducer, overlap=cfg.grad_accumulation_steps == 1 and os.environ.get("OVLA_DP_OVERLAP", "1") != "0")   # overlap only when every backward ends a step
     if dataset is None and (Path(cfg.data_root_dir) / cfg.dataset_name).is_dir():
@@ -473,6 +506,8 @@ def finetune(cfg: FinetuneConfig, *, model_config: VLAConfig = OPENVLA_7B, state
         history.update({"curr_action_l1_loss": [], "next_actions_l1_loss": []})
     if ema_decay is not None:
         history["ema_decay"] = []
+    if grad_clip:
+        history.update({"grad_norm": [], "grad_clip_coef": [], "skipped_steps": []})
 
     def make_diffusion(batch):   # DiffusionActionHead.sample_noisy_actions (action_heads.py:167-197)
         if device_noise:
@@ -524,8 +559,15 @@ def finetune(cfg: FinetuneConfig, *, model_config: VLAConfig = OPENVLA_7B, state
                 if discrete:
                     for k, v in token_metrics(batch, pred_ids).items():
                         history[k].append(v)
+                clip_note = ""
+                if grad_clip:   # the feature's only readback, where the loss was just read
+                    stats = engine.grad_clip_stats()
+                    history["grad_norm"].append(stats["norm"])
+                    history["grad_clip_coef"].append(stats["coef"])
+                    history["skipped_steps"].append(stats["skipped"])
+                    clip_note = f" grad_norm {stats['norm']:.4g} clip_coef {stats['coef']:.4g} skipped {stats['skipped']}"
                 if rank == 0:
-                    log(f"step {log_step}: loss {history['loss_value'][-1]:.5f} lr {lr:.2e}")
+                    log(f"step {log_step}: loss {history['loss_value'][-1]:.5f} lr {lr:.2e}{clip_note}")
             if cfg.use_val_set and log_step > 0 and log_step % cfg.val_freq == 0:   # finetune.py:1128-1144
                 with engine.ema_weights() if ema_decay is not None else contextlib.nullcontext():   # validation sees the averaged weights
                     history["val"].append((log_step, run_validation(engine, cfg, val_dataset(), log_step, log if rank == 0 else (lambda *_: None), discrete=discrete,
