@@ -186,26 +186,6 @@ int ovla_gemm_tn_bf16(const ovla_gemm_tn_args* a, void* stream);
 int ovla_gemm_tn_grouped(const ovla_gemm_tn_args* problems, int32_t n, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
- * LoRA backward, the two products that stream dy, in ONE pass over it (peft LoRA r = 32 on every nn.Linear, finetune.py:862-871; autograd's
- * backward of `result + lora_B(lora_A(x)) * scaling`):
- *     dt[:, g r : (g+1) r]  = bf16(scale * dy_g . B_g)        dy_g = dy[:, g gn : (g+1) gn], B_g [gn, r] given transposed (Bt rows g r ..)
- *     dB[g gn : (g+1) gn]  += dy_g^T . t[:, g r : (g+1) r]    fp32, atomically accumulated (dB must hold the running sum)
- * for the G fused groups of one adapted Linear (q|k|v: 3, gate|up: 2).  dt partial sums of the 256-column chunks go through the fp32
- * workspace and are added in a fixed order: dt is bit-reproducible run to run.  r must be 32. */
-typedef struct {
-  const void* dy; int64_t ld_dy;   /* bf16 [M, G*gn] */
-  const void* Bt; int64_t ld_bt;   /* bf16 [G*r, gn]: B_g^T stacked */
-  const void* t;  int64_t ld_t;    /* bf16 [M, G*r]: the forward's saved  scale * x . A_g^T */
-  void* dt; int64_t ld_dt;         /* out bf16 [M, G*r] */
-  float* dB; int64_t ld_db;        /* in/out fp32 [G*gn, r] */
-  int32_t M, gn, G, r;
-  float scale;
-  void* workspace; int64_t workspace_bytes;   /* >= ovla_lora_bwd_workspace_bytes(M, gn, G), 16-byte aligned */
-} ovla_lora_bwd_args;
-int64_t ovla_lora_bwd_workspace_bytes(int32_t M, int32_t gn, int32_t G);
-int ovla_lora_bwd(const ovla_lora_bwd_args* a, void* stream);
-
-/* ------------------------------------------------------------------------------------------------------------------
  * Multi-adapter serving: n LoRA adapters ("slots", one per fine-tuned policy) in ONE K-extended GEMM launch.  peft applies one adapter per
  * model, `result + lora_B(lora_A(x)) * scaling` (finetune.py:862-871); here the projection GEMM runs against the n adapters' stacked A
  * (t [M, G*n*r], group-major: group g owns columns [g n r, (g+1) n r), slot s inside it [s r, (s+1) r)) and ovla_lora_route then stores bf16 +0
@@ -602,37 +582,6 @@ typedef struct {
   int32_t rows, dim, adim;
 } ovla_head_out_bwd_args;
 int ovla_head_out_bwd(const ovla_head_out_bwd_args* a, void* stream);
-
-/* The fused L1 / diffusion action-head tail (`north_star`: "a fused L1 action-head"): everything of MLPResNet.forward after fc1
- * (prismatic/models/action_heads.py:72-81, 49-56) and the loss of finetune.py:400 / :407 in ONE launch, for up to 64 rows (batch 8 x chunk 8):
- *     for b in 0, 1:   x <- x + relu(fc_b(LayerNorm_b(x)))           (MLPResNetBlock: ffn = LN -> Linear -> ReLU, residual outside)
- *     h2 = LayerNorm_2(x);  pred = fc2(h2);  loss_sum += sum |pred - target|   (or squared, mse)
- * dim / 16 <= 256 workgroups, all resident.  Five stages: LayerNorm rows of block 0 | GEMM 0 + epilogue | LayerNorm rows of block 1 | GEMM 1 +
- * epilogue | LayerNorm 2 + fc2 + loss.  LayerNorm stages deal ROWS over the workgroups and write the normalised rows (hb: the Linear's saved
- * input); GEMM stages deal 16-column strips: a workgroup streams ITS 16 weight rows from HBM once (each 33.5 MB matrix crosses HBM once,
- * spread over the chip) and reads the R x dim normalised rows from L2, one wave per 16-row MFMA tile.  The stages are separated by four
- * grid-wide barriers: agent-scope release / arrival counter / bounded spin / agent-scope acquire (the arrival counter sync[0] is zeroed by a memset
- * node ahead of the launch; a spin that runs out fills pred, loss_sum and every saved buffer with NaN and sets sync[1], which NO launch clears:
- * the host reads it where it already synchronises).  The launch is refused unless the whole grid can be co-resident
- * (ovla_head_tail_resident_blocks() = occupancy x compute units >= dim / 16 workgroups).
- * Arithmetic, rounding points AND summation orders are those of the unfused sequence (ovla_norm_fwd, ovla_gemm_bf16 with split_k = 2 and
- * its reduce epilogue, ovla_head_out_fwd): results are bit-identical to it (tests/test_kernels_gpu.py).
- * Everything the backward needs is written out when the pointers are given (training): per block the LayerNorm output hb (the Linear's
- * saved input), the pre-activation zb and mean / rstd; h2, mean2, rstd2.  rows = R must be a multiple of 16 (<= 64; pad with zero rows),
- * rows_real <= R rows enter pred / loss.  All [R, dim] buffers contiguous bf16; W_b [dim, dim] row-major [out, in]. */
-typedef struct {
-  const void* x0;                                   /* [R, dim] input of block 0 (= relu(fc1(LN1(.)))) */
-  const void* ln_w[2]; const void* ln_b[2]; const void* W[2]; const void* bias[2];
-  void* hb[2]; void* zb[2]; void* xo[2];            /* hb (LayerNorm output) and xo (block output) required; zb optional (training) */
-  float* mean[2]; float* rstd[2];                   /* optional, [R] */
-  const void* ln2_w; const void* ln2_b; void* h2; float* mean2; float* rstd2;   /* h2 required ([R, dim]); stats optional */
-  const void* W2; const void* b2; void* pred; const void* target; float* loss_sum;   /* W2 [adim, dim]; target / loss_sum optional */
-  uint32_t* sync;                                   /* device, >= 2 words: arrival counter (reset per launch), STICKY timeout flag */
-  int32_t rows, rows_real, dim, adim, mse, ksplit;  /* ksplit 1 | 2: accumulate K in that many halves, summed in order (= split_k of the unfused GEMM) */
-  float eps;
-} ovla_head_tail_args;
-int ovla_head_tail_resident_blocks(void);          /* workgroups of the fused tail that fit on the current device at once (0: unknown / no device) */
-int ovla_head_tail_fwd(const ovla_head_tail_args* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Fused AdamW over a flat parameter buffer (torch.optim.AdamW as called at finetune.py:952: betas (0.9,0.999),

@@ -90,7 +90,7 @@ OVLA_DEV float act_grad(float z, int act) {
 }
 
 // LayerNorm output element, y = (x - mean) * rstd * w + b in fp32 with ONE explicit fma (every kernel that normalises -- the row kernels of
-// elementwise.hip and the fused head tail of head_optim.hip -- goes through this function, so they agree bit for bit by construction).
+// elementwise.hip -- goes through this function, so they agree bit for bit by construction).
 OVLA_DEV float ln_affine(float x, float mean, float rstd, float w, float b) { return __builtin_fmaf((x - mean) * rstd, w, b); }
 
 // multi-policy serving: the adapter slot an observation is routed to, read from a device array and clamped, so that no index formed from it leaves a buffer

@@ -43,29 +43,12 @@ _FUSE = os.environ.get("OVLA_FUSE_DACT", "none")
 _FUSE_ROPE_FWD = os.environ.get("OVLA_FUSE_ROPE_FWD", "1") == "1"
 _GROUP_TN = os.environ.get("OVLA_GROUP_TN", "1") == "1"   # ViT blocks: two neighbouring linears' LoRA weight-gradient problems in one launch (A/B switch)
 _FUSE_ACT, _FUSE_SWIGLU = _FUSE in ("act", "all"), _FUSE in ("swiglu", "all")
-# The action head's tail (two MLPResNet blocks, LayerNorm 2, fc2, L1 / MSE loss) as ONE launch for up to 64 rows (ovla_head_tail_fwd),
-# bit-identical to the unfused eight-launch sequence.  OPT-IN (OVLA_FUSE_HEAD=1) since round 3: it never measured faster -- round 2: equal at 64
-# rows, 50 us slower per replayed inference chunk; round 3, after an 8-deep register ring on its weight / activation streams (kernel 148.8 ->
-# 114.6 us): whole head forward 219.8 vs 209.6 us unfused at 64 rows, 186.1 vs 169.6 us at 8 rows (tools/head_bench.py,
-# profiles/r03_head_bench.txt) -- four software grid barriers cost more than the eight kernel boundaries they replace, and a software grid
-# barrier needs every workgroup resident at once: the launch is refused otherwise, a timed-out spin poisons every output with NaN and sets a
-# sticky word that ActionHead.check_fused_tail() turns into an exception at the step's host sync.
-_FUSE_HEAD = {"0": False, "1": True}.get(os.environ.get("OVLA_FUSE_HEAD", "auto"), None)
 # OVLA_ASYNC_UPLOAD=0: upload ids / labels / lengths with synchronous pageable copies as before (A/B switch of VLAEngine.forward's pinned upload)
 _ASYNC_UPLOAD = os.environ.get("OVLA_ASYNC_UPLOAD", "1") != "0"
 # OVLA_FOLD_RMSNORM=0: keep the decoder's RMSNorms as their own launches on the merged inference path (A/B switch of LlamaStack.fold_norms).
 _FOLD_RMSNORM = os.environ.get("OVLA_FOLD_RMSNORM", "1") != "0"
 # OVLA_INFER_W4=0: the folded inference path's projections take the planner's tile instead of the 4-wave 128x256 configuration (A/B switch of LlamaStack._infer_tile)
 _INFER_W4 = os.environ.get("OVLA_INFER_W4", "1") != "0"
-# OVLA_FUSE_SWIGLU_FWD=1: the decoder's gate|up projection and SwiGLU become one launch in the unfolded forward too (OVLA_ACT_SWIGLU on the 256x256 tile, C_pre keeps
-# the [M, 2F] projection output for the backward).  Bit-identical; measured neutral on the fine-tune step (158.1 / 158.5 vs 158.0 / 158.0 ms: the read-back that saves
-# the swiglu_fwd launch is itself bound by the tile's stores), so it stays off there; the folded batch-1 path always fuses (LlamaStack._infer_tile).
-_FUSE_SWIGLU_FWD = os.environ.get("OVLA_FUSE_SWIGLU_FWD", "0") == "1"
-# OVLA_LORA_BWD=1: the LoRA backward's dt and dB from ONE pass over dy (csrc/lora_bwd.hip) instead of a skinny NT GEMM (dt) + TN GEMMs (dB, dA).
-# Built, parity-tested and measured in round 3 (tools/lora_bwd_bench.py, cold operands, M = 4864): 293.6 vs 272.4 us per decoder layer for the
-# three-kernel path -- reading dy once saves 0.4 GB per layer, but a 2-D (rows x 256-column) decomposition pays it back as fp32 partial-dt slabs
-# (+25 % of dy's bytes, written and read) and dB atomics (+21 %, at a quarter of the streaming rate); left OFF.
-_LORA_BWD_FUSED = os.environ.get("OVLA_LORA_BWD", "0") == "1"
 # OVLA_LORA_DROPOUT_FUSED=0: with lora_dropout > 0 the training forward materialises dropout_g(x) per fused group (ovla_lora_dropout_apply) and
 # projects each with an ordinary GEMM, instead of masking the fragments in registers (ovla_lora_dropout_proj).  Same masks; A/B switch.
 _LORA_DROPOUT_FUSED = os.environ.get("OVLA_LORA_DROPOUT_FUSED", "1") != "0"
@@ -540,16 +523,11 @@ class LoraLinear:
             raise RuntimeError(f"{self.name}: LoRA adapters were merged into the base weight; this engine is inference-only")
         if self.has_lora:
             r, G, gn = self.r, self.groups, self.group_n
-            if _LORA_BWD_FUSED and r == 32 and dy.shape[0] >= 512:
-                # ONE pass over dy: dt = s * dy_g . B_g and dB_g += dy_g^T t_g together (csrc/lora_bwd.hip); only dA += dt^T x is left to the TN GEMM
-                dt = ops.lora_bwd(dy, self.BT, t_s, self.B.grad, gn=gn, G=G, scale=self.scale)
-                probs = [(dt, x, self.A.grad)]
-            else:
-                # dt[:, g] = s * dy_g . B_g for every fused group in ONE block-diagonal skinny GEMM
-                dt = ops.gemm(dy, self.BT, alpha=self.scale, a_group_n=r if G > 1 else 0)
-                # dB_g += dy_g^T t_g ; dA += dt^T x : one grouped launch
-                probs = [(dy[:, g * gn:(g + 1) * gn], t_s[:, g * r:(g + 1) * r], self.B.grad[g * gn:(g + 1) * gn]) for g in range(G)]
-                probs.append((dt, x, self.A.grad))
+            # dt[:, g] = s * dy_g . B_g for every fused group in ONE block-diagonal skinny GEMM
+            dt = ops.gemm(dy, self.BT, alpha=self.scale, a_group_n=r if G > 1 else 0)
+            # dB_g += dy_g^T t_g ; dA += dt^T x : one grouped launch
+            probs = [(dy[:, g * gn:(g + 1) * gn], t_s[:, g * r:(g + 1) * r], self.B.grad[g * gn:(g + 1) * gn]) for g in range(G)]
+            probs.append((dt, x, self.A.grad))
             if drop_call is not None:
                 # dA_g += dt_g^T dropout_g(x): the dropped input is regenerated into a buffer of its own (not a fixed workspace: tn_queue may launch
                 # the problem later, and the two towers run on two streams)
@@ -850,12 +828,6 @@ class LlamaStack:
         self.folded = True
         self._fold_plan = {}
 
-    def _swiglu_pair_ok(self, lin) -> bool:
-        """OVLA_ACT_SWIGLU's shape rules (ovla.h): F a multiple of 128, K of 64, LoRA rank 32 grouped by F (or merged / absent), no bias."""
-        F, D = self.cfg.llm_ff, self.cfg.llm_dim
-        live = lin.has_lora and not getattr(lin, "merged", False)
-        return F % 128 == 0 and D % 64 == 0 and lin.bias is None and (not live or (lin.r == 32 and lin.groups == 2))
-
     def _infer_tile(self, M: int) -> int:
         """Tile configuration of the folded inference path's four projections.  A few hundred rows (the batch-1 chunk: M = 608 = 4.75 row tiles of 128): the
         4-wave 128x256 configuration with the hand-scheduled K loop (ovla.h tile 122: -9...-16 % per projection on cold weights, tools/cold_gemm_probe.py);
@@ -951,14 +923,8 @@ class LlamaStack:
             else:
                 x2, s_o = l["o"].fwd(o, residual=x)
             h2, _, r2 = ops.norm_fwd(x2, l["n2"], eps=cfg.rms_eps, rms=True, save_stats=train)
-            if _FUSE_SWIGLU_FWD and x2.shape[0] >= 256 and not invariant and self._swiglu_pair_ok(l["gu"]):
-                # gate|up + SwiGLU in ONE launch (ovla.h OVLA_ACT_SWIGLU on the 4-wave 256x256 configuration): h comes out of the projection's read-back;
-                # the [M, 2F] projection output is still written (C_pre) when the backward needs it, but never read again in the forward
-                gu = torch.empty((x2.shape[0], 2 * F), dtype=BF16, device=x.device) if train else None
-                hm, s_gu = l["gu"].fwd(h2, act=ops.ACT_SWIGLU, c_pre=gu)
-            else:
-                gu, s_gu = l["gu"].fwd(h2)
-                hm = ops.swiglu_fwd(gu)
+            gu, s_gu = l["gu"].fwd(h2)
+            hm = ops.swiglu_fwd(gu)
             x3, s_d = l["down"].fwd(hm, residual=x2)
             if train:
                 saved.append((x, r1, s_qkv, qkv, o, lse, s_o, x2, r2, s_gu, gu, s_d))
@@ -1046,29 +1012,6 @@ class ActionHead:
         z1 = torch.empty((rows, cfg.llm_dim), dtype=BF16, device=x0.device) if train else None
         split = 8 if rows <= 256 else 1      # small-M weight stream: split K over the chip
         x, s1 = self.fc1.fwd(h0, act=ops.ACT_RELU, c_pre=z1, split_k=split)
-        D = cfg.llm_dim
-        if bool(_FUSE_HEAD) and rows <= 64 and not ops.batch_invariant_enabled() and D % 64 == 0 and D // 16 <= 256 and (D // 16) % 4 == 0 and \
-                _lib.lib().ovla_head_tail_resident_blocks() >= D // 16:      # software grid barriers: only when the whole grid is co-resident
-            # everything after fc1 -- both MLPResNet blocks, LayerNorm 2, fc2 and the loss -- is ONE launch (ovla_head_tail_fwd), bit-identical
-            # to the unfused sequence below; its backward is the unfused one, fed from the tensors the kernel saves
-            R = (rows + 15) // 16 * 16
-            if R != rows:
-                xp = torch.zeros((R, D), dtype=BF16, device=x.device)
-                xp[:rows] = x
-                x_in = xp
-            else:
-                x_in = x
-            if getattr(self, "_sync", None) is None:
-                self._sync = torch.zeros(2, dtype=torch.int32, device=x.device)
-            loss_sum = torch.zeros(1, dtype=F32, device=x0.device) if target is not None else None
-            o = ops.head_tail_fwd(x_in, [(b["ln_w"].data, b["ln_b"].data, b["fc"].Wc, b["fc"].bc) for b in self.blocks], (self.ln2_w.data, self.ln2_b.data),
-                                  self.out_w.data, self.out_b.data, rows_real=rows_real, target=target, loss_sum=loss_sum, mse=mse, train=train, sync=self._sync)
-            saved = None
-            if train:
-                xs = [x_in[:rows], o["xo"][0][:rows]]
-                blocks_saved = [(xs[b], o["mean"][b][:rows], o["rstd"][b][:rows], o["zb"][b][:rows], (o["hb"][b][:rows],)) for b in range(2)]
-                saved = (x0, m0, r0, z1, s1, blocks_saved, o["xo"][1][:rows], o["mean2"][:rows], o["rstd2"][:rows], o["h2"][:rows], o["pred"], target, mse, rows_real)
-            return o["pred"], loss_sum, saved
         blocks_saved = []
         for b in self.blocks:
             hb, mb, rb = ops.norm_fwd(x, b["ln_w"].data, b["ln_b"].data, eps=1e-5, rms=False, save_stats=train)
@@ -1083,15 +1026,8 @@ class ActionHead:
         saved = (x0, m0, r0, z1, s1, blocks_saved, x, m2, r2, h2, pred, target, mse, rows_real) if train else None
         return pred, loss_sum, saved
 
-    def check_fused_tail(self):
-        """Host-side check of the fused tail's sticky timeout word (ovla_head_tail_args.sync[1]): call where the step already synchronises
-        (loss.item()).  A timed-out grid barrier has already turned the loss, the predictions and every saved buffer into NaN; this turns it
-        into an exception and clears the word."""
-        sync = getattr(self, "_sync", None)
-        if sync is not None and int(sync[1].item()) != 0:
-            sync[1] = 0
-            raise RuntimeError("ovla_head_tail_fwd: a grid barrier timed out (the workgroups were not co-resident); the step's head outputs are NaN. "
-                               "Set OVLA_FUSE_HEAD=0 to use the unfused sequence.")
+    def check_fused_tail(self):   # bench.py still calls this after its timed steps; it goes when that call does
+        pass
 
     def bwd(self, saved, dloss: float = 1.0, dpred=None):
         """Returns d(actions_hidden) [B*A_tokens, D]; accumulates the head's gradients.  With `dpred` (bf16

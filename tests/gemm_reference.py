@@ -1,4 +1,4 @@
-"""Exact operands, a float64 reference and bit-level checks for the GEMM kernels (`csrc/gemm_nt.hip`, `gemm_tn.hip`, `lora_bwd.hip`).
+"""Exact operands, a float64 reference and bit-level checks for the GEMM kernels (`csrc/gemm_nt.hip`, `gemm_tn.hip`).
 Nothing here needs a GPU.
 
 Why exact: bf16 x bf16 products of small integers are integers, and integers below 2^24 add exactly in fp32 in ANY order.  With the

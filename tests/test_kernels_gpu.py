@@ -759,13 +759,12 @@ def test_token_ce(ops, dev, rows, vocab, ld):
 
 @pytest.mark.parametrize("D,rows,adim,mse,train", [(256, 24, 7, False, True), (256, 8, 7, True, False), (4096, 64, 7, False, True), (4096, 8, 7, False, False),
                                                    (1024, 56, 14, True, True)])
-def test_fused_head_tail_is_bit_identical_to_the_unfused_sequence(dev, D, rows, adim, mse, train):
-    """ovla_head_tail_fwd (two MLPResNet blocks -> LayerNorm 2 -> fc2 -> L1 / MSE loss in ONE launch, grid-wide barriers between the stages)
-    against the unfused kernel sequence the engine ran before (ovla_norm_fwd, ovla_gemm_bf16 split_k = 2 + reduce epilogue, ovla_head_out_fwd):
-    predictions, loss and EVERY tensor saved for the backward are bit-identical; and against plain torch fp32 within bf16 tolerance."""
+def test_action_head_forward_matches_torch(dev, D, rows, adim, mse, train):
+    """ActionHead.fwd (LayerNorm 1 -> fc1 -> two MLPResNet blocks -> LayerNorm 2 -> fc2 -> L1 / MSE loss: ovla_norm_fwd, ovla_gemm_bf16 with split K
+    and its reduce epilogue, ovla_head_out_fwd) against plain torch fp32 within bf16 tolerance; in training mode the backward off the saved
+    tensors gives finite gradients and a bit-reproducible d(actions_hidden)."""
     import dataclasses
     import importlib
-    import os
 
     load = importlib.import_module
     engine_mod, config_mod = load("openvla-oft_amd.engine"), load("openvla-oft_amd.config")
@@ -781,35 +780,18 @@ def test_fused_head_tail_is_bit_identical_to_the_unfused_sequence(dev, D, rows, 
     head = engine_mod.build_component(engine_mod.ActionHead, dev, get, hp, cfg=cfg)
     ah = (torch.randn(rows * adim, D, generator=g) * 0.7).to(dev, BF)
     tgt = (torch.rand(rows, adim, generator=g) * 2 - 1).to(dev, BF)
-    outs = {}
-    for fused in (True, False):
-        engine_mod._FUSE_HEAD = fused
-        try:
-            pred, loss_sum, saved = head.fwd(ah, target=tgt, mse=mse, train=train)
-        finally:
-            engine_mod._FUSE_HEAD = {"0": False, "1": True}.get(os.environ.get("OVLA_FUSE_HEAD", "auto"), None)
-        torch.cuda.synchronize()
-        outs[fused] = (pred.clone(), loss_sum.clone(), saved)
-    assert int(head._sync[1].item()) == 0, "a grid barrier of the fused kernel timed out"
-    (pf, lf, sf), (pu, lu, su) = outs[True], outs[False]
-    assert torch.equal(pf, pu), f"pred: {(pf != pu).sum().item()} of {pf.numel()} differ"
-    assert abs(lf.item() - lu.item()) <= 1e-6 * max(1.0, abs(lu.item())), "loss: same addends, atomic order only"
+    pf, loss_sum, saved = head.fwd(ah, target=tgt, mse=mse, train=train)
+    assert torch.isfinite(loss_sum).all()
     if train:
-        names = ["x0", "m0", "r0", "z1", "s1", "blocks", "x_last", "m2", "r2", "h2", "pred"]
-        for nm, a, b in zip(names, sf, su):
-            if nm == "blocks":
-                for bi, (ba, bb) in enumerate(zip(a, b)):
-                    for k, (ta, tb) in enumerate(zip(ba[:4] + ba[4], bb[:4] + bb[4])):
-                        assert torch.equal(ta, tb), f"block {bi} saved tensor {k}: {(ta != tb).sum().item()} differ"
-            elif torch.is_tensor(a):
-                assert torch.equal(a, b), f"{nm}: {(a != b).sum().item()} of {a.numel()} differ"
-        # and the backward runs off the fused kernel's saved tensors
         head.store.zero_grad()
-        d1 = head.bwd(sf).clone()
+        d1 = head.bwd(saved).clone()
         g1 = {k: v.clone() for k, v in head.store.flat_grad.items()}
+        assert torch.isfinite(d1.float()).all() and all(torch.isfinite(v).all() for v in g1.values())
+        p2, _, saved2 = head.fwd(ah, target=tgt, mse=mse, train=True)
         head.store.zero_grad()
-        d2 = head.bwd(su)
-        assert torch.equal(d1, d2) and all(torch.allclose(g1[k], head.store.flat_grad[k], rtol=1e-5, atol=1e-7) for k in g1)
+        d2 = head.bwd(saved2)
+        assert torch.equal(pf, p2) and torch.equal(d1, d2), "the head's forward and d(actions_hidden) are bit-reproducible run to run"
+        assert all(torch.allclose(g1[k], head.store.flat_grad[k], rtol=1e-5, atol=1e-7) for k in g1)
     # plain torch fp32 reference of the same head
     x = ah.float().cpu().view(rows, adim * D)
     F = torch.nn.functional
@@ -821,32 +803,6 @@ def test_fused_head_tail_is_bit_identical_to_the_unfused_sequence(dev, D, rows, 
     ref = F.linear(F.layer_norm(h, (D,), w("layer_norm2.weight"), w("layer_norm2.bias"), 1e-5), w("fc2.weight"), w("fc2.bias"))
     err = (pf.float().cpu() - ref).abs().max().item()
     assert err < 3e-2 * max(1.0, ref.abs().max().item()), err
-
-
-@pytest.mark.parametrize("M,gn,G", [(300, 264, 1), (1216, 512, 3), (4176, 1152, 1), (1000, 4304, 2)])
-def test_lora_bwd_one_pass(ops, dev, M, gn, G):
-    """ovla_lora_bwd: dt = bf16(s * dy_g . B_g) and dB_g += dy_g^T t_g from ONE staging of dy (peft LoRA backward, finetune.py:862-871), against
-    torch fp32 on the bf16-exact operands: ragged row counts, a column count that is no multiple of the 256-column chunk, fused groups, an
-    existing dB that is accumulated into; dt bit-identical between two runs (its chunk partials are added in a fixed order)."""
-    r, s = 32, 0.5
-    dy, t = rnd(M, G * gn, dev=dev), rnd(M, G * r, dev=dev)
-    Bt = rnd(G * r, gn, dev=dev, scale=0.3)
-    dB0 = torch.randn(G * gn, r, device=dev)
-    dB = dB0.clone()
-    dt = ops.lora_bwd(dy, Bt, t, dB, gn=gn, G=G, scale=s)
-    for g in range(G):
-        dyg, tg, Btg = dy[:, g * gn:(g + 1) * gn].float(), t[:, g * r:(g + 1) * r].float(), Bt[g * r:(g + 1) * r].float()
-        close(dt[:, g * r:(g + 1) * r], s * (dyg @ Btg.T), what=f"dt group {g}")
-        ref = dyg.T @ tg
-        err = ((dB[g * gn:(g + 1) * gn] - dB0[g * gn:(g + 1) * gn]) - ref).abs().max().item() / ref.abs().max().item()
-        assert err < 2e-5, f"dB group {g}: rel err {err:.3e} (fp32 accumulation of exact bf16 products)"
-    dB2 = dB0.clone()
-    dt2 = ops.lora_bwd(dy, Bt, t, dB2, gn=gn, G=G, scale=s)
-    assert torch.equal(dt, dt2), "dt must be bit-reproducible (it feeds the data-gradient chain)"
-    # and it equals what the two-kernel path computes, up to the bf16 rounding of differently ordered fp32 sums
-    dt_old = ops.gemm(dy, Bt, alpha=s, a_group_n=r if G > 1 else 0) if (G == 1 or gn % 128 == 0) else None
-    if dt_old is not None:
-        assert (dt.float() - dt_old.float()).abs().max().item() <= 2.0 ** -7 * dt_old.float().abs().max().item()
 
 
 @pytest.mark.parametrize("M,N,K,tile,rope", [(608, 1024, 512, 1, False), (608, 768, 1024, 1, True), (1000, 1024, 512, 101, False), (300, 640, 512, 101, True),

@@ -1,4 +1,4 @@
-"""The other matmul kernels (gemm_tn, gemm_tn_grouped, lora_bwd, colsum) with the exact operands of tests/gemm_reference.py: integer
+"""The other matmul kernels (gemm_tn, gemm_tn_grouped, colsum) with the exact operands of tests/gemm_reference.py: integer
 products add exactly in fp32 whatever the M split, the chunk order or the order atomics land in, so every fp32 result is compared with
 torch.equal against float64 and every bf16 one against its single rounding."""
 import pytest
@@ -48,29 +48,6 @@ def test_gemm_tn_grouped(ops, dev, n):
     ops.gemm_tn_grouped(probs)
     for (M, P, Q), (_, _, out), ref in zip(sizes, probs, refs):
         fails.exact(out, ref, f"grouped problem {M},{P},{Q} of {n}")
-    fails.done()
-
-
-@pytest.mark.parametrize("G", [1, 2, 3])
-def test_lora_bwd(ops, dev, G):
-    """gn below, just below, at and just beyond the 256-column chunk and over two chunks; M below and beyond the row blocks; scale a power of
-    two.  dt (bf16, one rounding of an exact sum) and dB (fp32 atomics onto a nonzero integer dB) are both exact; dt sits in a sentinel-filled
-    buffer whose guards stay untouched."""
-    fails = R.Failures()
-    g = R.rng(22000 + G)
-    r, scale = 32, 0.25
-    for gn in (8, 248, 256, 264, 520):
-        for M in (1, 31, 33, 300):
-            dy, Bt, t, dB0 = R.operand(g, M, G * gn), R.operand(g, G * r, gn), R.operand(g, M, G * r), R.bias_like(g, G * gn, r).float()
-            dB = dB0.to(dev)
-            dt = R.embed(BF, shape=(M, G * r), align=4, right=2, fill="sentinel", device=dev)
-            ops.lora_bwd(dy.to(dev), Bt.to(dev), t.to(dev), dB, gn=gn, G=G, scale=scale, dt=dt.view)
-            what = f"lora_bwd M {M} gn {gn} G {G}"
-            for k in range(G):
-                dyg, tg, Btg = dy[:, k * gn:(k + 1) * gn].double(), t[:, k * r:(k + 1) * r].double(), Bt[k * r:(k + 1) * r].double()
-                fails.exact(dt.view[:, k * r:(k + 1) * r], R.rbf(R._exact32(scale * (dyg @ Btg.T), "dt")).to(BF), what + f" dt group {k}")
-                fails.exact(dB[k * gn:(k + 1) * gn], _exact_f32(dyg.T @ tg + dB0[k * gn:(k + 1) * gn].double()), what + f" dB group {k}")
-            dt.assert_guards(what + " dt")
     fails.done()
 
 
