@@ -533,7 +533,10 @@ int ovla_assemble_multimodal(const ovla_assemble_args* a, void* stream);
  * input of the FIRST decoder layer (ovla_gemm_args.rowscale_part); later layers get theirs from the producing GEMM's epilogue (rowsq_out). */
 int ovla_row_sumsq(const void* x, int64_t ld, float* out, int32_t rows, int32_t dim, void* stream);
 
-/* dst[i, :] = src[index[i], :]  /  scatter-add backward  */
+/* dst[i, :] = src[index[i], :]  /  scatter-add backward dst[index[i], :] += src[i, :].
+ * An index < 0 means "no row" (ovla_assemble_multimodal leaves -1 in action_pos for an action slot the labels do not hold, and the labels
+ * may be device-resident, where no host check sees them): the gather writes a ZERO row at i, the scatter-add skips entry i.  Nothing is
+ * read or written outside src / dst for it.  An index beyond the last row is the caller's to exclude: the row count is not an argument. */
 typedef struct { const void* src; const int32_t* index; void* dst; int32_t n, dim; int64_t src_ld, dst_ld; int32_t scatter_add; } ovla_gather_rows_args;
 int ovla_gather_rows(const ovla_gather_rows_args* a, void* stream);
 

@@ -541,10 +541,14 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const bf16_bits* __res
                                                           int64_t dst_ld, int scatter_add) {
   const int i = blockIdx.x;
   const int64_t r = index[i];
+  // index < 0 = "no row" (an action slot ovla_assemble_multimodal did not find leaves -1): the gather writes a zero row, the scatter-add
+  // skips the entry.  Uniform per workgroup, so no lane diverges.
+  if (r < 0 && scatter_add) return;
   for (int c = threadIdx.x; c < (dim >> 3); c += 256) {
     if (!scatter_add) {
-      *reinterpret_cast<bf16x8_bits*>(dst + (int64_t)i * dst_ld + c * 8) =
-          *reinterpret_cast<const bf16x8_bits*>(src + r * src_ld + c * 8);
+      bf16x8_bits v = {0, 0, 0, 0, 0, 0, 0, 0};
+      if (r >= 0) v = *reinterpret_cast<const bf16x8_bits*>(src + r * src_ld + c * 8);
+      *reinterpret_cast<bf16x8_bits*>(dst + (int64_t)i * dst_ld + c * 8) = v;
     } else {  // dst[index[i]] += src[i]   (indices are unique per launch on this path)
       float a[8], bb[8];
       load8(src + (int64_t)i * src_ld + c * 8, a);

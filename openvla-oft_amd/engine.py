@@ -1776,7 +1776,11 @@ class VLAEngine:
         are computed (LlamaStack.fwd) and returned as `action_hidden` [n, D]; `hidden` is then None."""
         dev = self.device
         B, L = input_ids.shape
+        if train and self.film_per_policy:
+            raise RuntimeError("a per-policy-FiLM engine is inference-only: the FiLM Linears live in frozen slot storage, there is nothing to train")
         lens = self.check_right_padding(attention_mask)
+        if not labels.is_cuda:   # (device-resident labels cannot be read without a sync: ovla_gather_rows skips the -1 a short row leaves)
+            self.check_action_labels(labels, self.cfg.num_action_tokens)
         if input_ids.is_cuda or labels.is_cuda or not _ASYNC_UPLOAD:
             ids = input_ids.to(dev, torch.int64).contiguous()
             lab = labels.to(dev, torch.int64).contiguous()
@@ -1803,6 +1807,18 @@ class VLAEngine:
         if not bool((am == (torch.arange(L)[None, :] < lens[:, None])).all()):
             raise ValueError("attention_mask must be right padding (a prefix of ones per row), as produced by the reference collator")
         return lens
+
+    @staticmethod
+    def check_action_labels(labels, num_action_tokens: int, action_token_begin: int = 31743):
+        """Host-side validation of the action labels: every row holds exactly `num_action_tokens` labels above `action_token_begin` (the rule
+        of ovla_assemble_multimodal's action mask; IGNORE_INDEX never counts).  A truncated sample would leave -1 in `action_rows`, one with
+        more would drop slots silently; the reference fails on both with a reshape error.  Raises before anything is uploaded or launched."""
+        counts = (labels.to("cpu") > action_token_begin).sum(1)
+        bad = torch.nonzero(counts != num_action_tokens).reshape(-1)
+        if bad.numel():
+            b = int(bad[0])
+            raise ValueError(f"labels: row {b} holds {int(counts[b])} action labels (ids above {action_token_begin}), the model takes exactly "
+                             f"{num_action_tokens} per row ({bad.numel()} of {labels.shape[0]} rows are malformed)")
 
     def patches_dev(self, ids, lab, pixel_values, proprio, proprio_projector, film_avg, train):
         """The step-independent front of forward_dev: FiLM average (unless given), both towers, the projector and the proprio token ->
@@ -1936,10 +1952,11 @@ class VLAEngine:
         self.llm.on_grads_ready = llm_layer_done
 
     def train_step_fwd_bwd(self, batch: dict, loss_scale: float = 1.0, action_head=None, proprio_projector=None, diffusion=None,
-                           noisy_action_projector=None):
+                           noisy_action_projector=None, film_avg=None):
         """One run_forward_pass (finetune.py:280-451) + backward.  L1 branch by default; with
         `diffusion = dict(noise, noisy_actions, timestep_emb)` the noise-prediction MSE branch (:402-407).
-        Gradients accumulate in the flat buffers.  Returns (loss_sum fp32[1] device, element count, predictions)."""
+        Gradients accumulate in the flat buffers.  `film_avg` (what language_average returns) replaces the FiLM conditioning vector the forward
+        would compute from the batch's own ids.  Returns (loss_sum fp32[1] device, element count, predictions)."""
         self._not_in_ema_scope("train_step_fwd_bwd")
         cfg = self.cfg
         head = action_head if action_head is not None else self.head
@@ -1947,7 +1964,7 @@ class VLAEngine:
         if diffusion is not None:
             kw = dict(noisy_actions=diffusion["noisy_actions"], timestep_emb=diffusion["timestep_emb"], noisy_action_projector=noisy_action_projector)
         out = self.forward(batch["input_ids"], batch["attention_mask"], batch["pixel_values"], batch["labels"], proprio=batch.get("proprio"),
-                           train=True, proprio_projector=proprio_projector, sel="actions", **kw)
+                           train=True, proprio_projector=proprio_projector, sel="actions", film_avg=film_avg, **kw)
         B, S, D = batch["input_ids"].shape[0], out["S"], cfg.llm_dim
         ah, idx = self.action_hidden(out)
         tgt_src = diffusion["noise"] if diffusion is not None else batch["actions"]
@@ -2058,6 +2075,7 @@ class VLAEngine:
         if self.lm_head is None:
             raise RuntimeError("the discrete objective needs language_model.lm_head.weight in the checkpoint")
         labels = batch["labels"].to("cpu", torch.int64)
+        self.check_action_labels(labels, self.cfg.num_action_tokens)
         B, L = labels.shape
         D = self.cfg.llm_dim
         use_pp = batch.get("proprio") is not None and (proprio_projector is not None or self.proprio is not None)

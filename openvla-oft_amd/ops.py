@@ -743,7 +743,8 @@ def assemble_multimodal(ids, labels, table, patches, *, A, noisy=None, ignore_in
 
 
 def gather_rows(src, index, dim, *, dst=None, scatter_add=False, n_dst_rows=None):
-    """gather: dst[i] = src[index[i]];  scatter_add: dst[index[i]] += src[i]."""
+    """gather: dst[i] = src[index[i]];  scatter_add: dst[index[i]] += src[i].  An index < 0 is "no row" (the -1 assemble_multimodal leaves
+    for an action slot it did not find): the gather writes a zero row there, the scatter-add skips the entry."""
     n = index.numel()
     if dst is None:
         dst = torch.empty((n, dim), dtype=BF16, device=src.device)

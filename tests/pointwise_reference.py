@@ -673,6 +673,34 @@ def suite_elementwise(fails, K):
             same_bits(fails, K.transpose(src, dst), want, f"transpose {rows}x{cols} (whole destination buffer)")
 
 
+NO_ROW_INDEX = (3, -1, 0, 7)
+
+
+def suite_gather_no_row(fails, K):
+    """gather_rows with an index < 0 ("no row": what ovla_assemble_multimodal leaves for an action slot the labels do not hold): the gather
+    writes a ZERO row there, the scatter-add skips the entry.  `src` and `dst` are views inside larger allocations with three guard rows
+    above them, so row -1 of either lies inside the same allocation whatever a kernel does with the index; the guards of the source hold
+    NaN and those of the destination the sentinel, and whole destination buffers are compared bit for bit."""
+    g = rng(410)
+    idx = torch.tensor(NO_ROW_INDEX, dtype=torch.int32)
+    keep = idx >= 0
+    for dim in (8, 264):
+        src = embed(randn_bf(g, (9, dim)), fill="nan")
+        dst = embed(BF, shape=(4, dim), fill="sentinel", device="cpu")
+        assert src.r0 >= 1 and dst.r0 >= 1
+        rows = torch.zeros((4, dim), dtype=BF)
+        rows[keep] = src.view[idx[keep].long()]
+        want = dst.buf.clone()
+        want[dst.r0:dst.r0 + 4, dst.c0:dst.c0 + dim] = rows
+        same_bits(fails, K.gather_rows(src, idx, dim, dst, False), want, f"gather_rows index -1 dim {dim}: a zero row (whole destination buffer)")
+        upd = embed(randn_bf(g, (4, dim)), fill="nan")
+        dst = embed(randn_bf(g, (9, dim)), fill="zero")
+        dst.fill_guards("sentinel")
+        want = dst.buf.clone()
+        want[dst.r0 + idx[keep].long(), dst.c0:dst.c0 + dim] = (dst.view[idx[keep].long()].float() + upd.view[keep].float()).to(BF)
+        same_bits(fails, K.gather_rows(upd, idx, dim, dst, True), want, f"gather_rows scatter_add index -1 dim {dim}: entry skipped (whole destination buffer, guards included)")
+
+
 WRAP_PARTS = ("add", "act_bwd", "colscale", "swiglu_fwd", "swiglu_bwd", "copy_rows", "vit_embed", "im2col", "cvt", "adamw_bf16", "adamw_f32")
 
 

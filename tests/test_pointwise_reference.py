@@ -207,10 +207,21 @@ class Emulated:
     def gather_rows(self, src, idx, dim, dst, scatter_add):
         out = dst.buf.clone()
         r0, c0 = dst.r0, dst.c0
+        if self.mut == "gather_no_skip":       # the index taken as it comes: row -1 is the guard row above the view (inside the allocation)
+            if scatter_add:
+                rows = r0 + idx.long()
+                out[rows, c0:c0 + dim] = self._store(dst.buf[rows, c0:c0 + dim].float() + src.view.float())
+            else:
+                out[r0:r0 + idx.numel(), c0:c0 + dim] = src.buf[src.r0 + idx.long(), src.c0:src.c0 + dim]
+            return out
+        keep = idx >= 0                        # an index < 0 is "no row": a zero row on gather, skipped on scatter-add
+        ok = idx[keep].long()
         if scatter_add:
-            out[r0 + idx.long(), c0:c0 + dim] = self._store(dst.view[idx.long()].float() + src.view.float())
+            out[r0 + ok, c0:c0 + dim] = self._store(dst.view[ok].float() + src.view[keep].float())
         else:
-            out[r0:r0 + idx.numel(), c0:c0 + dim] = src.view[idx.long()]
+            rows = torch.zeros((idx.numel(), dim), dtype=BF)
+            rows[keep] = src.view[ok]
+            out[r0:r0 + idx.numel(), c0:c0 + dim] = rows
         return out
 
     def transpose(self, src, dst):
@@ -290,6 +301,7 @@ SUITES = {
     "token_ce": lambda f, K: P.suite_token_ce(f, K),
     "head": lambda f, K: P.suite_head(f, K),
     "adamw": lambda f, K: P.suite_adamw(f, K),
+    "gather_no_row": lambda f, K: P.suite_gather_no_row(f, K),
 }
 
 
@@ -325,6 +337,8 @@ MUTATIONS = {
     "adamw_fma": ("AdamW with one fused multiply-add where the sequence has two roundings", "adamw_fma", lambda f, K: P.suite_adamw(f, K, n=512 + 77), "adamw torch.float32"),
     "adamw_no_grad_scale": ("AdamW ignoring grad_scale", "adamw_no_grad_scale", lambda f, K: P.suite_adamw(f, K, n=512 + 77), "grad_scale 0.37"),
     "sigmoid_no_tail": ("the sigmoid family without its tail: 0 from z = -88.7 on, where the value is still 1e-39 ... 4e-37", "sigmoid_no_tail", SUITES["activations"], "act_bwd silu dh 1.0: "),
+    "gather_no_skip": ("gather_rows taking an index of -1 as a row: the row before the buffer", "gather_no_skip", SUITES["gather_no_row"],
+                       ("gather_rows index -1", "gather_rows scatter_add index -1")),
     "gelu_tanh_old": ("gelu_tanh_grad with an unclamped polynomial factor: NaN at z = -1e19", "gelu_tanh_old", SUITES["activations"], "act_bwd gelu_tanh dh 1.0: "),
 }
 # What the old close() says when it is shown the same outputs.  It ACCEPTS a dropped register slot (rstd 0.4 % off: y stays inside 1.5e-2), a
