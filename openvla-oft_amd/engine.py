@@ -17,7 +17,7 @@ from __future__ import annotations
 
 import contextlib
 import math
-from typing import Dict, List, Optional, Tuple
+from typing import Any, Dict, List, NamedTuple, Optional, Tuple
 
 import os
 
@@ -1097,6 +1097,21 @@ def build_component(cls, device, get, prefix, **kw):
 # ======================================================================================================================
 # the whole path
 # ======================================================================================================================
+class ForwardSaved(NamedTuple):
+    """What a training forward keeps for backward_from_hidden (`saved` of forward()'s result; None without `train`)."""
+    vsaved: Any
+    psaved: Any
+    nsaved: Any
+    lsaved: Any
+    B: int
+    S: int
+    P: int
+    n_vis: int
+    proprio_projector: Any
+    noisy_action_projector: Any
+    action_rows: torch.Tensor
+
+
 class VLAEngine:
     """Prismatic VLM stack + heads.  `get(name)` returns the bf16 device tensor of a reference-named parameter
     (see weights.py for the state-dict naming)."""
@@ -1137,6 +1152,7 @@ class VLAEngine:
         self.embed = get("language_model.model.embed_tokens.weight")
         self.llm = LlamaStack(st, cfg, get, lora)
         self.lm_head = get("language_model.lm_head.weight") if (has is None or has("language_model.lm_head.weight")) else None
+        self._lm_head_t = None      # its transpose, made by the first lm_loss_bwd
         st.finalize()
         # components are separate modules with their own parameter stores, like the reference's DDP-wrapped
         # ProprioProjector / action head / NoisyActionProjector (finetune.py:894-932); they can also be built standalone
@@ -1774,10 +1790,20 @@ class VLAEngine:
         call) skips the vision towers / projector / proprio projector: the DDIM sampler reuses them across its steps
         (modeling_prismatic.py:810).  `sel="actions"` (or an int32 tensor of flattened rows): only those rows of the last hidden state
         are computed (LlamaStack.fwd) and returned as `action_hidden` [n, D]; `hidden` is then None."""
-        dev = self.device
-        B, L = input_ids.shape
+        self._refuse_per_policy_film_training(train)
+        ids, lab, lens_dev = self.upload_text(input_ids, attention_mask, labels)
+        return self.forward_dev(ids, lab, lens_dev, pixel_values, proprio=proprio, noisy_actions=noisy_actions, timestep_emb=timestep_emb, train=train, sel=sel,
+                                proprio_projector=proprio_projector, noisy_action_projector=noisy_action_projector, cached_patches=cached_patches, film_avg=film_avg)
+
+    def _refuse_per_policy_film_training(self, train: bool):
         if train and self.film_per_policy:
             raise RuntimeError("a per-policy-FiLM engine is inference-only: the FiLM Linears live in frozen slot storage, there is nothing to train")
+
+    def upload_text(self, input_ids, attention_mask, labels):
+        """The text side of a batch (host or device tensors [B, L]), validated on the host before anything is uploaded ->
+        (ids int64 [B, L], labels int64 [B, L], text lengths int32 [B]) on the device."""
+        dev = self.device
+        B, L = input_ids.shape
         lens = self.check_right_padding(attention_mask)
         if not labels.is_cuda:   # (device-resident labels cannot be read without a sync: ovla_gather_rows skips the -1 a short row leaves)
             self.check_action_labels(labels, self.cfg.num_action_tokens)
@@ -1794,9 +1820,7 @@ class VLAEngine:
             packed_dev = packed.to(dev, non_blocking=True)
             ids, lab = packed_dev[: B * L].view(B, L), packed_dev[B * L: 2 * B * L].view(B, L)
             lens_dev = packed_dev[2 * B * L:].to(torch.int32)
-        return self.forward_dev(ids, lab, lens_dev, pixel_values, proprio=proprio, noisy_actions=noisy_actions,
-                                timestep_emb=timestep_emb, train=train, proprio_projector=proprio_projector,
-                                noisy_action_projector=noisy_action_projector, cached_patches=cached_patches, sel=sel, film_avg=film_avg)
+        return ids, lab, lens_dev
 
     @staticmethod
     def check_right_padding(attention_mask) -> torch.Tensor:
@@ -1847,8 +1871,7 @@ class VLAEngine:
                     proprio_projector=None, noisy_action_projector=None, cached_patches=None, film_avg=None, sel=None):
         """Device-only part of forward(): ids / lab int64 [B, L] and text_lens int32 [B] already on the device; launches
         kernels and allocates, never synchronises or reads host memory -- the part a hipGraph can capture (ChunkGraph)."""
-        if train and self.film_per_policy:
-            raise RuntimeError("a per-policy-FiLM engine is inference-only: the FiLM Linears live in frozen slot storage, there is nothing to train")
+        self._refuse_per_policy_film_training(train)
         self.dropout.begin_forward(train)
         try:
             return self._forward_dev(ids, lab, text_lens, pixel_values, proprio, noisy_actions, timestep_emb, train, proprio_projector,
@@ -1891,14 +1914,12 @@ class VLAEngine:
             if sel_rows.numel() % 8 != 0:
                 sel_rows = None          # (e.g. ALOHA discrete: 4 x 351 rows) -> the full last layer
         hidden, lsaved = self.llm.fwd(mm.view(B * S, cfg.llm_dim), B, S, kv_len, train, sel=sel_rows)
-        saved = (vsaved, psaved, nsaved, lsaved, B, S, P, n_vis, proprio_projector, noisy_action_projector, action_rows) if train else None
+        saved = ForwardSaved(vsaved, psaved, nsaved, lsaved, B, S, P, n_vis, proprio_projector, noisy_action_projector, action_rows) if train else None
         # `all_patches` [B, P, D]: what sits between BOS and the text in the multimodal sequence (projected patches + proprio + timestep
         # tokens) = the reference's `projector_features` (modeling_prismatic.py:586-599, 674)
-        if sel_rows is not None:
-            return dict(hidden=None, action_hidden=hidden, sel_rows=sel_rows, P=P, S=S, action_rows=action_rows, patches=(base, n_vis), saved=saved,
-                        all_patches=allp)
-        return dict(hidden=hidden.view(B, S, cfg.llm_dim), action_hidden=None, sel_rows=None, P=P, S=S, action_rows=action_rows, patches=(base, n_vis),
-                    saved=saved, all_patches=allp)
+        on_rows = sel_rows is not None                                       # then `hidden` holds those rows only
+        return dict(hidden=None if on_rows else hidden.view(B, S, cfg.llm_dim), action_hidden=hidden if on_rows else None, sel_rows=sel_rows, P=P, S=S,
+                    action_rows=action_rows, patches=(base, n_vis), saved=saved, all_patches=allp)
 
     def action_hidden(self, out):
         """(hidden rows that predict the action slots [B*A, D], their flattened row indices) of a forward() result, whether the last
@@ -1918,23 +1939,32 @@ class VLAEngine:
     def backward_from_hidden(self, dhidden, saved):
         """dhidden bf16 [B*S, D] (gradient of hidden_states[-1]; [n, D] for the selected rows when the forward ran with `sel`) ->
         accumulates every VLM / projector gradient."""
-        vsaved, psaved, nsaved, lsaved, B, S, P, n_vis, proprio_projector, noisy_action_projector, action_rows = saved
-        D = self.cfg.llm_dim
-        dmm_flat = self.llm.bwd(dhidden, lsaved)
+        B, S, n_vis, D = saved.B, saved.S, saved.n_vis, self.cfg.llm_dim
+        dmm_flat = self.llm.bwd(dhidden, saved.lsaved)
         dmm = dmm_flat.view(B, S, D)
-        if nsaved is not None:
+        if saved.nsaved is not None:
             # the projected noisy-action features sit AT the action slots: one row after the row that predicts them
-            slot_rows = (action_rows.reshape(-1) + 1).contiguous()
+            slot_rows = (saved.action_rows.reshape(-1) + 1).contiguous()
             n = slot_rows.numel()
             dn = torch.zeros(((n + 7) // 8 * 8, D), dtype=BF16, device=self.device)
             ops.gather_rows(dmm_flat, slot_rows, D, dst=dn)
-            noisy_action_projector.bwd(dn, nsaved)
-        if psaved is not None:
+            saved.noisy_action_projector.bwd(dn, saved.nsaved)
+        if saved.psaved is not None:
             dpr = torch.zeros(((B + 7) // 8 * 8, D), dtype=BF16, device=self.device)
             dpr[:B] = dmm[:, 1 + n_vis]
-            proprio_projector.bwd(dpr, psaved)
+            saved.proprio_projector.bwd(dpr, saved.psaved)
         dpatches = dmm[:, 1: 1 + n_vis].contiguous().view(B * n_vis, D)
-        self.vision_bwd(dpatches, vsaved)
+        self.vision_bwd(dpatches, saved.vsaved)
+
+    def backward_from_rows(self, drows, rows_idx, out, run: bool = True):
+        """drows bf16 [n, D], the gradient of the hidden rows `rows_idx` of the forward result `out`, sent into the decoder: as it is when the last layer
+        ran on exactly these rows, else scatter-added into a zero [B*S, D].  `run=False` returns that instead (the autograd bridge calls later)."""
+        if out["sel_rows"] is None:
+            dhidden = torch.zeros((out["action_rows"].shape[0] * out["S"], drows.shape[1]), dtype=BF16, device=self.device)
+            drows = ops.gather_rows(drows, rows_idx, drows.shape[1], dst=dhidden, scatter_add=True)
+        if not run:
+            return drows
+        self.backward_from_hidden(drows, out["saved"])
 
     def attach_reducer(self, reducer, overlap: bool = True):
         """Overlaps the data-parallel gradient all-reduce with the backward: the head's gradients go out as soon as its
@@ -1958,48 +1988,34 @@ class VLAEngine:
         Gradients accumulate in the flat buffers.  `film_avg` (what language_average returns) replaces the FiLM conditioning vector the forward
         would compute from the batch's own ids.  Returns (loss_sum fp32[1] device, element count, predictions)."""
         self._not_in_ema_scope("train_step_fwd_bwd")
-        cfg = self.cfg
-        head = action_head if action_head is not None else self.head
-        kw = {}
-        if diffusion is not None:
-            kw = dict(noisy_actions=diffusion["noisy_actions"], timestep_emb=diffusion["timestep_emb"], noisy_action_projector=noisy_action_projector)
-        out = self.forward(batch["input_ids"], batch["attention_mask"], batch["pixel_values"], batch["labels"], proprio=batch.get("proprio"),
-                           train=True, proprio_projector=proprio_projector, sel="actions", film_avg=film_avg, **kw)
-        B, S, D = batch["input_ids"].shape[0], out["S"], cfg.llm_dim
-        ah, idx = self.action_hidden(out)
-        tgt_src = diffusion["noise"] if diffusion is not None else batch["actions"]
-        target = tgt_src.to(self.device, BF16).reshape(B * cfg.chunk, cfg.action_dim).contiguous()
-        pred, loss_sum, hsaved = head.fwd(ah, target=target, mse=diffusion is not None, train=True)
-        # ---- backward ----
-        dah = head.bwd(hsaved, dloss=loss_scale)
-        if getattr(self, "_overlap", False) and hasattr(head, "store"):
-            for dt, g in head.store.flat_grad.items():
-                self.reducer.notify(head.store, dt, g.numel())
-        if out["sel_rows"] is not None:
-            self.backward_from_hidden(dah, out["saved"])            # the last layer ran on exactly these rows
-        else:
-            dhidden = torch.zeros((B * S, D), dtype=BF16, device=self.device)
-            ops.gather_rows(dah, idx, D, dst=dhidden, scatter_add=True)
-            self.backward_from_hidden(dhidden, out["saved"])
-        return loss_sum, pred.numel(), pred
-
+        return self._head_step(batch, diffusion, action_head if action_head is not None else self.head, loss_scale,
+                               proprio_projector=proprio_projector, noisy_action_projector=noisy_action_projector, film_avg=film_avg)
 
     def eval_step(self, batch: dict, diffusion=None, discrete: bool = False):
         """run_forward_pass under torch.no_grad() (run_validation, finetune.py:678-760): the same loss as the training step,
         no activations kept, no gradients touched.  Returns (loss_sum fp32[1] device, count, predictions)."""
         if discrete:
             return self.train_step_discrete(batch, backward=False)
-        cfg = self.cfg
-        kw = {}
+        return self._head_step(batch, diffusion, self.head, None)
+
+    def _head_step(self, batch: dict, diffusion, head, loss_scale: Optional[float], noisy_action_projector=None, **fwd_kw):
+        """The L1 / noise-prediction MSE objective of one batch: the forward on the action rows, the head and its loss; with a `loss_scale`
+        (the training step) also the backward of both.  -> (loss_sum fp32[1] device, element count, predictions)."""
+        cfg, train = self.cfg, loss_scale is not None
         if diffusion is not None:
-            kw = dict(noisy_actions=diffusion["noisy_actions"], timestep_emb=diffusion["timestep_emb"])
+            fwd_kw.update(noisy_actions=diffusion["noisy_actions"], timestep_emb=diffusion["timestep_emb"], noisy_action_projector=noisy_action_projector)
         out = self.forward(batch["input_ids"], batch["attention_mask"], batch["pixel_values"], batch["labels"], proprio=batch.get("proprio"),
-                           train=False, sel="actions", **kw)
-        B = batch["input_ids"].shape[0]
-        ah, _ = self.action_hidden(out)
+                           train=train, sel="actions", **fwd_kw)
+        ah, idx = self.action_hidden(out)
         tgt_src = diffusion["noise"] if diffusion is not None else batch["actions"]
-        target = tgt_src.to(self.device, BF16).reshape(B * cfg.chunk, cfg.action_dim).contiguous()
-        pred, loss_sum, _ = self.head.fwd(ah, target=target, mse=diffusion is not None, train=False)
+        target = tgt_src.to(self.device, BF16).reshape(batch["input_ids"].shape[0] * cfg.chunk, cfg.action_dim).contiguous()
+        pred, loss_sum, hsaved = head.fwd(ah, target=target, mse=diffusion is not None, train=train)
+        if train:
+            dah = head.bwd(hsaved, dloss=loss_scale)
+            if getattr(self, "_overlap", False) and hasattr(head, "store"):
+                for dt, g in head.store.flat_grad.items():
+                    self.reducer.notify(head.store, dt, g.numel())
+            self.backward_from_rows(dah, idx, out)
         return loss_sum, pred.numel(), pred
 
     # -- the diffusion objective on the device ------------------------------------------------------------------------------
@@ -2039,6 +2055,7 @@ class VLAEngine:
         B = batch["input_ids"].shape[0]
         n = B * cfg.chunk * cfg.action_dim
         with torch.no_grad():
+            ids, lab, lens_dev = self.upload_text(batch["input_ids"], batch["attention_mask"], batch["labels"])   # (raises before any launch)
             if start_noise is None:
                 zeros = torch.zeros((B, cfg.chunk * cfg.action_dim), dtype=BF16, device=dev)
                 start = ops.diffusion_noise(zeros, st.ab, st.temb_table, seed=st.seed, call=st.call, stream=2)[0]
@@ -2049,10 +2066,6 @@ class VLAEngine:
             step = torch.zeros(1, dtype=torch.int32, device=dev)
             temb = torch.empty((B, cfg.llm_dim), dtype=BF16, device=dev)
             noisy = torch.empty(n, dtype=BF16, device=dev)
-            lens = self.check_right_padding(batch["attention_mask"])
-            ids = batch["input_ids"].to(dev, torch.int64).contiguous()
-            lab = batch["labels"].to(dev, torch.int64).contiguous()
-            lens_dev = lens.to(torch.int32).to(dev)
             cached = None
             for _ in range(st.T):
                 ops.ddim_prepare(step, st.step_temb, temb, sample, noisy)
@@ -2077,45 +2090,51 @@ class VLAEngine:
         labels = batch["labels"].to("cpu", torch.int64)
         self.check_action_labels(labels, self.cfg.num_action_tokens)
         B, L = labels.shape
-        D = self.cfg.llm_dim
         use_pp = batch.get("proprio") is not None and (proprio_projector is not None or self.proprio is not None)
         P = self.num_patches_total(batch["pixel_values"].shape[1] // 6, use_pp)
-        S = P + L
-        # text position j (j >= 1) with labels[b, j] != -100 is predicted by the hidden state of text position j - 1, which sits at
-        # multimodal row b * S + P + (j - 1) (the BOS row is 0, the patches are rows 1..P; modeling_prismatic.py:474-496)
-        bb, jj = torch.nonzero(labels[:, 1:] != -100, as_tuple=True)
-        n_tok = int(bb.numel())
-        if n_tok == 0:
-            raise ValueError("no label in the batch is different from IGNORE_INDEX")
-        rows_idx = (bb * S + P + jj).to(torch.int32).to(self.device)
-        targets = labels[bb, jj + 1].contiguous().to(self.device)
+        bb, jj, rows_idx, targets = self.counted_rows(labels, P + L, P)
+        n_tok = rows_idx.numel()
         out = self.forward(batch["input_ids"], batch["attention_mask"], batch["pixel_values"], batch["labels"], proprio=batch.get("proprio"),
                            train=backward, proprio_projector=proprio_projector, sel=rows_idx)     # last layer on the counted rows only
-        assert out["P"] == P and out["S"] == S
-        n_pad = (n_tok + 7) // 8 * 8
-        if out["sel_rows"] is not None:
-            x = out["action_hidden"]                       # n_tok % 8 == 0: already the gathered rows
-        else:
-            x = torch.zeros((n_pad, D), dtype=BF16, device=self.device)
-            ops.gather_rows(out["hidden"].view(B * S, D), rows_idx, D, dst=x)
-        logits = ops.gemm(x, self.lm_head)                                   # bf16 [n_pad, vocab]: lm_head under autocast
-        loss_rows, amax, dlogits = ops.token_ce(logits[:n_tok], targets, grad_scale=loss_scale / n_tok if backward else None)
+        assert out["P"] == P and out["S"] == P + L
+        loss_rows, amax, dlogits = self.lm_loss_fwd(out, rows_idx, targets, grad_scale=loss_scale / n_tok if backward else None)
         pred = torch.full((B, L - 1), -1, dtype=torch.int64)
         pred[bb, jj] = amax.to("cpu", torch.int64)
-        if not backward:
-            return loss_rows.sum().reshape(1), n_tok, pred
-        if n_pad > n_tok:
-            logits[n_tok:].zero_()
-        if getattr(self, "_lm_head_t", None) is None:
-            self._lm_head_t = ops.transpose(self.lm_head)                    # frozen: one transposed copy for the data gradient
-        dx = ops.gemm(logits, self._lm_head_t)                               # d hidden rows = dlogits @ W
-        if out["sel_rows"] is not None:
-            self.backward_from_hidden(dx, out["saved"])
-        else:
-            dhidden = torch.zeros((B * S, D), dtype=BF16, device=self.device)
-            ops.gather_rows(dx, rows_idx, D, dst=dhidden, scatter_add=True)
-            self.backward_from_hidden(dhidden, out["saved"])
+        if backward:
+            self.backward_from_rows(self.lm_loss_bwd(dlogits), rows_idx, out)
         return loss_rows.sum().reshape(1), n_tok, pred
+
+    # -- the next-token cross entropy on the counted rows: train_step_discrete above and modeling._LMLossFn (`output.loss`) ------------------
+    def counted_rows(self, labels, S: int, P: int):
+        """Host int64 labels [B, L] -> (bb, jj, rows_idx int32 [n_tok] device, targets int64 [n_tok] device).  Text position j + 1 with
+        labels[b, j + 1] != -100 is predicted by the hidden state of text position j, which sits at multimodal row b * S + P + j (the BOS row
+        is 0, the patches are rows 1..P; modeling_prismatic.py:474-496)."""
+        bb, jj = torch.nonzero(labels[:, 1:] != -100, as_tuple=True)
+        if bb.numel() == 0:
+            raise ValueError("no label in the batch is different from IGNORE_INDEX")
+        return bb, jj, (bb * S + P + jj).to(torch.int32).to(self.device), labels[bb, jj + 1].contiguous().to(self.device)
+
+    def lm_loss_fwd(self, out, rows_idx, targets, grad_scale: Optional[float]):
+        """Frozen lm_head (bf16, as under autocast) + ovla_token_ce on the rows `rows_idx` of the forward result `out` -> (loss per row fp32
+        [n_tok], argmax [n_tok], logits bf16 [n_tok padded to 8, vocab]).  With a `grad_scale` the logits come back overwritten by
+        grad_scale * d loss_rows / d logits, pad rows zero: lm_loss_bwd's argument."""
+        n_tok, D = rows_idx.numel(), self.cfg.llm_dim
+        if out["sel_rows"] is not None:
+            x = out["action_hidden"]                       # n_tok % 8 == 0 and the last layer ran on these rows: already gathered
+        else:
+            x = torch.zeros(((n_tok + 7) // 8 * 8, D), dtype=BF16, device=self.device)
+            ops.gather_rows(out["hidden"].detach().view(-1, D), rows_idx, D, dst=x)
+        logits = ops.gemm(x, self.lm_head)
+        loss_rows, amax, _ = ops.token_ce(logits[:n_tok], targets, grad_scale=grad_scale)
+        if grad_scale is not None:
+            logits[n_tok:].zero_()
+        return loss_rows, amax, logits
+
+    def lm_loss_bwd(self, dlogits, alpha: float = 1.0):
+        """alpha * dlogits @ W_lm_head -> gradient of the hidden rows lm_loss_fwd read, bf16 [rows, D]."""
+        if self._lm_head_t is None:
+            self._lm_head_t = ops.transpose(self.lm_head)                    # frozen: one transposed copy for the data gradient
+        return ops.gemm(dlogits, self._lm_head_t, alpha=alpha)
 
 
 # ======================================================================================================================

@@ -248,46 +248,27 @@ class NoisyActionProjector(ProprioProjector):
 class _LMLossFn(torch.autograd.Function):
     """`output.loss` of the reference's forward (LlamaForCausalLM with `labels`: logits.float(), shift by one, cross entropy with
     ignore_index -100, mean over the counted labels; modeling_prismatic.py:632-643 + :486-496 for the multimodal labels), computed on
-    the counted rows only: frozen lm_head GEMM on the gathered hidden rows, `ovla_token_ce` (fp32 log-sum-exp, gradient written in place),
-    and in the backward one GEMM with the transposed lm_head + a row scatter into d hidden."""
+    the counted rows only, by the engine's pieces of train_step_discrete (counted_rows, lm_loss_fwd, lm_loss_bwd, backward_from_rows).  The mean's
+    1 / n_tok rides in the token gradient and the incoming d loss in the backward GEMM's alpha.  `out`: the engine forward's result."""
 
     @staticmethod
-    def forward(ctx, hidden, vla, labels, P):
+    def forward(ctx, hidden, vla, labels, out):
         eng = vla.engine
         if eng.lm_head is None:
             raise RuntimeError("output.loss / output.logits need language_model.lm_head.weight, which this checkpoint was loaded without")
-        B, S, D = hidden.shape
-        lab = labels.to("cpu", torch.int64)
-        bb, jj = torch.nonzero(lab[:, 1:] != IGNORE_INDEX, as_tuple=True)
-        n_tok = int(bb.numel())
-        if n_tok == 0:
-            raise ValueError("no label in the batch is different from IGNORE_INDEX")
-        # text position j + 1 is predicted by the hidden state of text position j, which is multimodal row P + j (BOS is row 0)
-        rows_idx = (bb * S + P + jj).to(torch.int32).to(eng.device)
-        targets = lab[bb, jj + 1].contiguous().to(eng.device)
-        n_pad = (n_tok + 7) // 8 * 8
-        x = torch.zeros((n_pad, D), dtype=BF16, device=eng.device)
-        ops.gather_rows(hidden.detach().reshape(B * S, D), rows_idx, D, dst=x)
-        logits = ops.gemm(x, eng.lm_head)
+        bb, jj, rows_idx, targets = eng.counted_rows(labels.to("cpu", torch.int64), out["S"], out["P"])
+        n_tok = rows_idx.numel()
         need_grad = ctx.needs_input_grad[0]
-        loss_rows, amax, _ = ops.token_ce(logits[:n_tok], targets, grad_scale=(1.0 / n_tok) if need_grad else None)
+        loss_rows, amax, logits = eng.lm_loss_fwd(out, rows_idx, targets, grad_scale=(1.0 / n_tok) if need_grad else None)
         if need_grad:
-            if n_pad > n_tok:
-                logits[n_tok:].zero_()
-            ctx.dlogits, ctx.rows_idx, ctx.shape, ctx.eng = logits, rows_idx, (B, S, D), eng
+            ctx.dlogits, ctx.rows_idx, ctx.out, ctx.eng = logits, rows_idx, out, eng
         vla._last_token_argmax = (bb, jj, amax)
         return loss_rows.sum() / n_tok
 
     @staticmethod
     def backward(ctx, dloss):
-        eng = ctx.eng
-        B, S, D = ctx.shape
-        if getattr(eng, "_lm_head_t", None) is None:
-            eng._lm_head_t = ops.transpose(eng.lm_head)
-        dx = ops.gemm(ctx.dlogits, eng._lm_head_t, alpha=float(dloss))
-        dhidden = torch.zeros((B * S, D), dtype=BF16, device=eng.device)
-        ops.gather_rows(dx, ctx.rows_idx, D, dst=dhidden, scatter_add=True)
-        return dhidden.view(B, S, D), None, None, None
+        dhidden = ctx.eng.backward_from_rows(ctx.eng.lm_loss_bwd(ctx.dlogits, alpha=float(dloss)), ctx.rows_idx, ctx.out, run=False)
+        return dhidden.view(ctx.out["hidden"].shape), None, None, None
 
 
 class PrismaticCausalLMOutputWithPast:
@@ -299,16 +280,16 @@ class PrismaticCausalLMOutputWithPast:
     past_key_values = None
     attentions = None
 
-    def __init__(self, vla, hidden, labels, P, projector_features):
-        self._vla, self._labels, self._P = vla, labels, P
+    def __init__(self, vla, hidden, labels, out):
+        self._vla, self._labels, self._out = vla, labels, out           # `out`: the engine forward's result behind `hidden`
         self.hidden_states = (hidden,)
-        self.projector_features = projector_features
+        self.projector_features = out["all_patches"]
         self._loss = self._logits = None
 
     @property
     def loss(self) -> torch.Tensor:
         if self._loss is None:
-            self._loss = _LMLossFn.apply(self.hidden_states[-1], self._vla, self._labels, self._P)
+            self._loss = _LMLossFn.apply(self.hidden_states[-1], self._vla, self._labels, self._out)
         return self._loss
 
     @property
@@ -355,7 +336,7 @@ class _VLMFn(torch.autograd.Function):
         B, S, D = dhidden.shape
         eng.backward_from_hidden(dhidden.to(BF16).contiguous().view(B * S, D), ctx.saved)
         ctx.vla.publish_grads()
-        for comp in (ctx.saved[8], ctx.saved[9]):
+        for comp in (ctx.saved.proprio_projector, ctx.saved.noisy_action_projector):
             if comp is not None and hasattr(comp, "owner"):
                 comp.owner.publish_grads()
         return None, None, None, None
@@ -607,7 +588,7 @@ class OpenVLAForActionPrediction(_StoreModule):
                 hidden, _ = _VLMFn.apply(self._anchor, self, kwargs, False)
         # the reference also returns the CE loss / fp32 logits of the frozen lm_head; in L1 / diffusion mode they are discarded
         # (finetune.py:400,407), so the output object computes them on first access only
-        return PrismaticCausalLMOutputWithPast(self, hidden, labels, self._last["P"], self._last["all_patches"])
+        return PrismaticCausalLMOutputWithPast(self, hidden, labels, self._last)
 
     def logits_for(self, hidden_rows: torch.Tensor) -> torch.Tensor:
         """lm_head on selected hidden rows [n, D] -> fp32 logits [n, vocab] (discrete action-token path, :929-942)."""

@@ -160,7 +160,7 @@ def test_resume_continues_the_noise_stream_and_the_trajectory(world, dev, tmp_pa
     assert dist_with <= 2 * dist_l1        # 2x: the extra noisy-action projector path adds its own fp32-atomic weight gradients
 
 
-def test_sampler_equals_the_host_loop_bit_for_bit(world, dev):
+def test_sampler_equals_the_host_loop_bit_for_bit(world, dev, monkeypatch):
     T = 5
     eng = fresh(world, dev, T=T)
     diffusion = load("openvla-oft_amd.diffusion")
@@ -194,6 +194,13 @@ def test_sampler_equals_the_host_loop_bit_for_bit(world, dev):
     got_start = bf16_bits_to_f32(to_bits(start)).astype(np.float64)
     assert ((got_start == lo) | (got_start == hi)).all()
     assert torch.equal(eng.sample_actions(b, start_noise=start.view(B, 8, 7)), a1)
+    # one action label removed from one row: refused by check_action_labels before any launch
+    bad, launches, lib = dict(b, labels=b["labels"].clone()), [], load("openvla-oft_amd._lib")
+    bad["labels"][1, int((bad["labels"][1] > 31743).nonzero()[0])] = -100
+    monkeypatch.setattr(lib, "call", lambda name, *a: launches.append(name))
+    with pytest.raises(ValueError, match="row 1 holds 55 action labels"):
+        eng.sample_actions(bad)
+    assert not launches
 
 
 def _driver_cfg(ft, tmp_path, **kw):
