@@ -91,14 +91,19 @@ typedef struct {
                                     [g*K, (g+1)*K) with B rows of the same column range (per-group LoRA dt = dy_g . B_g) */
   int32_t act;
   int32_t split_k;               /* <=1: none */
-  int32_t tile;                  /* 0: auto; otherwise forces a tile configuration (tests / tuning) */
+  int32_t tile;                  /* 0: auto; otherwise forces a tile configuration (tests / tuning): 1 (128x128), 2 (64x128), 5 (128x32),
+                                    16 / 17 (256x256 on 4x2 / 2x4 waves), 18 (4-wave 256x256), 22 (4-wave 128x256); id + 100 = the same
+                                    configuration with the hybrid schedule forced.  10 .. 15, 20, 21: the experimental BK = 32 ring kernel
+                                    (plain epilogues and split-K only, no + 100 form).  6 (the skinny kernel) is what tile 0 resolves to for
+                                    N = 32, K <= 3072, M >= 512 and takes no epilogue.  Any other id is OVLA_EINVAL ("unknown tile id"). */
   float alpha;                   /* scales the accumulator (LoRA alpha/r); 0 means 1 */
   const void* dact_src; int64_t ld_dact;   /* optional saved pre-activations for the backward epilogues above */
   int32_t dact_mode, dact_act;
   const void* rope_cos; const void* rope_sin;  /* optional bf16 [>= rope_S, 64] tables: RoPE (head_dim 128, HF rotate_half, position = */
   int32_t rope_S, rope_cols;                   /* row % rope_S) applied to output columns [0, rope_cols) -- the q | k heads of a fused
                                                   q|k|v projection (modeling_llama apply_rotary_pos_emb).  Excludes the other epilogues;
-                                                  fused into the 256x256 config's epilogue, otherwise one extra ovla_rope launch. */
+                                                  fused into the epilogue on tiles 1, 16, 17, 18 and 22 (and their + 100 forms) where the
+                                                  shape allows, otherwise one extra ovla_rope launch: the same bits either way. */
   /* RMSNorm folded around the GEMM (the decoder's input_layernorm / post_attention_layernorm, HF LlamaRMSNorm at modeling_prismatic.py:632-643,
    * on the merged inference path; the norm WEIGHT is folded into B offline, B' = bf16(B * w[k])):
    *   producer side  rowsq_out [M, N/64] fp32: sum of squares of every 64-column group of the bf16 OUTPUT row (plain stores, one writer per

@@ -22,7 +22,7 @@ OUT=../libovla_hip.so; EXTRA=""; BUILD=../_build
 SRCS="$(ls *.hip | LC_ALL=C sort | tr '\n' ' ')"
 NOPK="$SRCS"
 if [ "$MODE" = "ablate" ]; then OUT=../libovla_hip_ablate.so; EXTRA="-DOVLA_GEMM_ABLATE"; BUILD=../_build_ablate; fi
-if [ "$MODE" = "exp" ]; then OUT=../libovla_hip_exp.so; EXTRA="${OVLA_EXP_FLAGS:-}"; BUILD=../_build_exp; fi   # same-call A/B of a compile-time experiment (OVLA_EXP_FLAGS="-DOVLA_GEMM_SPREAD2")
+if [ "$MODE" = "exp" ]; then OUT=../libovla_hip_exp.so; EXTRA="${OVLA_EXP_FLAGS:-}"; BUILD=../_build_exp; fi   # same-call A/B of a second build: a compile-time experiment (OVLA_EXP_FLAGS="-DNAME"), or another commit's csrc/ built beside this tree's library
 if [ "$MODE" = "packed" ]; then OUT=../libovla_hip_packed.so; BUILD=../_build_packed; NOPK=""; fi
 NOPK_FLAGS="-Xclang -target-feature -Xclang -packed-fp32-ops"   # (the host pass prints "not a recognized feature ... ignoring": filtered below)
 HASH=$(cat $(ls *.hip *.h | LC_ALL=C sort) build.sh ../../include/ovla.h | sha256sum | cut -c1-32)

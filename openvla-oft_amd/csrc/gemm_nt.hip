@@ -366,12 +366,6 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_kernel(const GemmParams 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WN, wn = wave % WN;
-#ifdef OVLA_GEMM_STAMPS   // in-kernel timeline (100 MHz wall clock) of a plain launch into the unused workspace: tools/gemm_stamps.py
-#define OVLA_STAMP(k) do { if (tid == 0) reinterpret_cast<unsigned long long*>(p.ws)[(int64_t)blockIdx.x * 8 + (k)] = wall_clock64(); } while (0)
-#else
-#define OVLA_STAMP(k) do { } while (0)
-#endif
-  OVLA_STAMP(0);
 
   // ---- block -> work unit ------------------------------------------------------------------------------------
   // Plain / split-K launch: blocks [0, tiles*splits) ; block ids are remapped so each XCD (private L2) owns a contiguous
@@ -383,11 +377,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_kernel(const GemmParams 
   const int remap_n = p.rem_tiles > 0 ? p.full_tiles : (int)gridDim.x;
   int split = 0, t_mn, rem_unit = -1;
   if (bid < remap_n) {
-#ifdef OVLA_XCD_ROT   // experiment: give physical XCD x the band of XCD (x + ROT) & 7 -- does a slow band follow the silicon or the data?
-    const int xcd = ((bid & 7) + OVLA_XCD_ROT) & 7, q = remap_n >> 3, r = remap_n & 7;
-#else
     const int xcd = bid & 7, q = remap_n >> 3, r = remap_n & 7;
-#endif
     bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
     split = bid / tiles_mn;
     t_mn = bid - split * tiles_mn;
@@ -489,15 +479,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_kernel(const GemmParams 
   // (`SPREAD` loop); the K tail and the LoRA K-extension tiles keep the simple stage-after-barrier scheme.
   constexpr int PA = BM / 8 / NW, PB = BN / 8 / NW, PP = PA + PB;
   constexpr int PPS = (PP + MT - 1) / MT;
-  // SPREAD2 (OVLA_GEMM_SPREAD2, experiment): when the pieces are no more than the m-tiles (256x256 on 8 waves: 8 and 8), deal ONE piece to every
-  // SECOND of the 2 MT row slots of a K tile instead of one to each of the first MT: 8 MFMAs (128 matrix-pipe cycles) between two pieces
-#ifdef OVLA_GEMM_SPREAD2
-  constexpr bool SPREAD2 = (PP <= MT);
-#else
-  constexpr bool SPREAD2 = false;
-#endif
   auto n_pieces_at = [](int slot) constexpr -> int {   // pieces issued at row slot `slot` (0 .. 2 MT - 1)
-    if (SPREAD2) return (slot % 2 == 0 && slot / 2 < PP) ? 1 : 0;
     if (slot >= MT) return 0;
     return ((slot + 1) * PPS <= PP) ? PPS : ((slot * PPS < PP) ? PP - slot * PPS : 0);
   };
@@ -506,9 +488,6 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_kernel(const GemmParams 
     const int buf = (t - t_begin) & 1;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's LDS-DMA for tile t has landed
     __syncthreads();                                   // ... everyone's has; and buf^1 is no longer being read
-#ifdef OVLA_GEMM_STAMPS
-    if (t == t_begin) OVLA_STAMP(2);
-#endif
     if constexpr (!SPREAD) {
       if (t + 1 < t_end && !(OVLA_DBG(1) && t > t_begin)) stage(t + 1, buf ^ 1);
     }
@@ -520,7 +499,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_kernel(const GemmParams 
     const char* gB = reinterpret_cast<const char*>(p.B) + (int64_t)(t + 1) * (BK * 2);
     auto pieces = [&](auto slot_tag) {
       constexpr int SLOT = decltype(slot_tag)::value;
-      constexpr int Q0 = SPREAD2 ? SLOT / 2 : SLOT * PPS, Q1 = SPREAD2 ? (SLOT % 2 == 0 ? SLOT / 2 + 1 : SLOT / 2) : (SLOT + 1) * PPS;
+      constexpr int Q0 = SLOT * PPS, Q1 = (SLOT + 1) * PPS;
 #pragma unroll
       for (int q = Q0; q < Q1 && q < PP; ++q) {
         if (q < PA)
@@ -571,7 +550,6 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_kernel(const GemmParams 
     __builtin_amdgcn_s_setprio(0);
   };
 
-  OVLA_STAMP(1);
   if (t_begin < t_end) stage(t_begin, 0);
   // (the fold's prologue loads are issued AFTER the first K tile's LDS-DMA, so the two latencies overlap: issued first, their wait delayed the DMA by a
   // whole memory round trip -- measured: the removed norm launches' time came back inside the GEMMs)
@@ -611,7 +589,6 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_kernel(const GemmParams 
   for (int j = 0; j < NT; ++j)
     acc[MT - 1][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b1[j], a_def, acc[MT - 1][j], 0, 0, 0);
 
-  OVLA_STAMP(3);
   if (OVLA_DBG(8)) {   // timing ablation: no epilogue at all (one store per lane keeps the accumulators alive)
     if (acc[0][0][0] == 123.456f) p.C[0] = 1;
     return;
@@ -747,10 +724,6 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_kernel(const GemmParams 
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (reads consumed above; keeps the next round's writes behind them)
     });
-#ifdef OVLA_GEMM_STAMPS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the tile's stores have been acknowledged
-    OVLA_STAMP(4);
-#endif
     return;
   }
   // General path (activations, pre-activation save, LayerScale, FiLM, backward epilogues, RoPE, edge tiles).
@@ -831,7 +804,6 @@ __global__ __launch_bounds__(256) void gemm_nt_w4_kernel(const GemmParams p) {
   const int cb = RMAP ? (wn >> 1) * 128 + (wn & 1) * 32 : GMAP ? wn * (WTN / 2) : wn * WTN;     // first column of the wave inside the tile
   auto cj = [](int j) constexpr { return RMAP ? 16 * (j & 1) + 64 * (j >> 1) : GMAP ? 16 * (j % NH) + 128 * (j / NH) : 16 * j; };   // column (B-tile row) of n-tile j relative to cb
   auto scol = [](int sc) constexpr { return RMAP ? (sc & 31) + 64 * (sc >> 5) : sc; };      // column (relative to cb) of slab column sc = 16 j + c
-  OVLA_STAMP(0);
 
   int bid = blockIdx.x;
   const int tiles_mn = p.tiles_m * p.tiles_n;
@@ -949,7 +921,6 @@ __global__ __launch_bounds__(256) void gemm_nt_w4_kernel(const GemmParams p) {
       for (int u = 0; u < 8; ++u) rs_q[u] = (4 * u < per) ? *reinterpret_cast<const f32x4*>(src + 4 * u) : f32x4{0.f, 0.f, 0.f, 0.f};
     }
   }
-  OVLA_STAMP(1);
   // (K2 = 32 KEXT, host-checked.  Straight-line code: a branch around asm that updates 64 accumulators makes the compiler merge them through scratch.  Two
   // fragment sets: steps 0 and 1 are requested up front, step 2 into set 0 once step 0's MFMAs have read it.)
   bf16x8_bits a2f[(KEXT > 1 || GMAP) ? 2 : 1][KEXT ? MT : 1], b2f[KEXT > 1 ? 2 : 1][KEXT ? NT : 1];   // (GMAP: a2f[0] / a2f[1] = the gate / the up group's columns of A2)
@@ -1086,7 +1057,6 @@ __global__ __launch_bounds__(256) void gemm_nt_w4_kernel(const GemmParams p) {
     a_def = af[(2 * MT - 1) % 3];
     asm volatile("s_setprio 0");
   };
-  OVLA_STAMP(2);
   auto k_loop = [&](auto shift_tag) {
     int t = t_begin;
     for (; t + 1 < t_end; t += 2) {
@@ -1104,7 +1074,6 @@ __global__ __launch_bounds__(256) void gemm_nt_w4_kernel(const GemmParams p) {
   asm volatile("s_nop 4");   // (compiler code may sit between the loop and the last deferred row's MFMAs: same hazard as in the prologue)
   static_for<NT>([&](auto j_tag) { constexpr int j = decltype(j_tag)::value; acc[MT - 1][j] = w4_mfma(acc[MT - 1][j], b1[j], a_def); });
   asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 7" ::: "memory");   // the compiler's hazard recognizer does not see the asm MFMAs' AGPR writes
-  OVLA_STAMP(3);
 
   // The epilogue takes the lane id from an opaque copy: whatever it derived from `lane` itself the compiler would share with the prologue's
   // staging addresses and keep in VGPRs across the K loop (two such values cost the 128x256 RoPE instantiation its second wave per SIMD).
@@ -1217,10 +1186,6 @@ __global__ __launch_bounds__(256) void gemm_nt_w4_kernel(const GemmParams p) {
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     });
-#ifdef OVLA_GEMM_STAMPS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    OVLA_STAMP(4);
-#endif
     return;
   }
   // general path (edge tiles, activations, pre-activation save, LayerScale, FiLM, backward epilogues)
@@ -1913,7 +1878,6 @@ constexpr TileCfg kTiles[] = {
     // 8-wave gemm_nt_kernel (BK = 64, LDS-DMA double buffer):  id, cost, auto rank, fixed rank, flags, RoPE
     w8_row<128, 128, 2, 2>(1, {2, 1.13e15, 4e-6, 0.86e-6}, 2, 4, CFG_PLUS100 | CFG_BDIAG | CFG_FOLD, ROPE_HEAD_TILE),
     w8_row<64, 128, 1, 4>(2, {3, 0.90e15, 3e-6, 0.57e-6}, 3, 5, CFG_PLUS100 | CFG_BDIAG),
-    w8_row<256, 128, 4, 2>(3, kCostGeneric, 0, 0, 0),
     w8_row<128, 32, 4, 1>(5, {4, 0.60e15, 3e-6, 0.53e-6}, 4, 6, CFG_PLUS100 | CFG_BDIAG),
     {6, 32, 32, FAM_SKINNY, kCostGeneric, 0, 0, 0, 0, 0, 0, 0, ROPE_UNFUSED, launch_skinny},   // single launch, 32 rows per workgroup; `tile = 0` takes it for LoRA t / dt (gemm_run)
     // gemm_nt_pipe_kernel (BK = 32 ring): experimental

@@ -29,9 +29,13 @@ CLASSES = [(12288, 4096, 0, 0), (4096, 4096, 0, 0), (22016, 4096, 0, 0), (4096, 
            (1152, 4608, 0, 0), (4096, 28672, 0, 0), (32, 4096, 0, 0), (12288, 4096, 32, 4096), (768, 256, 0, 0),
            (22016, 4096, 32, 11008), (4096, 11008, 32, 0), (4096, 4096, 32, 0), (3072, 1024, 32, 0), (1024, 1024, 32, 0),
            (4096, 4096, 16, 0), (4096, 4096, 64, 0), (4096, 4096, 96, 0), (4096, 4096, 128, 0), (4096, 4104, 0, 0)]
-BASE_TILES = [1, 2, 3, 5, 6, 10, 11, 12, 13, 14, 15, 16, 17, 18, 20, 21, 22]
+BASE_TILES = [1, 2, 5, 6, 10, 11, 12, 13, 14, 15, 16, 17, 18, 20, 21, 22]
 PLUS100 = [101, 102, 105, 116, 117, 118, 122]
-TILES = [0] + BASE_TILES + PLUS100 + [7, 103, 110, 1018]
+# ids that were configurations when the table was recorded and have been removed since (3: the 256x128 8-wave tile).  The query answers before
+# the unknown-id check, so their recorded columns still hold; they keep their place in the fixture's column order, among the base ids
+REMOVED_TILES = [3]
+UNKNOWN_TILES = [7, 103, 110, 1018]      # never configurations: kept to pin the unknown-id behaviour
+TILES = [0] + sorted(BASE_TILES + REMOVED_TILES) + PLUS100 + UNKNOWN_TILES
 EPILOGUES = ["plain", "bias", "residual", "residual_misaligned", "c_pre", "colscale", "film", "rope", "rope_misaligned", "rowsq", "rowscale",
              "swiglu", "swiglu_c_pre", "dact1", "dact2", "a_group_32", "a_group_128"]
 SPLIT_KS = [1, 4]

@@ -39,6 +39,7 @@ def test_fixture_covers_the_grid_the_generator_defines(gen, table):
     assert table["M"] == gen.MS and [tuple(c) for c in table["classes"]] == gen.CLASSES and table["tiles"] == gen.TILES
     assert [tuple(c) for c in table["combos"]] == gen.combos() and table["plan_workspaces"] == gen.PLAN_WS
     assert set(gen.TILES) >= {0, 7, 103, 110, 1018} | set(gen.BASE_TILES) | set(gen.PLUS100)
+    assert set(gen.TILES) == {0} | set(gen.BASE_TILES) | set(gen.PLUS100) | set(gen.REMOVED_TILES) | set(gen.UNKNOWN_TILES) and len(gen.TILES) == len(set(gen.TILES))
     assert len(table["resolved"]) == len(gen.CLASSES) and all(len(r) == len(gen.combos()) for r in table["resolved"])
     assert all(len(row) == len(gen.TILES) for row in table["rows"])
     assert (GOLDEN / "gemm_dispatch_table.json").stat().st_size < max(f.stat().st_size for f in GOLDEN.glob("*.npz"))

@@ -25,7 +25,7 @@ ANY = None
 # test_table_names_every_configuration_of_the_dispatch_table ties the ids to tests/golden/gemm_dispatch_table.json.
 Cfg = namedtuple("Cfg", "id BM BN BK kgran kext plus100 fam")
 CONFIGS = [
-    Cfg(1, 128, 128, 64, 8, ANY, True, "w8"), Cfg(2, 64, 128, 64, 8, ANY, True, "w8"), Cfg(3, 256, 128, 64, 8, ANY, False, "w8"),
+    Cfg(1, 128, 128, 64, 8, ANY, True, "w8"), Cfg(2, 64, 128, 64, 8, ANY, True, "w8"),
     Cfg(5, 128, 32, 64, 8, ANY, True, "w8"),
     Cfg(10, 256, 256, 32, 8, ANY, False, "ring"), Cfg(11, 256, 128, 32, 8, ANY, False, "ring"), Cfg(12, 256, 128, 32, 8, ANY, False, "ring"),
     Cfg(13, 128, 256, 32, 8, ANY, False, "ring"), Cfg(14, 128, 128, 32, 8, ANY, False, "ring"), Cfg(15, 256, 256, 32, 8, ANY, False, "ring"),
@@ -34,6 +34,7 @@ CONFIGS = [
     Cfg(18, 256, 256, 64, 64, (0, 32, 64, 96), True, "w4"), Cfg(22, 128, 256, 64, 64, (0, 32), True, "w4"),
     Cfg(6, 32, 32, 32, 8, (0,), False, "skinny"),
 ]
+REMOVED_TILES = [3]                                                       # the 256x128 8-wave tile: no longer in kTiles
 BY_ID = {c.id: c for c in CONFIGS}
 FORCED = [c.id for c in CONFIGS if c.fam != "skinny"]                     # ids `tile=` accepts
 PLUS100 = [c.id + 100 for c in CONFIGS if c.plus100]
@@ -89,9 +90,22 @@ def test_table_names_every_configuration_of_the_dispatch_table():
     """The literal table covers the ids the recorded dispatch table knows (tests/golden/gemm_dispatch_table.json): a tile added to kTiles is
     re-recorded there and then fails here until it is added to CONFIGS -- and with that to every test below."""
     tiles = json.loads((Path(__file__).resolve().parent / "golden" / "gemm_dispatch_table.json").read_text())["tiles"]
-    not_a_config = {0, 7, 103, 110, 1018}                # auto, and the ids the recorded table keeps to pin the "unknown tile" errors
+    not_a_config = {0, 7, 103, 110, 1018} | set(REMOVED_TILES)   # auto, and the ids the recorded table keeps to pin the "unknown tile" errors
     assert set(tiles) - not_a_config == {c.id for c in CONFIGS} | set(PLUS100)
     assert len({c.id for c in CONFIGS}) == len(CONFIGS) and set(FIXED_TILES) <= set(FORCED)
+    assert not set(REMOVED_TILES) & ({c.id for c in CONFIGS} | set(PLUS100))
+
+
+@pytest.mark.parametrize("tile", REMOVED_TILES, ids=tname)
+def test_removed_tile_ids_are_unknown(ops, dev, tile):
+    """The id of a removed configuration (3: the 256x128 8-wave tile) is no configuration any more: a launch that names it is refused with the
+    unknown-id message before anything runs, and the output keeps its bits."""
+    g = R.rng(500 + tile)
+    a, b = R.operand(g, 64, 64).to(dev), R.operand(g, 64, 64).to(dev)
+    out = torch.full((64, 64), 7.0, dtype=BF, device=dev)
+    with pytest.raises(RuntimeError, match=rf"unknown tile id {tile}\b"):
+        ops.gemm(a, b, out=out, tile=tile)
+    assert torch.equal(out, torch.full_like(out, 7.0)), f"tile {tile}: the refused launch wrote the output"
 
 
 # ---- plain GEMM, every configuration -----------------------------------------------------------------------------------------------------------

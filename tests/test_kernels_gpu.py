@@ -58,7 +58,7 @@ GEMM_SHAPES = [(128, 128, 64), (200, 136, 72), (1000, 512, 1024), (64, 256, 2048
 
 
 @pytest.mark.parametrize("M,N,K", GEMM_SHAPES)
-@pytest.mark.parametrize("tile", [0, 1, 2, 3, 5, 10, 11, 12, 13, 14, 15, 16, 17, 20, 21])
+@pytest.mark.parametrize("tile", [0, 1, 2, 5, 10, 11, 12, 13, 14, 15, 16, 17, 20, 21])
 def test_gemm_plain(ops, dev, M, N, K, tile):
     torch.manual_seed(M * 7 + N * 3 + K + tile)
     a, b = rnd(M, K, dev=dev), rnd(N, K, dev=dev)

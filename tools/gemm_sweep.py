@@ -30,7 +30,7 @@ def bench(fn, iters=20):
     return e0.elapsed_time(e1) / iters
 
 
-tiles = [int(t) for t in sys.argv[1:]] or [1, 3]
+tiles = [int(t) for t in sys.argv[1:]] or [1, 17]
 print(f"{'shape':12s} {'M':>5s} {'N':>6s} {'K':>6s} " + " ".join(f"tile{t:>2d}(TF)" for t in tiles) + "  torch(TF)")
 for name, m, n, k, k2 in SHAPES:
     a = torch.randn(m, k, device=dev).to(torch.bfloat16)
@@ -44,7 +44,7 @@ for name, m, n, k, k2 in SHAPES:
         elif m <= 64:
             ms = bench(lambda: ops.gemm(a, b, out=out, tile=2, split_k=8))
         elif n <= 128:
-            sk = {1: 1, 3: 1}.get(t, 4)
+            sk = {1: 1}.get(t, 4)
             ms = bench(lambda: ops.gemm(a, b, out=out, tile=(5 if n <= 32 else 2) if t >= 10 else t, split_k=sk))
         else:
             ms = bench(lambda: ops.gemm(a, b, out=out, tile=t))

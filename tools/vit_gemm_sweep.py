@@ -16,7 +16,7 @@ def bench(fn, iters=30):
     return e0.elapsed_time(e1) / iters * 1e3
 shapes = [(4096, 1152, 4304, 0), (4176, 1024, 4096, 0), (4096, 4304, 1152, 1), (4096, 4304, 1152, 0), (4176, 4096, 1024, 1), (4176, 4096, 1024, 0),
           (4096, 1152, 3456, 0), (4096, 1152, 1152, 0), (4096, 3456, 1152, 0), (4176, 1024, 1024, 0), (4176, 1024, 3072, 0), (4176, 3072, 1024, 0)]
-tiles = [int(t) for t in sys.argv[1:]] or [0, 101, 102, 105, 117, 3]
+tiles = [int(t) for t in sys.argv[1:]] or [0, 101, 102, 105, 117]
 for M, N, K, act in shapes:
     a = torch.randn(M, K, device=dev).to(BF); b = (torch.randn(N, K, device=dev) * 0.05).to(BF)
     t = torch.randn(M, 32, device=dev).to(BF); lb = torch.randn(N, 32, device=dev).to(BF)
