@@ -658,11 +658,15 @@ __global__ __launch_bounds__(256) void image_prep_kernel(const ImagePrepParams p
     if (p.crop) {
       const float ty = (float)oy * p.ystep, tx = (float)ox * p.xstep;
       const float ys = p.ybase + ty, xs = p.xbase + tx;
+      // A coordinate outside the image gives TF's extrapolation_value 0 and issues no load (image_aug_a_kernel's rule): with the box
+      // clipped to the whole image the last coordinate (out - 1) * fl((H - 1) / (out - 1)) can round above H - 1, and ceilf is then row H.
+      const bool outside = ys < 0.0f || ys > (float)(p.H - 1) || xs < 0.0f || xs > (float)(p.W - 1);
       const float fy = floorf(ys), fx = floorf(xs);
       const int y0 = (int)fy, x0 = (int)fx, y1 = (int)ceilf(ys), x1 = (int)ceilf(xs);
       const float wy = ys - fy, wx = xs - fx;
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
+        if (outside) { q[c] = 0; continue; }
         const float tl = (float)im[((int64_t)y0 * p.W + x0) * 3 + c] * inv255, tr = (float)im[((int64_t)y0 * p.W + x1) * 3 + c] * inv255;
         const float bl = (float)im[((int64_t)y1 * p.W + x0) * 3 + c] * inv255, br = (float)im[((int64_t)y1 * p.W + x1) * 3 + c] * inv255;
         const float dt = tr - tl, db = br - bl;

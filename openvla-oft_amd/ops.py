@@ -726,13 +726,19 @@ def image_augment(images_u8, params, *, ops_mask: int = AUG_ALL, out_size: int =
     return out
 
 
-def assemble_multimodal(ids, labels, table, patches, *, A, noisy=None, ignore_index=-100, action_token_begin=31743, action_dim=7):
+def assemble_multimodal(ids, labels, table, patches, *, A, noisy=None, ignore_index=-100, action_token_begin=31743, action_dim=7,
+                        out=None, action_pos=None):
     """ids/labels int64 [B,L]; table bf16 [V,D]; patches bf16 [B,P,D] -> (out [B,P+L,D], action_rows int32 [B,A]:
-    flattened row of the hidden state that predicts each action slot)."""
+    flattened row of the hidden state that predicts each action slot).  `out` / `action_pos`: contiguous tensors of those shapes to
+    write into; a given `action_pos` is the caller's to pre-fill (-1 = slot not found: the kernel writes found slots only)."""
     B, L = ids.shape
     P, D = patches.shape[1], patches.shape[2]
-    out = torch.empty((B, P + L, D), dtype=BF16, device=table.device)
-    action_pos = torch.full((B, A), -1, dtype=torch.int32, device=table.device)
+    if out is None:
+        out = torch.empty((B, P + L, D), dtype=BF16, device=table.device)
+    if action_pos is None:
+        action_pos = torch.full((B, A), -1, dtype=torch.int32, device=table.device)
+    assert out.shape == (B, P + L, D) and out.dtype == BF16 and out.is_contiguous()
+    assert action_pos.shape == (B, A) and action_pos.dtype == torch.int32 and action_pos.is_contiguous()
     g = STRUCTS["ovla_assemble_args"]()
     g.ids, g.labels, g.embed_table, g.patches, g.noisy = ids.data_ptr(), labels.data_ptr(), table.data_ptr(), patches.data_ptr(), _p(noisy)
     g.out, g.action_pos = out.data_ptr(), action_pos.data_ptr()

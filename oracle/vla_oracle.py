@@ -179,6 +179,7 @@ def crop_and_resize_center(image_u8: np.ndarray, crop_scale: float = 0.9, out_si
       CropAndResize kernel:             scale = (y2 - y1) * (H - 1) / (out - 1);  in_y = y1 * (H - 1) + i * scale
                                         top = floor(in_y), bottom = ceil(in_y), lerp = in_y - top
                                         v = tl + (tr - tl) * x_lerp  (top and bottom rows), out = top + (bottom - top) * y_lerp
+                                        in_y outside [0, H - 1] (or in_x outside [0, W - 1]): extrapolation_value 0 for the pixel
       clip_by_value(0, 1); convert_image_dtype(f32 -> u8, saturate): trunc(x * 255.5)."""
     f = np.float32
     img = image_u8.astype(f) * f(1.0 / 255.0)
@@ -190,16 +191,19 @@ def crop_and_resize_center(image_u8: np.ndarray, crop_scale: float = 0.9, out_si
     def coords(n):
         scale = ((o2 - o1) * f(n - 1) / f(out_size - 1)).astype(f)
         c = (o1 * f(n - 1) + np.arange(out_size, dtype=f) * scale).astype(f)
+        ok = (c >= 0) & (c <= f(n - 1))               # outside the image: extrapolation_value 0 (index parked at 0)
+        c = np.where(ok, c, f(0)).astype(f)
         lo, hi = np.floor(c), np.ceil(c)
-        return lo.astype(np.int64), hi.astype(np.int64), (c - lo).astype(f)
+        return lo.astype(np.int64), hi.astype(np.int64), (c - lo).astype(f), ok
 
-    y0, y1, wy = coords(H)
-    x0, x1, wx = coords(W)
+    y0, y1, wy, oky = coords(H)
+    x0, x1, wx, okx = coords(W)
     wy, wx = wy[:, None, None], wx[None, :, None]
     tl, tr, bl, br = img[y0][:, x0], img[y0][:, x1], img[y1][:, x0], img[y1][:, x1]
     top = (tl + ((tr - tl) * wx).astype(f)).astype(f)
     bot = (bl + ((br - bl) * wx).astype(f)).astype(f)
     out = (top + ((bot - top) * wy).astype(f)).astype(f)
+    out = np.where((oky[:, None] & okx[None, :])[:, :, None], out, f(0)).astype(f)
     return (np.clip(out, f(0), f(1)) * f(255.5)).astype(np.uint8)
 
 
