@@ -699,6 +699,39 @@ typedef struct {
 int ovla_adamw_clipped(const ovla_adamw_clipped_args* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * AdamW on fp32 master weights: the optimizer step of a bf16 parameter buffer whose state is kept in fp32 (opt-in,
+ * ParamStore.enable_fp32_state; the default stays ovla_adamw's torch-faithful bf16 state).  In bf16, exp_avg_sq.mul_(0.999) returns its
+ * input for every normal value (the decrement is below half an ulp: the second moment never decays) and a parameter update below half an
+ * ulp of the parameter is lost; here an fp32 master copy and fp32 moments take the update and the bf16 parameter is the rounded master.
+ * THE MASTER CONTRACT (identical in csrc/adamw_master.hip and in the restatement tests/adamw_master_reference.py), for i in [0, n):
+ *   gradient     r = grad[i] * grad_scale, one fp32 multiply and NO bf16 rounding: the optimizer-side dtype is fp32.  With clip_state,
+ *                r = r * state->coef, a second fp32 multiply (ovla_adamw_clipped's fp32 form).  If state->skip is set every workgroup
+ *                returns at once: master, exp_avg, exp_avg_sq and param keep their bits.
+ *   update       (master[i], exp_avg[i], exp_avg_sq[i]) <- ovla_adamw's fp32 element update of them with gradient r: one function
+ *                (csrc/adamw_elem.h adamw_update_f32) is called by both kernels, with the same scalars, no FMA contraction.
+ *   publication  param[i] = bf16_rne(master[i]) of the NEW master: NaN stays NaN, a value beyond the largest finite bf16 gives +-Inf, as
+ *                torch's .to(bfloat16).  After every call that is not skipped, param == bf16_rne(master) element for element.
+ *   purity       each output element is a pure function of (master[i], exp_avg[i], exp_avg_sq[i], grad[i]) and the scalars: nothing
+ *                depends on n, on launch geometry or on which lane holds the element.  The body moves four elements per lane and trip
+ *                (16-byte loads of grad, master and the moments, 16-byte stores of the three, one 8-byte store of four bf16), the last
+ *                n % 4 elements one per lane; a grid-stride loop under OVLA_ADAMW_MASTER_MAX_BLOCKS workgroups of 256 lanes.
+ *   memory       grad is never written; exactly [0, n) of master, exp_avg, exp_avg_sq and param is written.  Stream-ordered and
+ *                capturable, no atomics, no workspace.  30 bytes per element (16 read, 14 written); ovla_adamw on bf16 moves 16.
+ *   refusals     OVLA_EINVAL before any launch: a null pointer other than clip_state, n <= 0, step < 1, or master, exp_avg, exp_avg_sq,
+ *                param or grad not 16-byte aligned. */
+#define OVLA_ADAMW_MASTER_MAX_BLOCKS 2048
+typedef struct {
+  float* master; float* exp_avg; float* exp_avg_sq;   /* fp32 [n], in/out */
+  void* param;                                        /* bf16 [n], out */
+  const float* grad;                                  /* fp32 [n] */
+  int64_t n; int32_t step;                            /* step >= 1 (after increment, as torch) */
+  double lr, beta1, beta2, eps, weight_decay;
+  float grad_scale;
+  const void* clip_state;   /* NULL, or a device ovla_grad_clip_state written by ovla_grad_clip_coef earlier on the stream */
+} ovla_adamw_master_args;
+int ovla_adamw_master(const ovla_adamw_master_args* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * DDIM sampling on the device (prismatic/extern/hf/modeling_prismatic.py:793-877 `_run_diffusion_prediction`: per step, timestep
  * embedding + noisy actions in, `noise_scheduler.step(noise_pred, t, curr_noisy_actions).prev_sample` out).  The loop's step index k is a
  * DEVICE int32 that both kernels read and ovla_ddim_step advances, so one sampling step has no host-dependent argument and can be replayed

@@ -1,5 +1,6 @@
 // adamw_elem.h -- the element update of the fused AdamW, shared by ovla_adamw (head_optim.hip) and ovla_adamw_clipped (grad_clip.hip): the two
 // kernels differ only in how they form `grad`, the gradient in the parameter's precision, and call these functions for everything after it.
+// ovla_adamw_master (adamw_master.hip) runs the fp32 update on an fp32 master copy and publishes its bf16 rounding.
 #pragma once
 #include <math.h>
 #include "common.h"
@@ -48,15 +49,25 @@ OVLA_DEV void adamw_elem_bf16(bf16_bits* __restrict__ p, bf16_bits* __restrict__
   v[i] = f2bf(vv);
 }
 
-OVLA_DEV void adamw_elem_f32(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v, int64_t i, float grad, const AdamScalars& s) {
+// The fp32 element update by value: (p, m, v) in, (p, m, v) out.  adamw_elem_f32 below and ovla_adamw_master (adamw_master.hip, whose `p` is
+// the fp32 master copy of a bf16 parameter) both call it, so the two agree bit for bit by construction.
+struct AdamElemF32 {
+  float p, m, v;
+};
+OVLA_DEV AdamElemF32 adamw_update_f32(float p, float m, float v, float grad, const AdamScalars& s) {
 #pragma clang fp contract(off)
-  float pp = p[i] * s.decay;
-  const float mm = aten_lerp(m[i], grad, s.w1);
-  float vv = v[i] * s.beta2;
+  float pp = p * s.decay;
+  const float mm = aten_lerp(m, grad, s.w1);
+  float vv = v * s.beta2;
   vv = vv + (s.w2 * grad) * grad;
   const float d = sqrtf(vv) / s.bc2_sqrt + s.eps;
   pp = pp + (s.step_size * mm) / d;
-  p[i] = pp;
-  m[i] = mm;
-  v[i] = vv;
+  return {pp, mm, vv};
+}
+
+OVLA_DEV void adamw_elem_f32(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v, int64_t i, float grad, const AdamScalars& s) {
+  const AdamElemF32 r = adamw_update_f32(p[i], m[i], v[i], grad, s);
+  p[i] = r.p;
+  m[i] = r.m;
+  v[i] = r.v;
 }

@@ -16,6 +16,7 @@ HBM layout (sized for 288 GB):
 from __future__ import annotations
 
 import contextlib
+import logging
 import math
 from typing import Any, Dict, List, NamedTuple, Optional, Tuple
 
@@ -86,6 +87,8 @@ class ParamStore:
         self.finalized = False
         self.ema_shadow: Optional[Dict[torch.dtype, torch.Tensor]] = None   # weight EMA (enable_ema): one fp32 shadow per flat buffer
         self.ema_step = 0
+        self.fp32_state = False   # enable_fp32_state: the bf16 buffer's AdamW runs on an fp32 master copy and fp32 moments
+        self.master: Dict[torch.dtype, torch.Tensor] = {}   # {BF16: fp32 master of flat[BF16]} in fp32 mode; flat[BF16] == bf16_rne(master)
 
     def add(self, name: str, init: torch.Tensor) -> Param:
         assert not self.finalized and init.dtype in (BF16, F32)
@@ -116,9 +119,39 @@ class ParamStore:
 
     def init_optimizer(self):
         for dtype, flat in self.flat.items():
-            self.exp_avg[dtype] = torch.zeros_like(flat)
-            self.exp_avg_sq[dtype] = torch.zeros_like(flat)
+            state_dtype = F32 if self.fp32_state else dtype
+            self.exp_avg[dtype] = torch.zeros_like(flat, dtype=state_dtype)
+            self.exp_avg_sq[dtype] = torch.zeros_like(flat, dtype=state_dtype)
         self.step = 0
+
+    # -- fp32 optimizer state for the bf16 buffer (ovla.h "AdamW on fp32 master weights"): opt-in, the default is torch's bf16 state ---------------
+    def enable_fp32_state(self):
+        """From now on the bf16 flat buffer's AdamW step is ovla_adamw_master: an fp32 master copy (the current parameters widened exactly) and
+        fp32 moments (existing bf16 moments widened exactly, a fresh optimizer's zeros) take the update, and the bf16 buffer is bf16_rne(master)
+        after every step.  The fp32 flat buffer keeps ovla_adamw.  Idempotent."""
+        if self.fp32_state:
+            return
+        self.fp32_state = True
+        if BF16 not in self.flat:
+            return
+        self.rewiden_master()
+        if self.exp_avg:
+            self.exp_avg[BF16], self.exp_avg_sq[BF16] = self.exp_avg[BF16].float(), self.exp_avg_sq[BF16].float()
+
+    def rewiden_master(self):
+        """master <- the bf16 parameters widened exactly: after anything but the optimizer has written the flat buffer (a checkpoint load)."""
+        if not self.fp32_state or BF16 not in self.flat:
+            return
+        if BF16 not in self.master:
+            self.master[BF16] = torch.empty(self.flat[BF16].numel(), dtype=F32, device=self.device)
+        ops.cvt_bf16_to_f32(self.flat[BF16], self.master[BF16])
+
+    def master_matches_param(self) -> bool:
+        """bf16_rne(master) == param, bit for bit, checked on the device (one boolean is read back)."""
+        if BF16 not in self.master:
+            return True
+        rounded = ops.cvt_f32_to_bf16(self.master[BF16])
+        return bool(torch.equal(rounded.view(torch.int16), self.flat[BF16].view(torch.int16)))
 
     def zero_grad(self):
         for g in self.flat_grad.values():
@@ -128,12 +161,16 @@ class ParamStore:
         """torch.optim.AdamW(trainable_params, lr) of vla-scripts/finetune.py:952 as one fused launch per dtype.  With `clip_state` (the device
         state VLAEngine.adamw_step filled, ovla.h "Gradient-norm clipping") the launches are ovla_adamw_clipped: the gradient is scaled by the
         state's coefficient, and a step the state marks as skipped writes nothing.  `step` advances either way -- the host never learns of a
-        skip -- so a skipped step consumes its step number in the bias correction (and, in the driver, in the LR schedule)."""
+        skip -- so a skipped step consumes its step number in the bias correction (and, in the driver, in the LR schedule).  In fp32 mode
+        (enable_fp32_state) the bf16 buffer's launch is ovla_adamw_master, with or without the state."""
         if not self.exp_avg:
             self.init_optimizer()
         self.step += 1
         for dtype, flat in self.flat.items():
-            if clip_state is None:
+            if dtype in self.master:   # fp32 state: the update runs on the master, the bf16 buffer receives its rounding
+                ops.adamw_master(self.master[dtype], self.exp_avg[dtype], self.exp_avg_sq[dtype], flat, self.flat_grad[dtype], step=self.step, lr=lr,
+                                 beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay, grad_scale=grad_scale, clip_state=clip_state)
+            elif clip_state is None:
                 ops.adamw(flat, self.exp_avg[dtype], self.exp_avg_sq[dtype], self.flat_grad[dtype], step=self.step, lr=lr, beta1=beta1,
                           beta2=beta2, eps=eps, weight_decay=weight_decay, grad_scale=grad_scale)
             else:
@@ -142,11 +179,14 @@ class ParamStore:
 
     # -- weight EMA (ovla.h "Weight EMA"): the reference has none; diffusers' EMAModel, which Diffusion Policy evaluates on ------------------------
     def enable_ema(self):
-        """One fp32 shadow per flat buffer, initialised exactly from the current parameters (bf16 widened, fp32 copied); ema_step = 0."""
+        """One fp32 shadow per flat buffer, initialised exactly from the current parameters (bf16 widened, fp32 copied); ema_step = 0.  In fp32
+        mode the bf16 buffer's shadow starts from, and ema_update follows, its fp32 master."""
         self.ema_shadow = {}
         for dtype, flat in self.flat.items():
             shadow = torch.empty(flat.numel(), dtype=F32, device=self.device)
-            if dtype == BF16:
+            if dtype in self.master:
+                shadow.copy_(self.master[dtype])
+            elif dtype == BF16:
                 ops.cvt_bf16_to_f32(flat, shadow)
             else:
                 shadow.copy_(flat)
@@ -159,7 +199,7 @@ class ParamStore:
             raise RuntimeError("ema_update without enable_ema()")
         self.ema_step += 1
         for dtype, flat in self.flat.items():
-            ops.ema_update(flat, self.ema_shadow[dtype], 1.0 - float(decay))
+            ops.ema_update(self.master.get(dtype, flat), self.ema_shadow[dtype], 1.0 - float(decay))
 
     def ema_swap_in(self) -> Dict[torch.dtype, torch.Tensor]:
         """Writes the averaged weights over the live ones -- bf16_rne(shadow) into the bf16 buffer, shadow into the fp32 one -- and returns
@@ -1198,7 +1238,8 @@ class VLAEngine:
         slot = 0
         for st in self.stores:
             for dt, grad in st.flat_grad.items():
-                ops.grad_sumsq(grad, clip["slots"], slot, clip["workspace"], is_bf16=dt == BF16, grad_scale=grad_scale)
+                # (fp32 optimizer state: ovla_adamw_master does not round the gradient to bf16, and the norm is of the gradient it sees)
+                ops.grad_sumsq(grad, clip["slots"], slot, clip["workspace"], is_bf16=dt == BF16 and not st.fp32_state, grad_scale=grad_scale)
                 slot += 1
         ops.grad_clip_coef(clip["slots"], clip["state"], clip["max_norm"], clip["skip_nonfinite"])
         for st in self.stores:
@@ -1245,8 +1286,26 @@ class VLAEngine:
         self._grad_clip["state"][3:6].copy_(torch.tensor(counters, dtype=torch.int32))
         return True
 
+    # -- fp32 optimizer state (ovla.h "AdamW on fp32 master weights") -----------------------------------------------------------------------------
+    @property
+    def optimizer_state_precision(self) -> str:
+        """"param": AdamW state in each buffer's own dtype, as torch.optim.AdamW keeps it (the default); "fp32": enable_fp32_optimizer_state."""
+        return "fp32" if self.store.fp32_state else "param"
+
+    def enable_fp32_optimizer_state(self):
+        """Every store's bf16 buffer gets an fp32 master copy and fp32 AdamW moments (ParamStore.enable_fp32_state); the fp32 buffers are as
+        before.  +8 bytes per bf16 trainable element.  Call it before enable_ema (the shadows then start from, and follow, the master); a later
+        load_trainable re-widens the master from the loaded parameters.  Refused inside ema_weights(): the flat buffers hold the averaged weights."""
+        self._not_in_ema_scope("enable_fp32_optimizer_state")
+        for st in self.stores:
+            st.enable_fp32_state()
+
+    def fp32_optimizer_state_bytes(self) -> int:
+        """Device bytes fp32 mode adds: 4 for the master and 2 for each widened moment, per element of a bf16 flat buffer."""
+        return sum(8 * st.flat[BF16].numel() for st in self.stores if BF16 in st.flat)
+
     # -- weight EMA: fp32 shadows of every store's flat buffers, updated after the optimizer step, swapped in for evaluation and export -----------
-    _ema_scope = False   # true while ema_weights() holds the averaged weights in the flat buffers
+    _ema_scope = False  # true while ema_weights() holds the averaged weights in the flat buffers
 
     @property
     def ema_enabled(self) -> bool:
@@ -1609,6 +1668,8 @@ class VLAEngine:
                 view.copy_(src.to(view.device, view.dtype))
             else:
                 missing.append(name)
+        for st in self.stores:   # fp32 optimizer state: the master follows what was loaded (a no-op in the default mode)
+            st.rewiden_master()
         if missing and strict:
             raise KeyError(f"{len(missing)} trainable tensors missing from the checkpoint, e.g. {missing[:3]}")
         self.refresh_derived()
@@ -1626,6 +1687,8 @@ class VLAEngine:
                 tag = "bf16" if dt == BF16 else "f32"
                 out[f"store{i}.{tag}.exp_avg"] = st.exp_avg[dt]
                 out[f"store{i}.{tag}.exp_avg_sq"] = st.exp_avg_sq[dt]
+                if dt in st.master:   # fp32 mode: the moments above are fp32 as they are, and the master goes with them
+                    out[f"store{i}.{tag}.master"] = st.master[dt]
         out["lora_dropout.call"] = torch.tensor([self.dropout.call], dtype=torch.int64)   # the mask stream's position: a resumed run draws the masks the uninterrupted one would
         if self.diffusion is not None:   # ... and the noise and timesteps the uninterrupted one would
             out["diffusion_noise.call"] = torch.tensor([self.diffusion.call], dtype=torch.int64)
@@ -1640,7 +1703,18 @@ class VLAEngine:
                 out[f"grad_clip.{k}"] = torch.tensor([stats[k]], dtype=torch.int64)
         return out
 
-    def load_optimizer_state_dict(self, sd: Dict[str, torch.Tensor]):
+    def load_optimizer_state_dict(self, sd: Dict[str, torch.Tensor], log=None):
+        """Inverse of optimizer_state_dict.  The precision of the checkpoint's state (fp32: it holds a `store{i}.bf16.master`) against this engine's:
+          param -> param   the moments are copied.
+          param -> fp32    the bf16 moments are widened exactly; the master stays what load_trainable left, the widened loaded parameters.  One
+                           line goes to `log` (default: this module's logger).
+          fp32  -> fp32    master and moments are copied, then bf16_rne(master) == param is checked on the device: a mismatch means the model
+                           files and the optimizer file come from different steps, and raises ValueError.
+          fp32  -> param   ValueError before anything is changed: rounding the state back to bf16 is the defect fp32 mode removes."""
+        ckpt_fp32 = any(k.endswith(".bf16.master") for k in sd)
+        if ckpt_fp32 and not self.store.fp32_state:
+            raise ValueError('the optimizer state was saved with fp32 master weights and moments: load it into an engine with '
+                             'enable_fp32_optimizer_state() (finetune(..., optimizer_state="fp32")); it is not rounded back to bf16')
         if "lora_dropout.call" in sd:
             self.dropout.call = int(sd["lora_dropout.call"].item()) & 0xFFFFFFFF
         if "diffusion_noise.call" in sd and self.diffusion is not None:
@@ -1655,7 +1729,18 @@ class VLAEngine:
                     src = sd[f"store{i}.{tag}.{kind}"]
                     if src.numel() != buf.numel():
                         raise ValueError(f"optimizer state store{i}.{tag}.{kind}: {src.numel()} elements, model has {buf.numel()}")
-                    buf.copy_(src.to(buf.device, buf.dtype))
+                    buf.copy_(src.to(buf.device, buf.dtype))   # (fp32 mode, bf16 moments in the checkpoint: an exact widening)
+                if dt in st.master and ckpt_fp32:
+                    src = sd[f"store{i}.{tag}.master"]
+                    if src.numel() != st.master[dt].numel() or src.dtype != F32:
+                        raise ValueError(f"optimizer state store{i}.{tag}.master: {src.numel()} {src.dtype} elements, model has {st.master[dt].numel()} fp32")
+                    st.master[dt].copy_(src.to(self.device))
+                    if not st.master_matches_param():
+                        raise ValueError(f"optimizer state store{i}.{tag}.master does not round to the loaded bf16 parameters: the model files and the "
+                                         f"optimizer-state file come from different steps")
+        if self.store.fp32_state and not ckpt_fp32:
+            (log or logging.getLogger(__name__).info)("[optimizer state] the checkpoint holds bf16 AdamW moments: widened exactly to fp32; the fp32 master "
+                                                      "starts at the loaded bf16 parameters")
         if self.ema_enabled:
             self.load_ema_state_dict(sd)
         if self.grad_clip_enabled:

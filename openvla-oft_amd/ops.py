@@ -1123,6 +1123,27 @@ def adamw_clipped(param, exp_avg, exp_avg_sq, grad, state, *, step, lr, beta1=0.
     _lib.call("ovla_adamw_clipped", g, _stream())
 
 
+# -- AdamW on fp32 master weights (ovla.h "AdamW on fp32 master weights") ----------------------------------------------------------------------
+ADAMW_MASTER_MAX_BLOCKS = 2048   # OVLA_ADAMW_MASTER_MAX_BLOCKS: workgroups (of 256 lanes, 4 elements each) one trip of the grid-stride loop covers
+
+
+def adamw_master(master, exp_avg, exp_avg_sq, param, grad, *, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.01, grad_scale=1.0,
+                 clip_state=None):
+    """The fp32 AdamW update of (master, exp_avg, exp_avg_sq) with the fp32 gradient, and param <- bf16_rne(master), in one launch.  With
+    `clip_state` the gradient is scaled by the state's coefficient, and nothing is written when the state says skip."""
+    assert master.dtype == exp_avg.dtype == exp_avg_sq.dtype == grad.dtype == torch.float32 and param.dtype == BF16
+    assert master.numel() == exp_avg.numel() == exp_avg_sq.numel() == grad.numel() == param.numel()
+    assert all(t.is_contiguous() for t in (master, exp_avg, exp_avg_sq, param, grad))
+    g = STRUCTS["ovla_adamw_master_args"]()
+    g.master, g.exp_avg, g.exp_avg_sq, g.param, g.grad = master.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), param.data_ptr(), grad.data_ptr()
+    g.n, g.step = param.numel(), step
+    g.lr, g.beta1, g.beta2, g.eps, g.weight_decay, g.grad_scale = lr, beta1, beta2, eps, weight_decay, grad_scale
+    if clip_state is not None:
+        assert clip_state.dtype == torch.int32 and clip_state.numel() == 6
+        g.clip_state = clip_state.data_ptr()
+    _lib.call("ovla_adamw_master", g, _stream())
+
+
 def cvt_f32_to_bf16(src, dst=None, scale=1.0):
     if dst is None:
         dst = torch.empty(src.shape, dtype=BF16, device=src.device)

@@ -263,7 +263,7 @@ def save_training_checkpoint(run_dir: Path, log_step: int, engine: VLAEngine, da
     return ckpt
 
 
-def load_training_checkpoint(ckpt: Path, log_step: Optional[int], engine: VLAEngine, load_optimizer: bool = True) -> dict:
+def load_training_checkpoint(ckpt: Path, log_step: Optional[int], engine: VLAEngine, load_optimizer: bool = True, log=None) -> dict:
     """Resume (finetune.py:134-156 `load_checkpoint(module_name, path, step)` per component + the lora adapter the reference
     re-attaches through its merged checkpoint): reads `{component}--{step}_checkpoint.pt` (`latest` when step is None), the
     peft adapter directory and, if present, the optimizer state, which also carries the lora_dropout mask stream's `call` counter
@@ -292,7 +292,7 @@ def load_training_checkpoint(ckpt: Path, log_step: Optional[int], engine: VLAEng
         from safetensors.torch import load_file
 
         osd = load_file(str(opt))
-        engine.load_optimizer_state_dict(osd)
+        engine.load_optimizer_state_dict(osd, log=log)   # raises for an fp32-state file and an engine in the default mode (and says how to load it)
         loaded_opt, has_call, has_noise_call = True, "lora_dropout.call" in osd, "diffusion_noise.call" in osd
     return {"missing": missing, "optimizer": loaded_opt, "tensors": len(sd), "dropout_call": has_call, "diffusion_call": has_noise_call}
 
@@ -366,7 +366,7 @@ def finetune(cfg: FinetuneConfig, *, model_config: VLAConfig = OPENVLA_7B, state
              dataset: Optional[Iterable[dict]] = None, dataset_statistics: Optional[dict] = None, log=print, tokenizer=None,
              val_dataset=None, diffusion_noise: str = "host", ema_decay: Optional[float] = None, ema_power: Optional[float] = 0.75,
              ema_inv_gamma: float = 1.0, ema_update_after: int = 0, max_grad_norm: Optional[float] = None,
-             skip_nonfinite_steps: bool = True) -> Dict[str, list]:
+             skip_nonfinite_steps: bool = True, optimizer_state: str = "param") -> Dict[str, list]:
     """finetune.py:763-1154.  Returns the logged metric history.  Data source, in this order: `dataset` (any iterable of collated
     batches); an episode store at `cfg.data_root_dir / cfg.dataset_name` (prismatic/vla/datasets/rlds_free.py: the reference's
     RLDSDataset + RLDSBatchTransform + collator, finetune.py:981-1016, with the frames augmented and normalised on the device --
@@ -389,7 +389,16 @@ def finetune(cfg: FinetuneConfig, *, model_config: VLAConfig = OPENVLA_7B, state
     update after it averages the unchanged parameters.  `max_grad_norm=None` with the guard on means the guard alone (max_norm = inf); with the
     guard off as well nothing of this runs.  When it runs, the logging steps read the statistics back (the host waits there anyway) and the
     history gains `grad_norm`, `grad_clip_coef` (both of that step) and `skipped_steps` (the running count); the optimizer-state file gains
-    the counters `grad_clip.steps / clipped / skipped`, which a resumed run continues."""
+    the counters `grad_clip.steps / clipped / skipped`, which a resumed run continues.
+    `optimizer_state`: "param" keeps the AdamW state of the bf16 trainables (LoRA factors, action head) in bf16 exactly as torch.optim.AdamW does;
+    "fp32" gives them an fp32 master copy and fp32 moments (VLAEngine.enable_fp32_optimizer_state, +8 bytes per element), switched on before the
+    resume load, the EMA and the clipping: the second moment then decays, updates below half a bf16 ulp accumulate, the EMA follows the master
+    and the norm is taken over the unrounded gradient.  The model checkpoints keep their format (they hold bf16_rne(master)); the
+    optimizer-state file holds fp32 moments and `store{i}.bf16.master`, and loads only into an "fp32" run, while an "fp32" run resumes from a
+    "param" checkpoint by widening.  The master is rank-local and identical on every rank; with the default OVLA_DP_COMM_DTYPE=param the reduced
+    gradient of the bf16 buffers has passed through a bf16 wire, OVLA_DP_COMM_DTYPE=fp32 keeps it in full precision."""
+    if optimizer_state not in ("param", "fp32"):
+        raise ValueError(f'optimizer_state = {optimizer_state!r} ("param" or "fp32")')
     if max_grad_norm is not None and not float(max_grad_norm) > 0.0:   # NaN fails the comparison too
         raise ValueError(f"max_grad_norm = {max_grad_norm} (a positive number, or None)")
     grad_clip = max_grad_norm is not None or bool(skip_nonfinite_steps)
@@ -431,9 +440,14 @@ def finetune(cfg: FinetuneConfig, *, model_config: VLAConfig = OPENVLA_7B, state
         sched, time_enc = DDIMScheduler(cfg.num_diffusion_steps), SinusoidalPositionalEncoding(model_config.llm_dim)
         noise_gen = torch.Generator().manual_seed(7 + rank)
     log(f"# total trainable params: {engine.num_trainable()}")
+    if optimizer_state == "fp32":   # before the resume load (which then fills master and fp32 moments), the EMA shadows and the clip state
+        engine.enable_fp32_optimizer_state()
+        log(f"[finetune] optimizer_state=fp32: fp32 master weights and AdamW moments for the bf16 trainables, +{engine.fp32_optimizer_state_bytes()} bytes")
+    else:
+        log("[finetune] optimizer_state=param: AdamW state in each parameter's dtype")
     if cfg.resume:   # finetune.py:193-209: the trainable components come from the checkpoint directory `vla_path` at `resume_step`
         assert cfg.resume_step is not None, "resume=True needs resume_step"
-        info = load_training_checkpoint(Path(cfg.vla_path), cfg.resume_step, engine)
+        info = load_training_checkpoint(Path(cfg.vla_path), cfg.resume_step, engine, log=log)
         if not info["dropout_call"]:   # a checkpoint from before the counter was saved was trained with dropout ignored: there is no mask stream to
             # continue, only one to start; start it at a position that depends on the step, so two resumes at different steps do not share masks
             engine.dropout.call = (cfg.resume_step * cfg.grad_accumulation_steps) & 0xFFFFFFFF
