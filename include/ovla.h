@@ -355,6 +355,27 @@ typedef struct {
 } ovla_attn_bwd_args;
 int ovla_attn_bwd(const ovla_attn_bwd_args* a, void* stream);
 
+/* Attention probabilities of a list of query rows (output_attentions): read-only, recomputed from what ovla_attn_fwd consumed and wrote.
+ *   visible key:  P[r,h,k] = exp2( fp32(Q[row r,h,:] . K[b,k,h,:]) * (scale * log2e) - lse[b,h,s] * log2e )   (the backward kernels' expression)
+ *   masked key (k >= kv_len[b], or with `causal` k > s):  exactly 0.0f, by select -- a NaN in a masked K row does not reach the output
+ *   P_mean[r,k] = acc * (1.0f / H),  acc summed over h = 0 .. H-1 in that order in fp32 (no atomics: the same bits on every run)
+ * rows[r] = b*S + s is device memory and is range-checked before use: an index outside [0, B*S) writes a zero row and reads nothing.  A
+ * row's result depends on its own q row, its batch entry's K, lse and kv_len only -- not on R, on its position in the list or on B.
+ * head_dim in {64, 128} (the towers' 72 is refused); Q / K 16-byte aligned with row strides that are multiples of 8 elements; R > 0; at
+ * least one of P and P_mean.  Anything else returns OVLA_EINVAL with a message and launches nothing.
+ */
+typedef struct {
+  const void* Q; const void* K; int64_t q_stride, k_stride;  /* addressed exactly as in ovla_attn_fwd_args (post-RoPE, heads contiguous) */
+  const float* lse;        /* fp32 [B,H,S]: what ovla_attn_fwd wrote for the same Q, K, kv_len, causal, scale */
+  const int32_t* kv_len;   /* optional [B] */
+  const int32_t* rows;     /* int32 [R] flattened query rows b*S+s (the convention of LlamaStack.fwd's `sel` and of action_rows): any order,
+                              repeats allowed; NULL: R == B*S and row r is r */
+  float* P;                /* optional fp32 [R, H, S] */
+  float* P_mean;           /* optional fp32 [R, S]: mean over heads */
+  int32_t B, H, S, R, head_dim, causal; float scale;
+} ovla_attn_probs_args;
+int ovla_attn_probs(const ovla_attn_probs_args* a, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Normalisation.  RMSNorm: transformers LlamaRMSNorm (fp32 math, eps 1e-5).  LayerNorm: timm blocks (eps 1e-6) and
  * MLPResNet (action_heads.py:64,69, eps 1e-5).  x/y bf16 [rows, dim]; weight/bias bf16 [dim] (bias NULL for RMS).

@@ -821,6 +821,62 @@ class VitTower:
 # ======================================================================================================================
 # Llama decoder stack (transformers LlamaModel; reference call site modeling_prismatic.py:632-643)
 # ======================================================================================================================
+class AttnCapture:
+    """Asks a forward for the decoder's attention probabilities (`attn_capture=` of VLAEngine.forward / forward_dev, LlamaStack.fwd).
+
+    rows      "actions": the B*A rows that predict the action slots (the assembly kernel's `action_rows`, already on the device: no host
+              sync); "all": every one of the B*S rows; or an int32 device tensor of flattened rows b*S + s (any order, repeats allowed,
+              an index outside [0, B*S) gives a zero row).
+    per_head  also keep the per-head probabilities [n_layers, R, H, S] (the head mean [n_layers, R, S] is always kept).
+    layers    the decoder layers to capture (indices, negative ones count from the end); None: all of them.
+
+    The flash kernels never form P: right after each selected layer's ops.attn_fwd ONE ops.attn_probs launch recomputes it for the listed rows
+    from the same qkv views and lse.  It reads only, so hidden states, losses and gradients keep their bits.  Both buffers are allocated once
+    per forward.  Memory: the mean is R*S*4 bytes per layer (A = 56 of S = 608: 136 KB); rows="all" with per_head is B*H*S*S*4 bytes per
+    layer -- 47 MB at the 7B decoder's H = 32, S = 608 and B = 1, 1.5 GB for its 32 layers, 12 GB at B = 8: choose `layers` accordingly.
+
+    After the forward its result dict holds attention = dict(mean, per_head (or None), rows (the int32 tensor, None for "all"), layers)."""
+
+    def __init__(self, rows="actions", per_head: bool = False, layers=None):
+        if isinstance(rows, str):
+            if rows not in ("actions", "all"):
+                raise ValueError(f"AttnCapture: rows must be \"actions\", \"all\" or an int32 device tensor, got {rows!r}")
+        elif not (torch.is_tensor(rows) and rows.dtype == torch.int32 and rows.dim() == 1 and rows.numel() > 0):
+            raise ValueError("AttnCapture: a row list must be a non-empty 1-D int32 tensor of flattened rows b*S + s")
+        self.rows, self.per_head = rows, bool(per_head)
+        self.layers = None if layers is None else [int(i) for i in layers]
+        self._slot = None
+
+    def begin(self, n_layers: int, action_rows, B: int, S: int, H: int, device):
+        """Resolves rows and layers for one forward and allocates its buffers."""
+        if self.layers is None:
+            sel = list(range(n_layers))
+        else:
+            sel = [i + n_layers if i < 0 else i for i in self.layers]
+            if any(not 0 <= i < n_layers for i in sel) or len(set(sel)) != len(sel):
+                raise ValueError(f"AttnCapture: layers {self.layers} are not distinct indices into {n_layers} decoder layers")
+        if isinstance(self.rows, str):
+            if self.rows == "actions" and action_rows is None:
+                raise ValueError("AttnCapture(rows=\"actions\") needs the forward's action_rows (LlamaStack.fwd alone: pass the row tensor)")
+            rows = action_rows.reshape(-1).contiguous() if self.rows == "actions" else None
+        else:
+            rows = self.rows.to(device).contiguous()
+        R = B * S if rows is None else rows.numel()
+        self._slot = {li: n for n, li in enumerate(sel)}
+        self._rows, self._sel = rows, sel
+        self._mean = torch.empty((len(sel), R, S), dtype=F32, device=device)
+        self._per_head = torch.empty((len(sel), R, H, S), dtype=F32, device=device) if self.per_head else None
+
+    def layer(self, li: int, q, k, lse, B, S, H, hd, kv_len, causal):
+        n = self._slot.get(li)
+        if n is not None:
+            ops.attn_probs(q, k, lse, B, S, H, hd, rows=self._rows, kv_len=kv_len, causal=causal,
+                           out=(None if self._per_head is None else self._per_head[n], self._mean[n]))
+
+    def result(self) -> Dict[str, Any]:
+        return dict(mean=self._mean, per_head=self._per_head, rows=self._rows, layers=list(self._sel))
+
+
 class LlamaStack:
     def __init__(self, store, cfg: VLAConfig, get, lora):
         self.cfg = cfg
@@ -907,12 +963,14 @@ class LlamaStack:
             self.cos, self.sin = ops.rope_table(n, self.hd, self.cfg.rope_theta, device)
         return self.cos, self.sin
 
-    def fwd(self, x, B: int, S: int, kv_len, train: bool, sel=None):
+    def fwd(self, x, B: int, S: int, kv_len, train: bool, sel=None, attn_capture=None):
         """x bf16 [B*S, D] (inputs_embeds) -> (hidden_states[-1] [B*S, D] (post final norm), saved).
         `sel` (int32 [n], flattened (b, s) rows, n % 8 == 0): only these rows of hidden_states[-1] are wanted (the rows that predict
         the action tokens: everything else of the last layer's output is discarded by run_forward_pass / predict_action).  The last
         layer then runs its attention-output projection, MLP and the final norm on those n rows only (K / V still come from every
-        row) and the result is [n, D] in `sel` order -- the same numbers, 9 % of the rows for three of its four GEMMs."""
+        row) and the result is [n, D] in `sel` order -- the same numbers, 9 % of the rows for three of its four GEMMs.
+        `attn_capture` (an AttnCapture the caller has begun): one read-only ops.attn_probs launch behind each selected layer's attention;
+        None issues exactly the launches and allocations of a forward without the argument."""
         cfg = self.cfg
         D, H, hd, F = cfg.llm_dim, cfg.llm_heads, self.hd, cfg.llm_ff
         cos, sin = self._tables(S, x.device)
@@ -947,6 +1005,8 @@ class LlamaStack:
                     qkv, s_qkv = l["qkv"].fwd(h1)
                     ops.rope_(qkv, S, 2 * H, hd, cos, sin)
             o, lse = ops.attn_fwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], B, S, H, hd, kv_len=kv_len, causal=causal)
+            if attn_capture is not None:
+                attn_capture.layer(li, qkv[:, :D], qkv[:, D:2 * D], lse, B, S, H, hd, kv_len, causal)
             if fold and not last_sel:
                 part2 = torch.empty((M, D // 64), dtype=F32, device=x.device)
                 x2 = ops.gemm(o, l["o"].W, residual=x, rowsq_out=part2, tile=itile)
@@ -1869,16 +1929,18 @@ class VLAEngine:
         return ops.language_average(ids_dev, lab_dev, self.embed, avg)
 
     def forward(self, input_ids, attention_mask, pixel_values, labels, proprio=None, noisy_actions=None, timestep_emb=None, train=False,
-                proprio_projector=None, noisy_action_projector=None, cached_patches=None, sel=None, film_avg=None):
+                proprio_projector=None, noisy_action_projector=None, cached_patches=None, sel=None, film_avg=None, attn_capture=None):
         """Multimodal forward (modeling_prismatic.py:571-643 without the discarded lm_head/CE in L1/diffusion mode).
         Returns dict(hidden [B,S,D], P, action_rows [B,A], patches, saved).  `cached_patches` (the `patches` of a previous
         call) skips the vision towers / projector / proprio projector: the DDIM sampler reuses them across its steps
         (modeling_prismatic.py:810).  `sel="actions"` (or an int32 tensor of flattened rows): only those rows of the last hidden state
-        are computed (LlamaStack.fwd) and returned as `action_hidden` [n, D]; `hidden` is then None."""
+        are computed (LlamaStack.fwd) and returned as `action_hidden` [n, D]; `hidden` is then None.  `attn_capture` (an AttnCapture): the result
+        gains `attention`, the decoder's attention probabilities of the rows it names; everything else keeps its bits."""
         self._refuse_per_policy_film_training(train)
         ids, lab, lens_dev = self.upload_text(input_ids, attention_mask, labels)
         return self.forward_dev(ids, lab, lens_dev, pixel_values, proprio=proprio, noisy_actions=noisy_actions, timestep_emb=timestep_emb, train=train, sel=sel,
-                                proprio_projector=proprio_projector, noisy_action_projector=noisy_action_projector, cached_patches=cached_patches, film_avg=film_avg)
+                                proprio_projector=proprio_projector, noisy_action_projector=noisy_action_projector, cached_patches=cached_patches, film_avg=film_avg,
+                                attn_capture=attn_capture)
 
     def _refuse_per_policy_film_training(self, train: bool):
         if train and self.film_per_policy:
@@ -1953,19 +2015,19 @@ class VLAEngine:
         return base, n_vis, vsaved, psaved
 
     def forward_dev(self, ids, lab, text_lens, pixel_values, proprio=None, noisy_actions=None, timestep_emb=None, train=False,
-                    proprio_projector=None, noisy_action_projector=None, cached_patches=None, film_avg=None, sel=None):
+                    proprio_projector=None, noisy_action_projector=None, cached_patches=None, film_avg=None, sel=None, attn_capture=None):
         """Device-only part of forward(): ids / lab int64 [B, L] and text_lens int32 [B] already on the device; launches
         kernels and allocates, never synchronises or reads host memory -- the part a hipGraph can capture (ChunkGraph)."""
         self._refuse_per_policy_film_training(train)
         self.dropout.begin_forward(train)
         try:
             return self._forward_dev(ids, lab, text_lens, pixel_values, proprio, noisy_actions, timestep_emb, train, proprio_projector,
-                                     noisy_action_projector, cached_patches, film_avg, sel)
+                                     noisy_action_projector, cached_patches, film_avg, sel, attn_capture)
         finally:
             self.dropout.end_forward()
 
     def _forward_dev(self, ids, lab, text_lens, pixel_values, proprio, noisy_actions, timestep_emb, train, proprio_projector,
-                     noisy_action_projector, cached_patches, film_avg, sel):
+                     noisy_action_projector, cached_patches, film_avg, sel, attn_capture=None):
         cfg = self.cfg
         dev = self.device
         B, L = ids.shape
@@ -1998,13 +2060,19 @@ class VLAEngine:
             sel_rows = action_rows.reshape(-1) if isinstance(sel, str) else sel
             if sel_rows.numel() % 8 != 0:
                 sel_rows = None          # (e.g. ALOHA discrete: 4 x 351 rows) -> the full last layer
-        hidden, lsaved = self.llm.fwd(mm.view(B * S, cfg.llm_dim), B, S, kv_len, train, sel=sel_rows)
+        if attn_capture is not None:
+            attn_capture.begin(len(self.llm.layers), action_rows, B, S, cfg.llm_heads, dev)
+        hidden, lsaved = self.llm.fwd(mm.view(B * S, cfg.llm_dim), B, S, kv_len, train, sel=sel_rows, attn_capture=attn_capture)
         saved = ForwardSaved(vsaved, psaved, nsaved, lsaved, B, S, P, n_vis, proprio_projector, noisy_action_projector, action_rows) if train else None
         # `all_patches` [B, P, D]: what sits between BOS and the text in the multimodal sequence (projected patches + proprio + timestep
         # tokens) = the reference's `projector_features` (modeling_prismatic.py:586-599, 674)
         on_rows = sel_rows is not None                                       # then `hidden` holds those rows only
-        return dict(hidden=None if on_rows else hidden.view(B, S, cfg.llm_dim), action_hidden=hidden if on_rows else None, sel_rows=sel_rows, P=P, S=S,
-                    action_rows=action_rows, patches=(base, n_vis), saved=saved, all_patches=allp)
+        out = dict(hidden=None if on_rows else hidden.view(B, S, cfg.llm_dim), action_hidden=hidden if on_rows else None, sel_rows=sel_rows, P=P, S=S,
+                   action_rows=action_rows, patches=(base, n_vis), saved=saved, all_patches=allp)
+        if attn_capture is not None:
+            out["attention"] = attn_capture.result()
+            out["kv_len"] = kv_len
+        return out
 
     def action_hidden(self, out):
         """(hidden rows that predict the action slots [B*A, D], their flattened row indices) of a forward() result, whether the last
@@ -2067,14 +2135,16 @@ class VLAEngine:
         self.llm.on_grads_ready = llm_layer_done
 
     def train_step_fwd_bwd(self, batch: dict, loss_scale: float = 1.0, action_head=None, proprio_projector=None, diffusion=None,
-                           noisy_action_projector=None, film_avg=None):
+                           noisy_action_projector=None, film_avg=None, attn_capture=None):
         """One run_forward_pass (finetune.py:280-451) + backward.  L1 branch by default; with
         `diffusion = dict(noise, noisy_actions, timestep_emb)` the noise-prediction MSE branch (:402-407).
         Gradients accumulate in the flat buffers.  `film_avg` (what language_average returns) replaces the FiLM conditioning vector the forward
-        would compute from the batch's own ids.  Returns (loss_sum fp32[1] device, element count, predictions)."""
+        would compute from the batch's own ids.  `attn_capture` (an AttnCapture): filled by the step's forward (read its result() afterwards); loss and
+        gradients keep their bits.  Returns (loss_sum fp32[1] device, element count, predictions)."""
         self._not_in_ema_scope("train_step_fwd_bwd")
+        extra = {} if attn_capture is None else dict(attn_capture=attn_capture)
         return self._head_step(batch, diffusion, action_head if action_head is not None else self.head, loss_scale,
-                               proprio_projector=proprio_projector, noisy_action_projector=noisy_action_projector, film_avg=film_avg)
+                               proprio_projector=proprio_projector, noisy_action_projector=noisy_action_projector, film_avg=film_avg, **extra)
 
     def eval_step(self, batch: dict, diffusion=None, discrete: bool = False):
         """run_forward_pass under torch.no_grad() (run_validation, finetune.py:678-760): the same loss as the training step,

@@ -218,8 +218,11 @@ def device_pixel_values(images: List[np.ndarray], cfg: Any) -> torch.Tensor:
 
 
 def get_vla_action(cfg: Any, vla, processor: Any, obs: Dict[str, Any], task_label: str, action_head=None, proprio_projector=None,
-                   noisy_action_projector=None, use_film: bool = False) -> List[np.ndarray]:
-    """openvla_utils.py:711-796.  Note: like the reference, overwrites obs["state"] with the normalised proprio."""
+                   noisy_action_projector=None, use_film: bool = False, *, return_attention: bool = False):
+    """openvla_utils.py:711-796.  Note: like the reference, overwrites obs["state"] with the normalised proprio.
+    `return_attention=True` -> (actions, modeling.ActionAttention): which camera, patches and prompt tokens each action row looked at
+    (predict_action(output_attentions=True): the eager forward; not with a diffusion head)."""
+    extra = dict(output_attentions=True) if return_attention else {}
     with torch.inference_mode():
         all_images = [obs["full_image"]]
         if cfg.num_images_in_input > 1:
@@ -241,12 +244,13 @@ def get_vla_action(cfg: Any, vla, processor: Any, obs: Dict[str, Any], task_labe
             obs["state"] = normalize_proprio(obs["state"], vla.norm_stats[cfg.unnorm_key]["proprio"])
             proprio = obs["state"]
         if action_head is None:
-            action, _ = vla.predict_action(**inputs, unnorm_key=cfg.unnorm_key, do_sample=False)
+            action, *rest = vla.predict_action(**inputs, unnorm_key=cfg.unnorm_key, do_sample=False, **extra)
         else:
-            action, _ = vla.predict_action(**inputs, unnorm_key=cfg.unnorm_key, do_sample=False, proprio=proprio,
-                                           proprio_projector=proprio_projector, noisy_action_projector=noisy_action_projector,
-                                           action_head=action_head, use_film=use_film)
-    return [action[i] for i in range(min(len(action), cfg.num_open_loop_steps))]
+            action, *rest = vla.predict_action(**inputs, unnorm_key=cfg.unnorm_key, do_sample=False, proprio=proprio,
+                                               proprio_projector=proprio_projector, noisy_action_projector=noisy_action_projector,
+                                               action_head=action_head, use_film=use_film, **extra)
+    actions = [action[i] for i in range(min(len(action), cfg.num_open_loop_steps))]
+    return (actions, rest[1]) if return_attention else actions
 
 
 def device_pixel_values_batch(per_obs: List[List[np.ndarray]], cfg: Any) -> torch.Tensor:

@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import contextlib
 import math
-from typing import Any, Dict, Optional, Tuple
+from typing import Any, Dict, List, Optional, Tuple
 
 import os
 
@@ -23,7 +23,7 @@ import torch.nn as nn
 from . import ops
 from .config import VLAConfig
 from .diffusion import DDIMScheduler, SinusoidalPositionalEncoding
-from .engine import MAX_SLOTS, ChunkGraph, DiffusionGraph, ActionHead, MlpProjector, ParamStore, SlotProjectors, VLAEngine, build_component
+from .engine import MAX_SLOTS, AttnCapture, ChunkGraph, DiffusionGraph, ActionHead, MlpProjector, ParamStore, SlotProjectors, VLAEngine, build_component
 from .policy_pool import split_passes
 from .weights import make_getter
 
@@ -275,7 +275,9 @@ class PrismaticCausalLMOutputWithPast:
     """prismatic/extern/hf/modeling_prismatic.py:266-278 / :668-675.  `hidden_states[-1]` (post final norm) and `projector_features`
     are materialised by the forward; `loss` and `logits` -- which the reference always computes and the L1 / diffusion recipes throw
     away (finetune.py:396-407) -- are computed on first access: `loss` as an autograd node on the hidden state (`loss.backward()`
-    works), `logits` as the fp32 [B, S, vocab] tensor of the frozen lm_head without a gradient edge (0.6 GB at B = 8)."""
+    works), `logits` as the fp32 [B, S, vocab] tensor of the frozen lm_head without a gradient edge (0.6 GB at B = 8).
+    `attentions`: None, or with forward(output_attentions=True) a tuple of n_layers detached fp32 [B, H, S, S] tensors, the decoder's attention
+    probabilities as the HF decoder returns them (engine.AttnCapture(rows="all", per_head=True): B*H*S*S*4 bytes per layer)."""
 
     past_key_values = None
     attentions = None
@@ -285,6 +287,10 @@ class PrismaticCausalLMOutputWithPast:
         self.hidden_states = (hidden,)
         self.projector_features = out["all_patches"]
         self._loss = self._logits = None
+        att = out.get("attention")
+        if att is not None:   # output_attentions=True: per layer [B, H, S, S], permuted views of the [B*S, H, S] capture
+            B, S = hidden.shape[0], hidden.shape[1]
+            self.attentions = tuple(p.detach().view(B, S, p.shape[1], S).permute(0, 2, 1, 3) for p in att["per_head"])
 
     @property
     def loss(self) -> torch.Tensor:
@@ -302,6 +308,63 @@ class PrismaticCausalLMOutputWithPast:
 
     def __getitem__(self, key):   # ModelOutput-style access: out["loss"], out["hidden_states"]
         return getattr(self, key)
+
+
+class ActionAttention:
+    """What the rows that predict the action slots look at: the third element of predict_action / predict_action_batch with
+    `output_attentions=True`.
+
+    mean    fp32 [n_layers, B, A, S] on the device: the head-averaged attention probabilities of each observation's A action rows over the S
+            keys of the multimodal sequence (a padding key is exactly 0).
+    layout  per observation, an ordered dict of named half-open key ranges (start, stop) that tile [0, S): bos, image0 ... image{I-1},
+            proprio and timestep when present, text (the prompt), actions (the A slots), stop, padding."""
+
+    def __init__(self, mean: torch.Tensor, layout: List[Dict[str, Tuple[int, int]]], patches_per_image: int):
+        self.mean, self.layout, self.patches_per_image = mean, layout, patches_per_image
+
+    @property
+    def range_names(self) -> List[str]:
+        return list(self.layout[0])
+
+    def token_mass(self) -> torch.Tensor:
+        """fp32 [n_layers, B, A, n_ranges]: the probability mass of each action row inside each named range (in `range_names` order)."""
+        nl, B, A, _ = self.mean.shape
+        out = torch.zeros((nl, B, A, len(self.range_names)), dtype=torch.float32, device=self.mean.device)
+        for b, lay in enumerate(self.layout):
+            for i, (k0, k1) in enumerate(lay.values()):
+                if k1 > k0:
+                    out[:, b, :, i] = self.mean[:, b, :, k0:k1].sum(-1)
+        return out
+
+    def patch_maps(self, image: int = 0) -> torch.Tensor:
+        """fp32 [n_layers, B, A, g, g] with g * g = patches per image: the attention of each action row over image `image`'s patch grid."""
+        g = int(round(self.patches_per_image ** 0.5))
+        if g * g != self.patches_per_image:
+            raise ValueError(f"patch_maps: {self.patches_per_image} patches per image are not a square grid")
+        nl, B, A, _ = self.mean.shape
+        k0, k1 = self.layout[0][f"image{image}"]           # the image ranges are the same for every observation of a batch
+        return self.mean[:, :, :, k0:k1].reshape(nl, B, A, g, g)
+
+
+def _attention_layout(n_images: int, patches_per_image: int, P: int, S: int, text_lens, A: int, proprio: bool, timestep: bool = False):
+    """The named key ranges of each observation's multimodal sequence (ovla_assemble_multimodal: BOS, the P patch-side tokens, the text after
+    BOS).  `text_lens`: tokens of each text row (BOS, prompt, A action slots, stop)."""
+    layouts = []
+    for n in text_lens:
+        n = int(n)
+        lay, k = {"bos": (0, 1)}, 1
+        for i in range(n_images):
+            lay[f"image{i}"] = (k, k + patches_per_image)
+            k += patches_per_image
+        for name, on in (("proprio", proprio), ("timestep", timestep)):
+            if on:
+                lay[name] = (k, k + 1)
+                k += 1
+        assert k == P + 1, f"layout: {k - 1} patch-side tokens accounted for, the forward assembled {P}"
+        end = P + n
+        lay["text"], lay["actions"], lay["stop"], lay["padding"] = (k, end - A - 1), (end - A - 1, end - 1), (end - 1, end), (end, S)
+        layouts.append(lay)
+    return layouts
 
 
 class _VisionBackboneHandle:
@@ -581,6 +644,8 @@ class OpenVLAForActionPrediction(_StoreModule):
                       noisy_actions=noisy_actions, timestep_emb=diffusion_timestep_embeddings,
                       proprio_projector=None if proprio_projector is None else proprio_projector.comp,
                       noisy_action_projector=None if noisy_action_projector is None else noisy_action_projector.comp)
+        if output_attentions:
+            kwargs["attn_capture"] = AttnCapture(rows="all", per_head=True)
         if torch.is_grad_enabled():
             hidden, _ = _VLMFn.apply(self._anchor, self, kwargs, True)
         else:
@@ -647,13 +712,15 @@ class OpenVLAForActionPrediction(_StoreModule):
         return normalized.reshape(hidden.shape[0], cfg.chunk, cfg.action_dim)
 
     def _infer(self, ids, mask, labels, pixel_values, prop, *, batch: bool, action_head=None, proprio_projector=None, noisy_action_projector=None,
-               noise=None, policy=None):
+               noise=None, policy=None, attention: Optional[dict] = None):
         """The forward on prepared ids / mask / labels [B, L], the action rows, the head (L1, or the DDIM sampler from `noise`) or the token
         decode -> (normalised actions ndarray [B, chunk, action_dim], action hidden states [B, A, D] in a tensor of their own).
         `batch` is the mode.  False (predict_action): the planner's GEMM schedules, FiLM's average over all L positions, a graph per key.
         True (predict_action_batch): every GEMM under ops.batch_invariant(ops.BATCH_INVARIANT_DEFAULT), FiLM's average over each row's own
         tokens, "batch" graph keys under the LRU rule, and the token decode inside the graph.
-        `policy`: (adapter slot per observation, the policies' head components or None, their proprio projector components or None)."""
+        `policy`: (adapter slot per observation, the policies' head components or None, their proprio projector components or None).
+        `attention` (a dict to fill; output_attentions=True): the eager forward (routed with `policy`) with an AttnCapture of the action rows;
+        self._graphs is neither used nor touched.  It receives the capture's `mean` [n_layers, B*A, S] and the sequence's P and S."""
         cfg, eng = self.cfg, self.engine
         (B, L), A, D = ids.shape, cfg.num_action_tokens, cfg.llm_dim
         slots, heads, pps = policy if policy is not None else (None, None, None)
@@ -661,9 +728,13 @@ class OpenVLAForActionPrediction(_StoreModule):
         head_comp, nap_comp = getattr(action_head, "comp", None), getattr(noisy_action_projector, "comp", None)
         pp_comp = proprio_projector.comp if use_proprio and proprio_projector is not None else None
         use_diffusion = noisy_action_projector is not None and hasattr(action_head, "noise_scheduler")
+        if attention is not None and use_diffusion:
+            raise ValueError("output_attentions=True with a diffusion head: every DDIM step has its own maps (fifty sets per chunk), which is not supported")
+        use_graph = self.use_graph and attention is None
+        capture = AttnCapture(rows="actions") if attention is not None else None
         discrete = action_head is None and heads is None
         film, film_avg = batch and eng.use_film, None
-        if film and not self.use_graph:
+        if film and not use_graph:
             # FiLM's language average over each prompt's OWN tokens (padding would enter the mean: film_vit_wrapper.py:243): one ragged launch
             # for the batch, bit for bit ovla_language_average on each unpadded row.  (Under graph replay the launch is part of the graph.)
             film_avg = torch.zeros(((B + 7) // 8 * 8, D), dtype=BF16, device=self.device)
@@ -677,7 +748,7 @@ class OpenVLAForActionPrediction(_StoreModule):
                     noise = torch.randn((B, cfg.chunk, cfg.action_dim))
                 cur = torch.as_tensor(noise).to("cpu", torch.float32).reshape(B, cfg.chunk, cfg.action_dim).to(BF16).float()
                 ddim = (id(nap_comp), len(sched.timesteps), sched.config.num_train_timesteps)
-            if self.use_graph:
+            if use_graph:
                 def build():
                     invariant = ops.BATCH_INVARIANT_DEFAULT if batch else False
                     if use_diffusion:
@@ -726,7 +797,9 @@ class OpenVLAForActionPrediction(_StoreModule):
                 with route:
                     out = self.engine.forward(ids, mask, pixel_values, labels, proprio=prop, train=False,
                                               proprio_projector=SlotProjectors(pps, eng.route) if pps is not None else pp_comp, sel="actions",
-                                              film_avg=film_avg)
+                                              film_avg=film_avg, attn_capture=capture)
+                    if attention is not None:
+                        attention.update(mean=out["attention"]["mean"], P=out["P"], S=out["S"])
                     ah, _ = eng.action_hidden(out)                                            # rows P+NPT .. P+NPT+A-1 (:915-920)
                     hidden = ah.view(B, A, D).clone()
                     if heads is not None:
@@ -736,7 +809,7 @@ class OpenVLAForActionPrediction(_StoreModule):
             normalized = cur.numpy() if use_diffusion else self._decode(pred, bins, hidden)
         return normalized, hidden
 
-    def _infer_pooled(self, ids, mask, labels, pixel_values, prop, policy, use_proprio):
+    def _infer_pooled(self, ids, mask, labels, pixel_values, prop, policy, use_proprio, attention: Optional[dict] = None):
         """_infer(batch=True) of a pooled model: per pass of at most `resident` distinct policies (in order of first appearance) plan the
         residency, load what is missing (engine.load_slot: one launch per policy, on the stream of the forward), route each observation to its
         policy's slot.  The fixed schedules make an observation's bits independent of its batch, so the split does not show in the results."""
@@ -753,10 +826,19 @@ class OpenVLAForActionPrediction(_StoreModule):
             slot_of = st.commit(loads, needed)
             whole = len(passes) == 1
             sub = (lambda t: t) if whole else (lambda t: None if t is None else t[rows])
+            att_p = None if attention is None else {}
             n_p, h_p = self._infer(sub(ids), sub(mask), sub(labels), sub(pixel_values), sub(prop), batch=True,
-                                   policy=([slot_of[policy[b]] for b in rows], heads, pps))
+                                   policy=([slot_of[policy[b]] for b in rows], heads, pps), attention=att_p)
             if whole:
+                if attention is not None:
+                    attention.update(att_p)
                 return n_p, h_p
+            if attention is not None:   # the passes' maps, stitched by observation the way `hidden` is
+                m = att_p["mean"]
+                A = m.shape[1] // len(rows)
+                if "mean" not in attention:
+                    attention.update(mean=torch.empty((m.shape[0], len(policy) * A, m.shape[2]), dtype=m.dtype, device=m.device), P=att_p["P"], S=att_p["S"])
+                attention["mean"].view(m.shape[0], len(policy), A, m.shape[2])[:, rows] = m.view(m.shape[0], len(rows), A, m.shape[2])
             if normalized is None:
                 normalized = np.empty((len(policy),) + n_p.shape[1:], dtype=n_p.dtype)
                 hidden = torch.empty((len(policy),) + tuple(h_p.shape[1:]), dtype=h_p.dtype, device=h_p.device)
@@ -766,7 +848,7 @@ class OpenVLAForActionPrediction(_StoreModule):
     # -- predict_action (:946-1060) -------------------------------------------------------------------------------------
     @torch.no_grad()
     def predict_action(self, input_ids=None, unnorm_key=None, proprio=None, proprio_projector=None, action_head=None,
-                       noisy_action_projector=None, use_film: bool = False, **kwargs):
+                       noisy_action_projector=None, use_film: bool = False, output_attentions: bool = False, **kwargs):
         cfg = self.cfg
         if use_film != self.engine.use_film:
             raise ValueError(f"use_film={use_film} but the model was built with use_film={self.engine.use_film}")
@@ -785,14 +867,27 @@ class OpenVLAForActionPrediction(_StoreModule):
         labels[:, -1] = STOP_INDEX
         use_proprio = proprio_projector is not None and proprio is not None
         prop = torch.as_tensor(np.asarray(proprio), dtype=torch.float32) if use_proprio else None
+        attention = {} if output_attentions else None   # -> a third result, an ActionAttention (the eager forward; no graph is used or built)
         normalized, hidden = self._infer(ids, mask, labels, pixel_values, prop, batch=False, action_head=action_head, proprio_projector=proprio_projector,
-                                         noisy_action_projector=noisy_action_projector, noise=kwargs.get("noise"))
+                                         noisy_action_projector=noisy_action_projector, noise=kwargs.get("noise"), attention=attention)
+        if attention is not None:
+            return self._unnormalize_actions(normalized[0], unnorm_key), hidden, self._action_attention(attention, mask, pixel_values, use_proprio)
         return self._unnormalize_actions(normalized[0], unnorm_key), hidden
+
+    def _action_attention(self, attention: dict, mask, pixel_values, use_proprio: bool) -> ActionAttention:
+        """The ActionAttention of an _infer(attention=...) call on text rows `mask` [B, L] (right-padded)."""
+        mean, P, S = attention["mean"], attention["P"], attention["S"]
+        B, A = mask.shape[0], self.cfg.num_action_tokens
+        n_images = pixel_values.shape[1] // 6
+        n_vis = P - (1 if use_proprio else 0)
+        layout = _attention_layout(n_images, n_vis // n_images, P, S, mask.to("cpu").sum(1).tolist(), A, use_proprio)
+        return ActionAttention(mean.view(mean.shape[0], B, A, S), layout, n_vis // n_images)
 
     # -- batched inference (not in the reference: its predict_action asserts batch size 1) -----------------------------------------------
     @torch.no_grad()
     def predict_action_batch(self, prompts, pixel_values, unnorm_key=None, proprio=None, proprio_projector=None, action_head=None,
-                             noisy_action_projector=None, use_film: bool = False, noise=None, pad_to: Optional[int] = None, policy=None):
+                             noisy_action_projector=None, use_film: bool = False, noise=None, pad_to: Optional[int] = None, policy=None,
+                             output_attentions: bool = False):
         """predict_action for B observations in one forward.  prompts: list of B (input_ids, attention_mask) pairs ([1, L_b] or [L_b], lengths may
         differ; masks right-padded), pixel_values [B, 6 I, H, W], proprio [B, proprio_dim], noise [B, chunk, action_dim] (diffusion: each sample's
         DDIM trajectory starts from its own noise).  Returns (actions [B, chunk, action_dim] unnormalised with `unnorm_key`, action hidden states
@@ -806,7 +901,10 @@ class OpenVLAForActionPrediction(_StoreModule):
         (`unnorm_key` is looked up in the policy's own norm_stats when it has them); without per-policy heads the discrete token path with the
         shared lm_head.  `pad_to` repeats observation 0's policy.  On a model built with use_film="per_policy" (pass use_film=True) each observation's
         towers are modulated by its own policy's FiLM Linears (one ovla_film_vectors launch per forward), and `policy` is required.  A model with
-        its own FiLM Linears and diffusion heads are not supported with `policy`."""
+        its own FiLM Linears and diffusion heads are not supported with `policy`.
+        `output_attentions=True` returns a third element, an ActionAttention: the head-averaged attention of every observation's action rows, from the
+        eager forward (routed with `policy`; no graph is used or built).  An observation's maps are the same bits alone and in any batch, up to its own
+        key length; its padding keys are 0.  Not with a diffusion head (ValueError)."""
         cfg = self.cfg
         per_policy_film = bool(getattr(self.engine, "film_per_policy", False))
         if use_film != self.engine.use_film:
@@ -845,11 +943,15 @@ class OpenVLAForActionPrediction(_StoreModule):
                 return torch.cat([t, t[fill]])
 
             prop_p = rep(proprio)
-            actions, hidden = self.predict_action_batch(list(prompts) + [prompts[0]] * len(fill), rep(pixel_values), unnorm_key=unnorm_key,
-                                                        proprio=None if prop_p is None else prop_p.cpu().numpy(), proprio_projector=proprio_projector,
-                                                        action_head=action_head, noisy_action_projector=noisy_action_projector, use_film=use_film,
-                                                        noise=rep(noise), policy=None if policy is None else policy + [policy[0]] * len(fill))
-            return actions[:B], hidden[:B]
+            res = self.predict_action_batch(list(prompts) + [prompts[0]] * len(fill), rep(pixel_values), unnorm_key=unnorm_key,
+                                            proprio=None if prop_p is None else prop_p.cpu().numpy(), proprio_projector=proprio_projector,
+                                            action_head=action_head, noisy_action_projector=noisy_action_projector, use_film=use_film,
+                                            noise=rep(noise), policy=None if policy is None else policy + [policy[0]] * len(fill),
+                                            output_attentions=output_attentions)
+            if output_attentions:
+                att = res[2]
+                return res[0][:B], res[1][:B], ActionAttention(att.mean[:, :B], att.layout[:B], att.patches_per_image)
+            return res[0][:B], res[1][:B]
         use_proprio = proprio_projector is not None and proprio is not None
         if policy is not None:
             use_proprio = proprio is not None and next(iter(self._policies.values()))["pp"] is not None
@@ -881,21 +983,24 @@ class OpenVLAForActionPrediction(_StoreModule):
             ids[b, : len(r)], mask[b, : len(r)] = r, True
             labels[b, len(r) - A - 1: len(r)] = ACTION_TOKEN_BEGIN_IDX + 1
             labels[b, len(r) - 1] = STOP_INDEX
+        attention = {} if output_attentions else None
+        extra = (lambda: (self._action_attention(attention, mask, pixel_values, use_proprio),)) if output_attentions else (lambda: ())
         if policy is not None and self._pool_resident:
-            normalized, hidden = self._infer_pooled(ids, mask, labels, pixel_values, prop, policy, use_proprio)
+            normalized, hidden = self._infer_pooled(ids, mask, labels, pixel_values, prop, policy, use_proprio, attention=attention)
             stats = [self.policy_norm_stats(p) for p in policy]
-            return np.stack([self._unnormalize_actions(normalized[b], unnorm_key, stats[b]) for b in range(B)]), hidden
+            return (np.stack([self._unnormalize_actions(normalized[b], unnorm_key, stats[b]) for b in range(B)]), hidden) + extra()
         if policy is not None:   # each observation under its own policy's adapter slot, head, proprio projector and statistics
             names = list(self._policies)
             pols = list(self._policies.values())
             heads = [p["head"].comp for p in pols] if pols[0]["head"] is not None else None
             pps = [p["pp"].comp for p in pols] if use_proprio else None
-            normalized, hidden = self._infer(ids, mask, labels, pixel_values, prop, batch=True, policy=([names.index(p) for p in policy], heads, pps))
+            normalized, hidden = self._infer(ids, mask, labels, pixel_values, prop, batch=True, policy=([names.index(p) for p in policy], heads, pps),
+                                             attention=attention)
             stats = [self.policy_norm_stats(p) for p in policy]
-            return np.stack([self._unnormalize_actions(normalized[b], unnorm_key, stats[b]) for b in range(B)]), hidden
+            return (np.stack([self._unnormalize_actions(normalized[b], unnorm_key, stats[b]) for b in range(B)]), hidden) + extra()
         normalized, hidden = self._infer(ids, mask, labels, pixel_values, prop, batch=True, action_head=action_head, proprio_projector=proprio_projector,
-                                         noisy_action_projector=noisy_action_projector, noise=noise)
-        return np.stack([self._unnormalize_actions(normalized[b], unnorm_key) for b in range(B)]), hidden
+                                         noisy_action_projector=noisy_action_projector, noise=noise, attention=attention)
+        return (np.stack([self._unnormalize_actions(normalized[b], unnorm_key) for b in range(B)]), hidden) + extra()
 
     # -- statistics (:772-791, :1062-1087) -------------------------------------------------------------------------------
     @staticmethod

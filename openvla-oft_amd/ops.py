@@ -472,6 +472,43 @@ def attn_bwd(q, k, v, o, do, lse, B, S, H, hd, *, kv_len=None, causal=False, sca
     return dq, dk, dv
 
 
+def attn_probs(q, k, lse, B, S, H, hd, *, rows=None, kv_len=None, causal=False, scale=None, per_head=False, mean=True, out=None):
+    """The attention probabilities of the query rows `rows` (int32 device tensor of flattened rows b*S+s; None: all B*S rows), recomputed
+    from the q / k views and the `lse` of an `attn_fwd` call with the same kv_len, causal and scale.  Returns (P fp32 [R, H, S] or None,
+    P_mean fp32 [R, S] or None); `out=(P, P_mean)` supplies the buffers (either may be None).  Masked keys are exactly 0; a row index
+    outside [0, B*S) gives a zero row."""
+    for t in (q, k):
+        _chk(t)
+        assert t.stride(1) == 1 and t.shape[0] == B * S
+    _chk(lse, torch.float32, "lse")
+    assert lse.is_contiguous() and lse.numel() == B * H * S
+    if rows is not None:
+        _chk(rows, torch.int32, "rows")
+        assert rows.dim() == 1 and rows.is_contiguous()
+    R = B * S if rows is None else rows.numel()
+    P, Pm = out if out is not None else (None, None)
+    if out is None:
+        if not (per_head or mean):
+            raise ValueError("attn_probs: at least one of per_head and mean must be set")
+        if per_head:
+            P = torch.empty((R, H, S), dtype=torch.float32, device=q.device)
+        if mean:
+            Pm = torch.empty((R, S), dtype=torch.float32, device=q.device)
+    for t, shape, name in ((P, (R, H, S), "P"), (Pm, (R, S), "P_mean")):
+        if t is not None:
+            _chk(t, torch.float32, name)
+            assert tuple(t.shape) == shape and t.is_contiguous(), f"{name}: expected contiguous {shape}, got {tuple(t.shape)}"
+    g = STRUCTS["ovla_attn_probs_args"]()
+    g.Q, g.K, g.q_stride, g.k_stride = q.data_ptr(), k.data_ptr(), q.stride(0), k.stride(0)
+    g.lse, g.kv_len, g.rows, g.P, g.P_mean = lse.data_ptr(), _p(kv_len), _p(rows), _p(P), _p(Pm)
+    g.B, g.H, g.S, g.R, g.head_dim, g.causal = B, H, S, R, hd, int(causal)
+    g.scale = float(scale if scale is not None else hd ** -0.5)
+    e0 = _prof_begin()
+    _lib.call("ovla_attn_probs", g, _stream())
+    _prof_end(e0, "attn_probs", 2.0 * R * H * S * hd)
+    return P, Pm
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 def norm_fwd(x, weight, bias=None, *, eps, rms, out=None, save_stats=True):
     _chk(x); _chk(weight)
