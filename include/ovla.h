@@ -720,6 +720,67 @@ typedef struct {
 int ovla_adamw_clipped(const ovla_adamw_clipped_args* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Per-tensor statistics: for every trainable tensor of one flat buffer, the sum of squares of its gradient as AdamW sees it and of its
+ * parameter, the largest finite |gradient|, the number of non-finite gradient elements and a latch that counts the steps on which there
+ * were any -- what names the tensor that carried a NaN when the step guard above only says "skipped" (the reference reports such numbers
+ * through W&B; torch would need two tiny launches and a host synchronise per tensor).  Opt-in and read-only: it writes nothing but its own
+ * partials and out.  One table-driven launch pair per flat buffer, stream-ordered and capturable; every number is complete at a kernel
+ * boundary: no atomics, no grid barrier, no spin-wait, no cooperative launch, ordinary vector stores, and no host value depends on the data.
+ * THE STATS CONTRACT (identical in csrc/tensor_stats.hip and in the numpy restatement tests/tensor_stats_reference.py), for segment t =
+ * (offset_t, n_t) of the table:
+ *     r_i = grad[i] * grad_scale        one fp32 multiply, then rounded to bf16 (RNE) when grad_round_bf16 is set: exactly ovla_grad_sumsq's r_i
+ *   grad_sumsq   sum over the segment of (double)r_i * (double)r_i in ovla_grad_sumsq's FIXED order, with the chunks counted from the segment's
+ *                own start: chunk j of segment t covers offset_t + [j C, min(n_t, (j + 1) C)), C = OVLA_GRAD_SUMSQ_CHUNK, and is reduced by one
+ *                workgroup of L = OVLA_GRAD_SUMSQ_LANES lanes; element offset_t + j C + o belongs to lane (o / 4) % L and is added in ascending
+ *                o; the lane sums go through THE TREE of the clip contract; the segment's ceil(n_t / C) partials are summed as
+ *                ovla_grad_sumsq's second launch sums its P partials (lane j % L in ascending j, THE TREE again).  A one-entry table {0, n}
+ *                therefore gives ovla_grad_sumsq's slot bit for bit.  NaN and Inf propagate.
+ *   param_sumsq  the same sum over (double)param[i] * (double)param[i], same ownership and order; a bf16 parameter (param_is_bf16) is widened
+ *                exactly, an fp32 one (the fp32 buffer, or the fp32 master of a bf16 buffer) is taken as it is.
+ *   grad_absmax  the maximum of |r_i| over the finite r_i; 0 when there is none.
+ *   n_nonfinite  the number of r_i that are NaN or +-Inf.
+ *   n_bad_steps  in/out: incremented by 1 when n_nonfinite > 0, otherwise kept -- a latch that needs no per-step readback.  The caller
+ *                zeroes it once.
+ *   purity       a pure function of the segment's elements, the table and the scalars: nothing depends on the grid, on the previous contents
+ *                of partials or out (other than n_bad_steps), on the other segments or on which hardware lane holds an element.
+ *   memory       reads exactly the segments' elements of grad and param -- the padding between segments is never read -- in 16-byte groups
+ *                of four gradients (8 bytes of a bf16 parameter), the last n_t % 4 elements one by one by the lane that owns their group.
+ *                Writes partials[0 .. 32 total_chunks) and out[0 .. n_segs), nothing else.  Two launches: one workgroup per chunk, which finds
+ *                its segment by a binary search of chunk_start, then one workgroup per segment.
+ *   segments     n_t == 0 is legal: zero chunks, an all-zero output, n_bad_steps kept.
+ *   the plan     ovla_tensor_stats_plan (host only, no device call) checks the table and writes chunk_start[t] = the number of chunks of the
+ *                segments before t, t in [0, n_segs]; chunk_start[n_segs] is total_chunks.  The caller copies segs and chunk_start to the
+ *                device once.  The library remembers the (n_segs, total_chunks) pair of every plan made in the process, which is all the
+ *                launch can check of a table that lives in device memory.
+ *   refusals     OVLA_EINVAL before any launch.  From the plan: a null pointer, n_segs < 1, buffer_n < 0, a negative n or offset, offset % 8
+ *                != 0, segments not ascending or overlapping (offset_t < offset_{t-1} + n_{t-1}), a segment past buffer_n, more chunks than
+ *                a grid covers.  From the launch: a null pointer, n_segs < 1, total_chunks < 0, grad or param not 16-byte aligned, out, partials or
+ *                segs not 8-byte aligned, chunk_start not 4-byte aligned, partials_bytes < OVLA_TENSOR_STATS_PARTIAL_BYTES total_chunks, and a
+ *                (n_segs, total_chunks) pair no plan of this process produced (total_chunks different from the plan's). */
+#define OVLA_TENSOR_STATS_PARTIAL_BYTES 32
+typedef struct { int64_t offset, n; } ovla_tensor_seg;   /* elements of the flat buffer; offset % 8 == 0 */
+typedef struct {
+  double grad_sumsq, param_sumsq;
+  float grad_absmax;
+  int32_t n_bad_steps;
+  int64_t n_nonfinite;
+} ovla_tensor_stat;                                       /* 32 bytes */
+int ovla_tensor_stats_plan(const ovla_tensor_seg* segs, int32_t n_segs, int64_t buffer_n, int32_t* chunk_start /* n_segs + 1 */);
+typedef struct {
+  const float* grad;                /* fp32 flat gradient buffer */
+  const void* param;                /* bf16 or fp32 (param_is_bf16) flat parameter buffer, the same element indices */
+  int32_t param_is_bf16, grad_round_bf16;
+  float grad_scale;
+  const ovla_tensor_seg* segs;      /* device [n_segs] */
+  const int32_t* chunk_start;       /* device [n_segs + 1] */
+  int32_t n_segs, total_chunks;
+  void* partials;
+  int64_t partials_bytes;           /* >= OVLA_TENSOR_STATS_PARTIAL_BYTES * total_chunks */
+  ovla_tensor_stat* out;            /* device [n_segs]; n_bad_steps is in/out, every other field is written */
+} ovla_tensor_stats_args;
+int ovla_tensor_stats(const ovla_tensor_stats_args* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * AdamW on fp32 master weights: the optimizer step of a bf16 parameter buffer whose state is kept in fp32 (opt-in,
  * ParamStore.enable_fp32_state; the default stays ovla_adamw's torch-faithful bf16 state).  In bf16, exp_avg_sq.mul_(0.999) returns its
  * input for every normal value (the decrement is below half an ulp: the second moment never decays) and a parameter update below half an

@@ -65,8 +65,11 @@ def parse_header(path: Path = HEADER_PATH):
                 while var.startswith("*"):
                     ctype_name += "*"
                     var = var[1:].strip()
-                ct = _CTYPE[ctype_name]
-                am = re.match(r"^(\w+)\s*\[\s*(\d+)\s*\]$", var)      # fixed-size array member, e.g. `float mean[6]`
+                if ctype_name.endswith("*") and ctype_name.rstrip("*") in structs:   # a pointer to an earlier struct of the header: an address
+                    ct = ctypes.c_void_p
+                else:
+                    ct = _CTYPE[ctype_name]
+                am =re.match(r"^(\w+)\s*\[\s*(\d+)\s*\]$", var)      # fixed-size array member, e.g. `float mean[6]`
                 if am:
                     var, ct = am.group(1), ct * int(am.group(2))
                 fields.append((var, ct))

@@ -8,30 +8,11 @@
 // No atomics, no grid barrier, no spin-wait; nothing is read back.
 #pragma clang fp contract(off)
 #include "adamw_elem.h"
+#include "sumsq_order.h"
 
 namespace {
 
-constexpr int kChunk = OVLA_GRAD_SUMSQ_CHUNK, kLanes = OVLA_GRAD_SUMSQ_LANES;
-constexpr int kTrips = kChunk / (4 * kLanes);   // 16-byte loads per lane and full chunk
-static_assert(kLanes == 256 && kChunk % (4 * kLanes) == 0, "the tree below pairs four waves of 64 lanes");
-
-template <bool BF>
-OVLA_DEV double sq(float g, float scale) {
-  float r = g * scale;
-  if (BF) r = bfround(r);
-  const double d = (double)r;
-  return d * d;   // exact: 24 x 24 significant bits
-}
-
-// THE TREE of the contract: within each wave h = 32 .. 1: s[t] += s[t + h] for t < h (lanes t >= h compute values nobody reads), then
-// (w0 + w1) + (w2 + w3) over the four wave totals.  The result is valid in every lane.
-OVLA_DEV double block_tree(double acc, double* wave_total /* LDS [4] */) {
-#pragma unroll
-  for (int h = 32; h > 0; h >>= 1) acc += __shfl_down(acc, h, 64);
-  if ((threadIdx.x & 63) == 0) wave_total[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  return (wave_total[0] + wave_total[1]) + (wave_total[2] + wave_total[3]);
-}
+using namespace sumsq_order;   // kChunk, kLanes, kTrips, sq and THE TREE (block_tree): shared with tensor_stats.hip
 
 template <bool BF>
 __global__ __launch_bounds__(kLanes) void sumsq_chunk_kernel(const float* __restrict__ g, int64_t n, float scale, double* __restrict__ partials) {

@@ -1346,6 +1346,60 @@ class VLAEngine:
         self._grad_clip["state"][3:6].copy_(torch.tensor(counters, dtype=torch.int32))
         return True
 
+    # -- per-tensor statistics (ovla.h "Per-tensor statistics"): opt-in, read-only -------------------------------------------------------------------
+    _tensor_stats: Optional[dict] = None
+
+    @property
+    def tensor_stats_enabled(self) -> bool:
+        return self._tensor_stats is not None
+
+    def enable_tensor_stats(self):
+        """Allocates what collect_tensor_stats needs: per (store, dtype) flat buffer -- in `stores` order, bf16 before fp32 -- the segment table
+        of its tensors (Param.offset, Param.numel, ascending offset) and its plan, copied to the device once; one zeroed `out` record per
+        tensor (the n_bad_steps latches start at 0 and are not checkpointed) and one partials workspace shared by the buffers.  Idempotent.
+        Refused inside ema_weights(): the flat buffers hold the averaged weights."""
+        self._not_in_ema_scope("enable_tensor_stats")
+        if self._tensor_stats is not None:
+            return
+        tables, names = [], []
+        for st in self.stores:
+            for dt, flat in st.flat.items():
+                params = sorted((p for p in st.params if p.dtype == dt), key=lambda p: p.offset)
+                plan = ops.tensor_stats_plan([(p.offset, p.numel) for p in params], flat.numel(), device=self.device)
+                tables.append(dict(store=st, dtype=dt, plan=plan, first=len(names)))
+                names += [p.name for p in params]
+        assert len(set(names)) == len(names), "two trainable tensors share a name"
+        out, partials = ops.tensor_stats_buffers(len(names), max(t["plan"]["total_chunks"] for t in tables), self.device)
+        self._tensor_stats = dict(tables=tables, names=names, out=out, partials=partials)
+
+    def collect_tensor_stats(self, grad_scale: float = 1.0):
+        """One launch pair per flat buffer: the statistics of every trainable tensor's gradient as adamw_step(grad_scale=...) will see it (the
+        same `is_bf16 and not fp32_state` rounding rule as its norm) and of its parameter (in fp32-state mode the fp32 master), into the device
+        records.  Call it after the reducer and before adamw_step.  Writes nothing but its own records; nothing is read back."""
+        self._not_in_ema_scope("collect_tensor_stats")
+        ts = self._tensor_stats
+        if ts is None:
+            raise RuntimeError("collect_tensor_stats without enable_tensor_stats()")
+        for t in ts["tables"]:
+            st, dt, n = t["store"], t["dtype"], t["plan"]["n_segs"]
+            ops.tensor_stats(t["plan"], st.flat_grad[dt], st.master.get(dt, st.flat[dt]), ts["out"][t["first"]: t["first"] + n], ts["partials"],
+                             grad_round_bf16=dt == BF16 and not st.fp32_state, grad_scale=grad_scale)
+
+    def tensor_stats(self) -> Dict[str, Dict[str, float]]:
+        """The records of the last collect_tensor_stats, {name: {grad_norm, param_norm, grad_absmax, n_nonfinite, n_bad_steps}} in table order,
+        keyed by the stores' ParamStore.named() names; the norms are the square roots of the double sums (NaN or inf as computed).  The
+        feature's ONLY readback: it waits for the device, so call it where the host synchronises anyway."""
+        if self._tensor_stats is None:
+            raise RuntimeError("tensor_stats without enable_tensor_stats()")
+        rec = ops.read_tensor_stats(self._tensor_stats["out"])
+        return {name: {"grad_norm": math.sqrt(r["grad_sumsq"]), "param_norm": math.sqrt(r["param_sumsq"]), "grad_absmax": float(r["grad_absmax"]),
+                       "n_nonfinite": int(r["n_nonfinite"]), "n_bad_steps": int(r["n_bad_steps"])}
+                for name, r in zip(self._tensor_stats["names"], rec)}
+
+    def first_nonfinite(self) -> Optional[str]:
+        """The first tensor, in table order, whose last collected gradient held a NaN or Inf; None when there is none (this reads back)."""
+        return next((name for name, s in self.tensor_stats().items() if s["n_nonfinite"] > 0), None)
+
     # -- fp32 optimizer state (ovla.h "AdamW on fp32 master weights") -----------------------------------------------------------------------------
     @property
     def optimizer_state_precision(self) -> str:

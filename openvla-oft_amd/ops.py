@@ -1140,6 +1140,66 @@ def grad_sumsq(grad, slots, slot, workspace, *, is_bf16, grad_scale=1.0, n=None)
     _lib.call("ovla_grad_sumsq", g, _stream())
 
 
+# -- per-tensor statistics (ovla.h "Per-tensor statistics"): the segmented form of grad_sumsq -------------------------------------------------
+TENSOR_STATS_PARTIAL_BYTES = 32   # OVLA_TENSOR_STATS_PARTIAL_BYTES: one ovla_tensor_stat record per chunk
+TENSOR_STAT_DTYPE = [("grad_sumsq", "<f8"), ("param_sumsq", "<f8"), ("grad_absmax", "<f4"), ("n_bad_steps", "<i4"), ("n_nonfinite", "<i8")]
+
+
+def tensor_stats_plan(segments, buffer_n: int, device=None) -> dict:
+    """Checks a segment table [(offset, n), ...] (elements of a flat buffer of `buffer_n` elements: ascending, disjoint, offset % 8 == 0) on
+    the host and returns the plan of ovla_tensor_stats for it: `chunk_start` (numpy int32 [n_segs + 1], the prefix sums of the segments'
+    chunk counts), `total_chunks`, `n_segs`, the table as `segs_host`, and with `device` the device copies `segs` / `chunk_start_dev` (made
+    here, once).  Host only when `device` is None: no device call."""
+    import numpy as np
+
+    assert ctypes.sizeof(STRUCTS["ovla_tensor_seg"]) == 16 and ctypes.sizeof(STRUCTS["ovla_tensor_stat"]) == TENSOR_STATS_PARTIAL_BYTES
+    segs = np.ascontiguousarray(np.asarray(list(segments), dtype=np.int64).reshape(-1, 2))
+    chunk_start = np.zeros(segs.shape[0] + 1, np.int32)
+    rc = _lib.lib().ovla_tensor_stats_plan(ctypes.cast(segs.ctypes.data, ctypes.POINTER(STRUCTS["ovla_tensor_seg"])), segs.shape[0], int(buffer_n),
+                                           chunk_start.ctypes.data)
+    _lib.check(rc, "ovla_tensor_stats_plan")
+    plan = dict(segs_host=segs, chunk_start=chunk_start, n_segs=int(segs.shape[0]), total_chunks=int(chunk_start[-1]))
+    if device is not None:
+        plan["segs"] = torch.from_numpy(segs.reshape(-1)).to(device)
+        plan["chunk_start_dev"] = torch.from_numpy(chunk_start).to(device)
+    return plan
+
+
+def tensor_stats_buffers(n_segs: int, total_chunks: int, device):
+    """(out, partials): `out` zeroed int64 [n_segs, 4] (one 32-byte ovla_tensor_stat per segment: the n_bad_steps latches start at 0),
+    `partials` int64 [max(1, total_chunks), 4] (one record per chunk; its contents never matter)."""
+    return (torch.zeros((n_segs, 4), dtype=torch.int64, device=device), torch.empty((max(1, total_chunks), 4), dtype=torch.int64, device=device))
+
+
+def tensor_stats_args(plan, grad, param, out, partials, *, grad_round_bf16, grad_scale=1.0):
+    """The ovla_tensor_stats_args of tensor_stats, as that call fills them (the tests change one field at a time for the refusals)."""
+    assert grad.dtype == torch.float32 and param.dtype in (BF16, torch.float32) and grad.is_contiguous() and param.is_contiguous()
+    assert out.dtype == torch.int64 and partials.dtype == torch.int64 and out.is_contiguous() and partials.is_contiguous()
+    assert out.numel() * 8 >= TENSOR_STATS_PARTIAL_BYTES * plan["n_segs"]
+    g = STRUCTS["ovla_tensor_stats_args"]()
+    g.grad, g.param, g.param_is_bf16, g.grad_round_bf16, g.grad_scale = grad.data_ptr(), param.data_ptr(), int(param.dtype == BF16), int(grad_round_bf16), grad_scale
+    g.segs, g.chunk_start, g.n_segs, g.total_chunks = plan["segs"].data_ptr(), plan["chunk_start_dev"].data_ptr(), plan["n_segs"], plan["total_chunks"]
+    g.partials, g.partials_bytes, g.out = partials.data_ptr(), partials.numel() * 8, out.data_ptr()
+    return g
+
+
+def tensor_stats(plan, grad, param, out, partials, *, grad_round_bf16, grad_scale=1.0):
+    """out[t] <- the statistics of segment t of the flat fp32 gradient buffer `grad` as AdamW sees it (times grad_scale, rounded to bf16 when
+    `grad_round_bf16`) and of the flat parameter buffer `param` (bf16 or fp32), one launch pair for the whole table; out[t].n_bad_steps is
+    incremented where the segment holds a non-finite gradient.  `plan` is tensor_stats_plan(..., device=...)'s.  Nothing is read back."""
+    _lib.call("ovla_tensor_stats", tensor_stats_args(plan, grad, param, out, partials, grad_round_bf16=grad_round_bf16, grad_scale=grad_scale), _stream())
+
+
+def read_tensor_stats(out, n_segs=None):
+    """`out` on the host (this synchronises) as a numpy structured array of ovla_tensor_stat records: grad_sumsq, param_sumsq (double),
+    grad_absmax (float), n_bad_steps (int32), n_nonfinite (int64)."""
+    import numpy as np
+
+    raw = out.detach().cpu().contiguous().numpy().reshape(-1, 4)
+    rec = raw.view(np.dtype(TENSOR_STAT_DTYPE)).reshape(-1)
+    return rec if n_segs is None else rec[:n_segs]
+
+
 def grad_clip_coef(slots, state, max_norm, skip_nonfinite=True, n_slots=None):
     """state <- norm over slots[0 .. n_slots), clip coefficient, skip flag and counters (one tiny launch, nothing read back)."""
     assert slots.dtype == torch.float64 and slots.is_contiguous() and state.dtype == torch.int32 and state.numel() == 6 and state.is_contiguous()

@@ -19,6 +19,7 @@ import contextlib
 import json
 import math
 import os
+import re
 from dataclasses import dataclass
 from pathlib import Path
 from typing import Dict, Iterable, Optional, Tuple
@@ -333,6 +334,33 @@ def sampled_l1_metrics(engine: VLAEngine, batch: dict) -> Dict[str, float]:
     return {"curr_action_l1_loss": torch.nn.L1Loss()(gt[:, 0], pred[:, 0]).item(), "next_actions_l1_loss": torch.nn.L1Loss()(gt[:, 1:], pred[:, 1:]).item()}
 
 
+def tensor_stats_group(name: str) -> str:
+    """The owning module of a trainable tensor, the key of history["tensor_stats"]: each decoder layer, each vision tower, the projector
+    and each head-side store (proprio_projector, action_head, noisy_action_projector) by the first component of its name."""
+    m = re.match(r"language_model\.model\.layers\.\d+", name)
+    if m:
+        return m.group(0)
+    for tower in ("vision_backbone.fused_featurizer", "vision_backbone.featurizer"):
+        if name.startswith(tower + "."):
+            return tower
+    return name.split(".", 1)[0]
+
+
+def group_tensor_stats(table: Dict[str, Dict[str, float]]) -> Dict[str, Dict[str, float]]:
+    """VLAEngine.tensor_stats() summed per tensor_stats_group: the group norms are the square roots of the summed squares (NaN and inf
+    propagate), grad_absmax the maximum, n_nonfinite the sum."""
+    groups: Dict[str, Dict[str, float]] = {}
+    for name, s in table.items():
+        g = groups.setdefault(tensor_stats_group(name), {"grad_norm": 0.0, "param_norm": 0.0, "grad_absmax": 0.0, "n_nonfinite": 0})
+        g["grad_norm"] += s["grad_norm"] * s["grad_norm"]
+        g["param_norm"] += s["param_norm"] * s["param_norm"]
+        g["grad_absmax"] = max(g["grad_absmax"], s["grad_absmax"])
+        g["n_nonfinite"] += s["n_nonfinite"]
+    for g in groups.values():
+        g["grad_norm"], g["param_norm"] = math.sqrt(g["grad_norm"]), math.sqrt(g["param_norm"])
+    return groups
+
+
 def run_validation(engine: VLAEngine, cfg: FinetuneConfig, val_batches: Iterable[dict], log_step: int, log, *, discrete: bool, make_diffusion=None,
                    metric_fn=None, sample_l1: bool = False) -> Dict[str, float]:
     """finetune.py:678-760: the training loss (and, for the discrete objective, the token metrics; with `sample_l1`, the diffusion objective's
@@ -366,7 +394,7 @@ def finetune(cfg: FinetuneConfig, *, model_config: VLAConfig = OPENVLA_7B, state
              dataset: Optional[Iterable[dict]] = None, dataset_statistics: Optional[dict] = None, log=print, tokenizer=None,
              val_dataset=None, diffusion_noise: str = "host", ema_decay: Optional[float] = None, ema_power: Optional[float] = 0.75,
              ema_inv_gamma: float = 1.0, ema_update_after: int = 0, max_grad_norm: Optional[float] = None,
-             skip_nonfinite_steps: bool = True, optimizer_state: str = "param") -> Dict[str, list]:
+             skip_nonfinite_steps: bool = True, optimizer_state: str = "param", tensor_stats_freq: Optional[int] = None) -> Dict[str, list]:
     """finetune.py:763-1154.  Returns the logged metric history.  Data source, in this order: `dataset` (any iterable of collated
     batches); an episode store at `cfg.data_root_dir / cfg.dataset_name` (prismatic/vla/datasets/rlds_free.py: the reference's
     RLDSDataset + RLDSBatchTransform + collator, finetune.py:981-1016, with the frames augmented and normalised on the device --
@@ -396,7 +424,18 @@ def finetune(cfg: FinetuneConfig, *, model_config: VLAConfig = OPENVLA_7B, state
     and the norm is taken over the unrounded gradient.  The model checkpoints keep their format (they hold bf16_rne(master)); the
     optimizer-state file holds fp32 moments and `store{i}.bf16.master`, and loads only into an "fp32" run, while an "fp32" run resumes from a
     "param" checkpoint by widening.  The master is rank-local and identical on every rank; with the default OVLA_DP_COMM_DTYPE=param the reduced
-    gradient of the bf16 buffers has passed through a bf16 wire, OVLA_DP_COMM_DTYPE=fp32 keeps it in full precision."""
+    gradient of the bf16 buffers has passed through a bf16 wire, OVLA_DP_COMM_DTYPE=fp32 keeps it in full precision.
+    `tensor_stats_freq=k` (k >= 1; None: nothing of this runs) collects, on the optimizer steps with log_step % k == 0, the per-tensor
+    statistics of VLAEngine.collect_tensor_stats -- gradient norm as AdamW sees it, parameter norm, largest finite |gradient|, non-finite count
+    of every trainable tensor -- on the device, between the reducer and the optimizer step, one launch pair per flat buffer and no readback.
+    A logging step after a collection reads the records back once: history gains `tensor_stats`, a list of (collected step, {group: {grad_norm,
+    param_norm, grad_absmax, n_nonfinite}}) per owning module (tensor_stats_group), and `nonfinite_tensors`, the sorted names whose gradient
+    has been non-finite on a collected step so far; rank 0 appends one JSON line {"step", "tensors": {name: {...}}} with the full table to
+    `run_dir/tensor_stats.jsonl`.  With the step guard on, a log line whose skipped count rose names up to three tensors whose n_bad_steps
+    rose with it.  The statistics are rank-local and identical on every rank (they are taken of the reduced gradient), so only rank 0 writes.
+    The n_bad_steps counters are NOT checkpointed: they restart at 0 on resume."""
+    if tensor_stats_freq is not None and (isinstance(tensor_stats_freq, bool) or not isinstance(tensor_stats_freq, int) or tensor_stats_freq < 1):
+        raise ValueError(f"tensor_stats_freq = {tensor_stats_freq!r} (an integer >= 1, or None)")
     if optimizer_state not in ("param", "fp32"):
         raise ValueError(f'optimizer_state = {optimizer_state!r} ("param" or "fp32")')
     if max_grad_norm is not None and not float(max_grad_norm) > 0.0:   # NaN fails the comparison too
@@ -467,6 +506,8 @@ def finetune(cfg: FinetuneConfig, *, model_config: VLAConfig = OPENVLA_7B, state
             resumed_clip = load_grad_clip_state(Path(cfg.vla_path), cfg.resume_step, engine)
             log(f"[finetune] gradient clipping continues its counters: {engine.grad_clip_stats()}" if resumed_clip else
                 "[finetune] the checkpoint holds no grad_clip counters: they start at 0")
+    if tensor_stats_freq is not None:
+        engine.enable_tensor_stats()
     reducer = GradReducer(engine.stores, world) if world > 1 else None
     engine.attach_reducer(reducer, overlap=cfg.grad_accumulation_steps == 1 and os.environ.get("OVLA_DP_OVERLAP", "1") != "0")   # overlap only when every backward ends a step
     if dataset is None and (Path(cfg.data_root_dir) / cfg.dataset_name).is_dir():
@@ -520,6 +561,11 @@ def finetune(cfg: FinetuneConfig, *, model_config: VLAConfig = OPENVLA_7B, state
         history["ema_decay"] = []
     if grad_clip:
         history.update({"grad_norm": [], "grad_clip_coef": [], "skipped_steps": []})
+    if tensor_stats_freq is not None:
+        history.update({"tensor_stats": [], "nonfinite_tensors": []})
+    stats_step = None                    # the step of a collection not yet read back
+    stats_table, bad_seen = {}, {}       # the last table read back; each tensor's n_bad_steps at the last logging step
+    skipped_seen = engine.grad_clip_stats()["skipped"] if grad_clip and tensor_stats_freq is not None else 0
 
     def make_diffusion(batch):   # DiffusionActionHead.sample_noisy_actions (action_heads.py:167-197)
         if device_noise:
@@ -555,6 +601,9 @@ def finetune(cfg: FinetuneConfig, *, model_config: VLAConfig = OPENVLA_7B, state
             if reducer is not None:
                 reducer.all_reduce()
             lr = learning_rate_at(cfg, gradient_step_idx)
+            if tensor_stats_freq is not None and log_step % tensor_stats_freq == 0:   # of the gradient adamw_step is about to see
+                engine.collect_tensor_stats(grad_scale=1.0 / world)
+                stats_step = log_step
             engine.adamw_step(lr, grad_scale=1.0 / world)
             if ema_decay is not None:
                 decay = ema_decay_at(engine.ema_step + 1, max_decay=ema_decay, power=ema_power, inv_gamma=ema_inv_gamma, update_after=ema_update_after)
@@ -576,6 +625,20 @@ def finetune(cfg: FinetuneConfig, *, model_config: VLAConfig = OPENVLA_7B, state
                     history["grad_clip_coef"].append(stats["coef"])
                     history["skipped_steps"].append(stats["skipped"])
                     clip_note = f" grad_norm {stats['norm']:.4g} clip_coef {stats['coef']:.4g} skipped {stats['skipped']}"
+                if stats_step is not None:   # the statistics' only readback, once per collection that a logging step follows
+                    stats_table = engine.tensor_stats()
+                    history["tensor_stats"].append((stats_step, group_tensor_stats(stats_table)))
+                    history["nonfinite_tensors"].append(sorted(n for n, s in stats_table.items() if s["n_bad_steps"] > 0))
+                    if rank == 0:
+                        with open(run_dir / "tensor_stats.jsonl", "a") as f:
+                            f.write(json.dumps({"step": stats_step, "tensors": stats_table}) + "\n")
+                    stats_step = None
+                if tensor_stats_freq is not None:
+                    rose = [n for n, s in stats_table.items() if s["n_bad_steps"] > bad_seen.get(n, 0)]
+                    if grad_clip and stats["skipped"] > skipped_seen and rose:
+                        clip_note += f" non-finite gradient in {', '.join(rose[:3])}" + (f" (+{len(rose) - 3} more)" if len(rose) > 3 else "")
+                    bad_seen = {n: s["n_bad_steps"] for n, s in stats_table.items()}
+                    skipped_seen = stats["skipped"] if grad_clip else 0
                 if rank == 0:
                     log(f"step {log_step}: loss {history['loss_value'][-1]:.5f} lr {lr:.2e}{clip_note}")
             if cfg.use_val_set and log_step > 0 and log_step % cfg.val_freq == 0:   # finetune.py:1128-1144
