@@ -870,6 +870,63 @@ typedef struct {
 } ovla_diffusion_noise_args;
 int ovla_diffusion_noise(const ovla_diffusion_noise_args* a, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Token sampling and the policy-gradient objective (the discrete action-token path beyond greedy decode and cross entropy: draw the chunk's
+ * tokens from the tempered softmax over a token window, report their log-probabilities and entropy, and the gradient of the PPO / GRPO
+ * clipped surrogate).  Everything stays on the device; the position of the random stream is the 32-bit `call` the caller advances once per
+ * draw and checkpoints.  One workgroup of 256 lanes per row, always: a row's bits depend on neither the row count nor the row's position.
+ * The row reductions are csrc/token_row.h, the body ovla_token_ce is built from.  THE SAMPLING CONTRACT (identical in csrc/token_sample.hip
+ * and in the numpy restatement tests/token_sample_reference.py), for one row z[0 .. vocab) of bf16 logits, window [lo, hi), temperature T:
+ *   scale       invT = 1.0f / T (IEEE division);  s_j = float(z_j) * invT, one rounded fp32 multiply (no FMA contraction anywhere below).
+ *   generator   Philox4x32-10 as in "LoRA dropout" above.  Token id j (ABSOLUTE, not relative to the window) takes word w = o[j & 3] of
+ *               o = philox(j >> 2, row_key, 3, call) with key (seed_lo, seed_hi).  row_key is row_key[r], or r itself without the array.
+ *   uniform     u = float(2 (w >> 9) + 1) * 2^-24: exact in fp32, strictly inside (0, 1), symmetric about 1/2.
+ *   Gumbel      g = -logf(-logf(u)) with the accurate logf (the winners have u near 1, where -log u is tiny and a fast log's absolute
+ *               error would dominate).  g lies in [-2.812, 16.636].
+ *   draw        key_j = s_j + g;  token = the LOWEST index of the maximum key over the window (Gumbel-max: P(token = j) = softmax(s)_j).
+ *               A NaN key never wins; -inf inside the window has probability 0 and is never drawn.
+ *   logprob     lse = __logf(sum_j __expf(s_j - m)) + m over the window, m = max_j s_j, in token_row.h's order (lane t sums j = lo + t,
+ *               lo + t + 256, ...; wave butterfly; (w0 + w1) + (w2 + w3));  logprob = s_token - lse.
+ *   entropy     lse - (sum_j e_j s_j) / (sum_j e_j), e_j = __expf(s_j - m), a term with e_j == 0 skipped, the numerator in the same order.
+ *   degenerate  a window whose maximum is not finite (all -inf; or a +inf): token = lo, logprob = entropy = NaN.
+ *   isolation   columns outside [lo, hi) influence nothing, whatever they hold; columns >= vocab are never read.
+ *   bin         clip(n_tokens - token - 1, 0, n_bins - 1), ovla_argmax_bins' rule.
+ * state_dev (optional, DEVICE uint32[3] = seed_lo, seed_hi, call) overrides the three host values when the kernel runs, so a captured graph
+ * draws fresh values on every replay.  With a 16-byte aligned base and ld % 8 == 0 the key pass loads whole 8-column groups as 16 bytes and
+ * does the head and the tail of the window column by column.  logits bf16 [rows, ld]; token / bin int32 [rows]; logprob / entropy fp32
+ * [rows] (entropy optional); row_key int32 [rows] (optional).
+ *
+ * ovla_token_pg: for GIVEN tokens (clamped into the window), in one launch, the same logprob and entropy and
+ *   ratio   = expf(logprob - old_logprob[r])     (accurate expf), or exactly 1 without old_logprob
+ *   gate    = 0 if (adv >= 0 and ratio > clip_hi) or (adv < 0 and ratio < clip_lo), otherwise ratio;   clipped[r] = (gate == 0)
+ *   c       = ((adv[r] * gate) * grad_scale) * invT
+ *   dlogits[r, j] = bf16(fmaf(e_j, 1.0f / sum, -[j == token]) * c) for j in the window, +0 for every other j < vocab   (optional; may alias logits)
+ * the gradient of -sum_r min(ratio A, clip(ratio, clip_lo, clip_hi) A) * grad_scale.  A gated row is STORED as zeros, never multiplied
+ * through (ovla_lora_route's convention).  With T = 1, the window [0, vocab), no old_logprob, adv = 1: dlogits and -logprob are
+ * ovla_token_ce's dlogits and loss_rows bit for bit.  advantage / old_logprob fp32 [rows] on the device; tokens int32 [rows].
+ *
+ * Both are stream-ordered and capturable, use no atomics and no workspace, and launch nothing on OVLA_EINVAL: a null pointer, rows or vocab
+ * <= 0, ld < vocab, a window that is empty or leaves [0, vocab], T <= 0 or NaN or inf, clip_lo > clip_hi or a NaN bound. */
+typedef struct {
+  const void* logits; int64_t ld;
+  int32_t* token; int32_t* bin; float* logprob; float* entropy;
+  const uint32_t* state_dev; const int32_t* row_key;
+  uint32_t seed_lo, seed_hi, call;
+  float temperature;
+  int32_t rows, vocab, lo, hi, n_tokens, n_bins;
+} ovla_sample_tokens_args;
+int ovla_sample_tokens(const ovla_sample_tokens_args* a, void* stream);
+
+typedef struct {
+  const void* logits; int64_t ld;
+  const int32_t* tokens; const float* advantage; const float* old_logprob;
+  float* logprob; float* entropy; float* ratio; int32_t* clipped;
+  void* dlogits; int64_t ld_d;
+  float temperature, clip_lo, clip_hi, grad_scale;
+  int32_t rows, vocab, lo, hi;
+} ovla_token_pg_args;
+int ovla_token_pg(const ovla_token_pg_args* a, void* stream);
+
 /* fp32 -> bf16 convert with scale (publishes .grad views), and fill */
 typedef struct { const float* src; void* dst; int64_t n; float scale; } ovla_cvt_args;
 int ovla_cvt_f32_to_bf16(const ovla_cvt_args* a, void* stream);

@@ -2,6 +2,7 @@
 // AdamW step.  Reference: prismatic/models/action_heads.py:69-81, vla-scripts/finetune.py:400,407,952.
 #include "common.h"
 #include "adamw_elem.h"
+#include "token_row.h"
 #include <math.h>
 
 namespace {
@@ -125,53 +126,27 @@ __global__ __launch_bounds__(256) void adamw_f32_kernel(float* __restrict__ p, f
 __global__ __launch_bounds__(256) void token_ce_kernel(const bf16_bits* __restrict__ logits, int64_t ld, const int64_t* __restrict__ targets,
                                                        float* __restrict__ loss_rows, int* __restrict__ argmax_out, bf16_bits* dlogits, int64_t ld_d,
                                                        int vocab, float grad_scale) {
-  __shared__ float red_f[4];
-  __shared__ int red_i[4];
-  __shared__ float bc_f[2];
-  __shared__ int bc_i;
-  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  __shared__ token_row::Shared sh;
+  const int row = blockIdx.x, tid = threadIdx.x;
   const bf16_bits* x = logits + (int64_t)row * ld;
   int tgt = (int)targets[row];
   tgt = tgt < 0 ? 0 : (tgt >= vocab ? vocab - 1 : tgt);   // rows with an ignored label never get here (the caller gathers); no out-of-bounds read either way
   const float x_tgt = bf2f(x[tgt]);          // read before the barriers below: the gradient pass may overwrite the row in place
-  float m = -INFINITY; int mi = 0x7fffffff;
-  for (int j = tid; j < vocab; j += 256) {
-    const float v = bf2f(x[j]);
-    if (v > m) { m = v; mi = j; }            // j ascends per thread: the first maximum wins
-  }
-  // wave then block reduction of (max, lowest index of it)
-  for (int off = 32; off > 0; off >>= 1) {
-    const float om = __shfl_xor(m, off); const int oi = __shfl_xor(mi, off);
-    if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
-  }
-  if (lane == 0) { red_f[wave] = m; red_i[wave] = mi; }
-  __syncthreads();
+  const auto value = [x](int j) { return bf2f(x[j]); };
+  // the row reductions are token_row.h's (shared with ovla_sample_tokens / ovla_token_pg).  A row that is all -inf or holds only NaN (no column
+  // ever compared greater) reports column 0, argmax_bins_kernel's rule.
+  float m, s, unused; int mi;
+  token_row::row_max(value, 0, vocab, sh, m, mi);
+  token_row::row_sumexp<false>(value, 0, vocab, m, sh, s, unused);
   if (tid == 0) {
-    float bm = red_f[0]; int bi = red_i[0];
-    for (int w = 1; w < 4; ++w) if (red_f[w] > bm || (red_f[w] == bm && red_i[w] < bi)) { bm = red_f[w]; bi = red_i[w]; }
-    bc_f[0] = bm; bc_i = bi >= vocab ? 0 : bi;   // a row that is all -inf or holds only NaN (no column ever compared greater): column 0, argmax_bins_kernel's rule
-  }
-  __syncthreads();
-  m = bc_f[0];
-  float s = 0.0f;
-  for (int j = tid; j < vocab; j += 256) s += __expf(bf2f(x[j]) - m);
-  s = wave_sum(s);
-  if (lane == 0) red_f[wave] = s;
-  __syncthreads();
-  if (tid == 0) bc_f[1] = (red_f[0] + red_f[1]) + (red_f[2] + red_f[3]);
-  __syncthreads();
-  s = bc_f[1];
-  if (tid == 0) {
-    loss_rows[row] = (__logf(s) + m) - x_tgt;
-    argmax_out[row] = bc_i;
+    loss_rows[row] = token_row::lse(s, m) - x_tgt;
+    argmax_out[row] = mi;
   }
   if (dlogits) {
     const float inv = 1.0f / s;
     bf16_bits* d = dlogits + (int64_t)row * ld_d;
-    for (int j = tid; j < vocab; j += 256) {
-      const float p = __expf(bf2f(x[j]) - m) * inv;
-      d[j] = f2bf((p - (j == tgt ? 1.0f : 0.0f)) * grad_scale);
-    }
+    for (int j = tid; j < vocab; j += 256)
+      d[j] = f2bf(token_row::grad_elem(__expf(bf2f(x[j]) - m), inv, j == tgt ? 1.0f : 0.0f, grad_scale));
   }
 }
 

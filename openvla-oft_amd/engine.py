@@ -309,6 +309,25 @@ class DiffusionNoiseState:
         return self
 
 
+class TokenSampleState:
+    """The engine-level state of stochastic action-token decoding (ovla.h "Token sampling and the policy-gradient objective"): 64-bit seed and
+    the 32-bit `call` counter that advances once per draw (VLAEngine.sample_action_tokens, a sampled predict_action) and is checkpointed
+    with the optimizer state.  A draw is a pure function of (seed, call, row key, token id); nothing else is stored."""
+
+    def __init__(self, seed: int = 0):
+        self.seed, self.call = int(seed) & 0xFFFFFFFFFFFFFFFF, 0
+
+    def advance(self) -> int:
+        """-> the `call` of this draw; the next draw takes the next one."""
+        call = self.call
+        self.call = (self.call + 1) & 0xFFFFFFFF
+        return call
+
+    def words(self, call: Optional[int] = None) -> List[int]:
+        """(seed_lo, seed_hi, call): the three 32-bit words of ovla_sample_tokens' device-side state."""
+        return [self.seed & 0xFFFFFFFF, self.seed >> 32, (self.call if call is None else call) & 0xFFFFFFFF]
+
+
 class SlotProjectors:
     """Every registered policy's proprio projector on all B observations, then each observation's own row (ovla_select_by_slot): n small
     forwards instead of data-dependent grouping, which a captured graph could not hold.  Quacks like MlpProjector.fwd for patches_dev."""
@@ -1217,10 +1236,12 @@ class VLAEngine:
     (see weights.py for the state-dict naming)."""
 
     def __init__(self, cfg: VLAConfig, get, device, *, lora: bool = True, use_proprio: bool = True, head: str = "l1", use_film: bool = False,
-                 has=None, lora_dropout: float = 0.0, dropout_seed: int = 0, num_diffusion_steps: Optional[int] = None, diffusion_seed: int = 0):
+                 has=None, lora_dropout: float = 0.0, dropout_seed: int = 0, num_diffusion_steps: Optional[int] = None, diffusion_seed: int = 0,
+                 sample_seed: int = 0):
         if head not in ("l1", "diffusion", "none"):
             raise ValueError(head)
         self.dropout = DropoutState(lora_dropout, dropout_seed)
+        self.token_sample = TokenSampleState(sample_seed)   # stochastic action-token decoding (sample_action_tokens, a sampled predict_action)
         # device noise of the diffusion objective (draw_diffusion / sample_actions): only an engine told the head's T carries the state
         if num_diffusion_steps is not None and head != "diffusion":
             raise ValueError("num_diffusion_steps belongs to the diffusion head")
@@ -1806,6 +1827,8 @@ class VLAEngine:
         out["lora_dropout.call"] = torch.tensor([self.dropout.call], dtype=torch.int64)   # the mask stream's position: a resumed run draws the masks the uninterrupted one would
         if self.diffusion is not None:   # ... and the noise and timesteps the uninterrupted one would
             out["diffusion_noise.call"] = torch.tensor([self.diffusion.call], dtype=torch.int64)
+        if self.token_sample.call:   # ... and the action tokens (a stream that never drew is not written: a file without the entry loads as call = 0)
+            out["token_sample.call"] = torch.tensor([self.token_sample.call], dtype=torch.int64)
         if self.ema_enabled:   # the averaged weights and the position of their decay schedule
             out["ema.step"] = torch.tensor([self.ema_step], dtype=torch.int64)
             for i, st in enumerate(self.stores):
@@ -1833,6 +1856,7 @@ class VLAEngine:
             self.dropout.call = int(sd["lora_dropout.call"].item()) & 0xFFFFFFFF
         if "diffusion_noise.call" in sd and self.diffusion is not None:
             self.diffusion.call = int(sd["diffusion_noise.call"].item()) & 0xFFFFFFFF
+        self.token_sample.call = int(sd["token_sample.call"].item()) & 0xFFFFFFFF if "token_sample.call" in sd else 0   # (a file from before the stream existed)
         for i, st in enumerate(self.stores):
             if not st.exp_avg:
                 st.init_optimizer()
@@ -2313,6 +2337,99 @@ class VLAEngine:
             self.backward_from_rows(self.lm_loss_bwd(dlogits), rows_idx, out)
         return loss_rows.sum().reshape(1), n_tok, pred
 
+    # -- stochastic decoding and the policy-gradient objective on the action tokens (ovla.h "Token sampling and the policy-gradient objective") --
+    def token_window(self, window) -> Tuple[int, int]:
+        """"actions": the n_action_bins ids the action tokenizer writes, [n_tokens - n_action_bins, n_tokens); "vocab": every lm_head row; or (lo, hi)."""
+        n_tokens = self.cfg.vocab - self.cfg.pad_to_multiple_of
+        if window == "actions":
+            return n_tokens - self.cfg.n_action_bins, n_tokens
+        if window == "vocab":
+            return 0, self.cfg.vocab
+        if isinstance(window, (tuple, list)) and len(window) == 2:
+            return int(window[0]), int(window[1])
+        raise ValueError(f'window = {window!r} ("actions", "vocab" or (lo, hi))')
+
+    def _action_logits(self, batch: dict, train: bool, who: str):
+        """The forward on the action rows and lm_head on them -> (out, rows_idx, bf16 logits [B * A padded to 8, vocab], B * A).  The action slots'
+        inputs are zeroed by ovla_assemble_multimodal: the logits do not depend on which tokens the labels hold there."""
+        if self.lm_head is None:
+            raise RuntimeError(f"{who} needs language_model.lm_head.weight in the checkpoint")
+        out = self.forward(batch["input_ids"], batch["attention_mask"], batch["pixel_values"], batch["labels"], proprio=batch.get("proprio"),
+                           train=train, sel="actions")
+        ah, idx = self.action_hidden(out)
+        return out, idx, self.lm_head_rows(ah), ah.shape[0]
+
+    def _rows_dev(self, t, dtype, B: int, what: str):
+        """A per-token [B, A] or (with `per_obs`) per-observation [B] host or device tensor -> contiguous [B * A] on the device."""
+        A = self.cfg.num_action_tokens
+        t = torch.as_tensor(t).to(self.device, dtype)
+        if t.numel() == B and t.dim() <= 1 and what == "advantages":
+            t = t.reshape(B, 1).expand(B, A)
+        if t.numel() != B * A:
+            raise ValueError(f"{what}: {tuple(t.shape)} for {B} observations of {A} action tokens")
+        return t.reshape(B * A).contiguous()
+
+    def sample_action_tokens(self, batch: dict, temperature: float = 1.0, window="actions", row_keys=None):
+        """Draws the chunk's action tokens from softmax(logits[window] / temperature): one forward (inference mode) on the action rows, lm_head
+        on them, ONE ovla_sample_tokens launch; nothing is read back.  `row_keys` int32 [B, A] (or [B]: key * A + a per token) replaces the
+        row index in the generator's counter, so k draws of one observation in a batch differ and a draw does not depend on its position.
+        Advances the token stream's `call` by one.  -> dict(tokens, bins int32, logprob, entropy fp32), each [B, A] on the device."""
+        cfg, B = self.cfg, batch["input_ids"].shape[0]
+        A = cfg.num_action_tokens
+        lo, hi = self.token_window(window)
+        keys = None
+        if row_keys is not None:
+            keys = torch.as_tensor(row_keys).to(self.device, torch.int32)
+            if keys.numel() == B:
+                keys = keys.reshape(B, 1) * A + torch.arange(A, dtype=torch.int32, device=self.device)[None, :]
+            if keys.numel() != B * A:
+                raise ValueError(f"row_keys: {tuple(keys.shape)} for {B} observations of {A} action tokens")
+            keys = keys.reshape(B * A).contiguous()
+        with torch.no_grad():
+            _, _, logits, n = self._action_logits(batch, False, "sample_action_tokens")
+            st = self.token_sample
+            tok, bins, lp, ent = ops.sample_tokens(logits[:n], n_tokens=cfg.vocab - cfg.pad_to_multiple_of, n_bins=cfg.n_action_bins - 1, window=(lo, hi),
+                                                   temperature=temperature, seed=st.seed, call=st.advance(), row_key=keys)
+        return dict(tokens=tok.view(B, A), bins=bins.view(B, A), logprob=lp.view(B, A), entropy=ent.view(B, A))
+
+    def policy_logprobs(self, batch: dict, tokens, temperature: float = 1.0, window="actions"):
+        """Log-probability and entropy of given action tokens [B, A] under the current weights: the forward of sample_action_tokens, then
+        ovla_token_pg without a gradient -- for the tokens a draw returned, the bits that draw reported.  -> dict(logprob, entropy) [B, A]."""
+        B, A = batch["input_ids"].shape[0], self.cfg.num_action_tokens
+        tok = self._rows_dev(tokens, torch.int32, B, "tokens")
+        with torch.no_grad():
+            _, _, logits, n = self._action_logits(batch, False, "policy_logprobs")
+            lp, ent, _, _, _ = ops.token_pg(logits[:n], tok, torch.ones(n, dtype=F32, device=self.device), window=self.token_window(window), temperature=temperature)
+        return dict(logprob=lp.view(B, A), entropy=ent.view(B, A))
+
+    def train_step_policy_gradient(self, batch: dict, tokens, advantages, old_logprobs=None, clip=(0.8, 1.2), temperature: float = 1.0, window="actions",
+                                   loss_scale: float = 1.0):
+        """One policy-gradient micro-step on drawn action tokens: the PPO / GRPO clipped surrogate
+            loss = -(1 / (B A)) sum_{b, a} min(ratio A_b, clip(ratio, clip[0], clip[1]) A_b),   ratio = exp(logprob - old_logprob)  (1 without old_logprobs)
+        and its backward through lm_head and the decoder, into the flat gradient buffers.  `tokens` int32 [B, A], `advantages` [B] or [B, A],
+        `old_logprobs` [B, A] (what sample_action_tokens / policy_logprobs returned when the tokens were drawn), host or device tensors.
+        The forward does not depend on `tokens` (the action slots' inputs are zero): they only select the targets.
+        -> dict of device scalars: loss, logprob (mean), entropy (mean), clip_frac, ratio (mean)."""
+        self._not_in_ema_scope("train_step_policy_gradient")
+        self._refuse_per_policy_film_training(True)
+        B = batch["input_ids"].shape[0]
+        tok = self._rows_dev(tokens, torch.int32, B, "tokens")
+        adv = self._rows_dev(advantages, F32, B, "advantages")
+        old = None if old_logprobs is None else self._rows_dev(old_logprobs, F32, B, "old_logprobs")
+        lo, hi = self.token_window(window)
+        out, idx, logits, n = self._action_logits(batch, True, "train_step_policy_gradient")
+        lp, ent, ratio, clipped, _ = ops.token_pg(logits[:n], tok, adv, window=(lo, hi), temperature=temperature, old_logprob=old, clip=clip,
+                                                  grad_scale=loss_scale / n, inplace_grad=True)
+        logits[n:].zero_()
+        dah = self.lm_loss_bwd(logits)
+        if getattr(self, "_overlap", False) and self.head is not None and hasattr(self.head, "store"):   # (no head trains here: its gradients are final)
+            for dt, g in self.head.store.flat_grad.items():
+                self.reducer.notify(self.head.store, dt, g.numel())
+        self.backward_from_rows(dah, idx, out)
+        # the surrogate's value from the row outputs (device arithmetic, nothing read back): min(r A, clip(r) A)
+        surr = torch.minimum(ratio * adv, ratio.clamp(float(clip[0]), float(clip[1])) * adv)
+        return dict(loss=-surr.mean(), logprob=lp.mean(), entropy=ent.mean(), clip_frac=clipped.to(F32).mean(), ratio=ratio.mean())
+
     # -- the next-token cross entropy on the counted rows: train_step_discrete above and modeling._LMLossFn (`output.loss`) ------------------
     def counted_rows(self, labels, S: int, P: int):
         """Host int64 labels [B, L] -> (bb, jj, rows_idx int32 [n_tok] device, targets int64 [n_tok] device).  Text position j + 1 with
@@ -2425,7 +2542,7 @@ class ChunkGraph(_StaticInputs):
 
     def __init__(self, engine: "VLAEngine", B: int, L: int, pixel_shape, *, head=None, use_proprio: bool = True, proprio_projector=None,
                  invariant: bool = False, film: bool = False, discrete: bool = False, n_tokens: Optional[int] = None, n_bins: Optional[int] = None,
-                 policies=None):
+                 policies=None, sample=None):
         dev = engine.device
         self.policies = policies
         self.obs_slot = None
@@ -2448,6 +2565,14 @@ class ChunkGraph(_StaticInputs):
         self.discrete = discrete
         self.n_tokens = n_tokens if n_tokens is not None else engine.cfg.vocab - engine.cfg.pad_to_multiple_of   # modeling_prismatic.py:732
         self.n_bins = n_bins if n_bins is not None else engine.cfg.n_action_bins - 1                              # bin_centers.shape[0]
+        # `sample` = (temperature, (lo, hi)): ovla_sample_tokens in place of ovla_argmax_bins.  The generator's (seed_lo, seed_hi, call) and the
+        # row keys are static device buffers that load() writes, so every replay draws what the eager call with the same values draws.
+        if sample is not None and not discrete:
+            raise ValueError("ChunkGraph(sample=...) goes with discrete=True")
+        self.sample = None if sample is None else (float(sample[0]), (int(sample[1][0]), int(sample[1][1])))
+        if self.sample is not None:
+            self.sample_state = torch.zeros(3, dtype=torch.int32, device=dev)
+            self.row_key = torch.arange(B * engine.cfg.num_action_tokens, dtype=torch.int32, device=dev)
         self.proprio_projector = proprio_projector
         self.graph = None
         self.out = None
@@ -2469,12 +2594,24 @@ class ChunkGraph(_StaticInputs):
             if self.policies is not None and self.slot_heads is not None:
                 pred = eng.policy_heads_fwd(ah, self.slot_heads)
             if self.discrete:   # modeling.logits_for's GEMM, then the decode on the bf16 logits
+                if self.sample is not None:
+                    tok, bins, lp, ent = ops.sample_tokens(eng.lm_head_rows(ah)[: ah.shape[0]], n_tokens=self.n_tokens, n_bins=self.n_bins, window=self.sample[1],
+                                                           temperature=self.sample[0], state_dev=self.sample_state, row_key=self.row_key)
+                    return pred, ah, tok, bins, lp, ent
                 tok, bins = ops.argmax_bins(eng.lm_head_rows(ah)[: ah.shape[0]], n_tokens=self.n_tokens, n_bins=self.n_bins)
                 return pred, ah, tok, bins
         return pred, ah
 
-    def load(self, input_ids, attention_mask, pixel_values, labels, proprio=None, slots=None):
+    def load(self, input_ids, attention_mask, pixel_values, labels, proprio=None, slots=None, sample_state=None, row_key=None):
         super().load(input_ids, attention_mask, pixel_values, labels, proprio)
+        if (sample_state is None) != (self.sample is None):
+            raise ValueError("ChunkGraph.load: `sample_state` goes with a graph built with sample=")
+        if sample_state is not None:   # (seed_lo, seed_hi, call) as 32-bit words; row_key int32 [B * A], default the row indices
+            words = torch.tensor([int(v) & 0xFFFFFFFF for v in sample_state], dtype=torch.int64)
+            self.sample_state.copy_(torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32), non_blocking=True)
+            if row_key is None:
+                row_key = torch.arange(self.row_key.numel(), dtype=torch.int32)
+            self.row_key.copy_(torch.as_tensor(row_key).to(torch.int32).reshape(-1), non_blocking=True)
         if (slots is None) != (self.obs_slot is None):
             raise ValueError("ChunkGraph.load: `slots` goes with a graph built with policies=")
         if slots is not None:   # the host sees the values here: an out-of-range slot never reaches a kernel
@@ -2496,8 +2633,8 @@ class ChunkGraph(_StaticInputs):
         self.graph.replay()
         return self.out
 
-    def __call__(self, input_ids, attention_mask, pixel_values, labels, proprio=None, slots=None):
-        self.load(input_ids, attention_mask, pixel_values, labels, proprio, slots)
+    def __call__(self, input_ids, attention_mask, pixel_values, labels, proprio=None, slots=None, sample_state=None, row_key=None):
+        self.load(input_ids, attention_mask, pixel_values, labels, proprio, slots, sample_state, row_key)
         if self.graph is None:
             self.capture()
         return self.replay()

@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import contextlib
 import math
-from typing import Any, Dict, List, Optional, Tuple
+from typing import NamedTuple, Any, Dict, List, Optional, Tuple
 
 import os
 
@@ -308,6 +308,15 @@ class PrismaticCausalLMOutputWithPast:
 
     def __getitem__(self, key):   # ModelOutput-style access: out["loss"], out["hidden_states"]
         return getattr(self, key)
+
+
+class SampledTokens(NamedTuple):
+    """What a sampled decode drew (predict_action / predict_action_batch with do_sample=True, return_tokens=True): device tensors [B, A] --
+    the action-token ids (int32), their log-probabilities under softmax(logits[action window] / temperature) and the entropy of that
+    distribution per action row (fp32).  `logprobs` is the `old_logprobs` of VLAEngine.train_step_policy_gradient."""
+    tokens: torch.Tensor
+    logprobs: torch.Tensor
+    entropy: torch.Tensor
 
 
 class ActionAttention:
@@ -670,7 +679,7 @@ class OpenVLAForActionPrediction(_StoreModule):
         temb = torch.cat([action_head.time_encoder(torch.tensor([float(t)])).to(BF16).reshape(1, -1) for t in sched.timesteps])
         return sched.step_coefficients(), temb
 
-    def _graph_key(self, batch, B, L, pixel_shape, *, use_proprio, head_comp, pp_comp, film, discrete, ddim, n_policies):
+    def _graph_key(self, batch, B, L, pixel_shape, *, use_proprio, head_comp, pp_comp, film, discrete, ddim, n_policies, sample=None):
         """The key of a captured graph in self._graphs.  predict_action: one graph per (text length, head, projector), led by "ddim" for the
         sampler.  The batch API: ("batch", B, text bucket, ...), what _evict_batch_graph counts.  `ddim`: (id of the noisy-action projector,
         sampling steps, training steps)."""
@@ -680,6 +689,8 @@ class OpenVLAForActionPrediction(_StoreModule):
         if not batch:
             return ("ddim", L, shape, id(head_comp), id(pp_comp)) + ddim if ddim else (L, shape, id(head_comp), id(pp_comp))
         key = ("batch", B, L, shape, id(head_comp), id(pp_comp), ops.BATCH_INVARIANT_DEFAULT, film)
+        if sample is not None:   # the sampled decode is captured: temperature and window are part of the graph
+            return key + (discrete, "sample") + sample
         return key + ("ddim",) + ddim if ddim else key + (discrete,)
 
     def _graph_for(self, key, build):
@@ -698,13 +709,43 @@ class OpenVLAForActionPrediction(_StoreModule):
         if len(batched) >= self.max_batch_graphs:   # B and the bucket come from callers (/act_batch): keep the most recent few
             del self._graphs[batched[0]]
 
-    def _decode(self, pred, bins, hidden):
+    def _sample_spec(self, do_sample, temperature, sample_seed, sample_keys, B, discrete: bool, return_tokens: bool):
+        """The `sample` argument of _infer for a do_sample=True call (None otherwise): temperature, the action-token window, the generator's
+        three words (the engine's token stream, advanced by one; `sample_seed` replaces its seed for this draw), and the int32 key of every
+        action row -- observation key k_b (sample_keys[b], default b) gives k_b * A + a."""
+        if not do_sample:
+            if return_tokens:
+                raise ValueError("return_tokens=True goes with do_sample=True (the greedy decode reports no log-probabilities)")
+            return None
+        if not discrete:
+            raise ValueError("do_sample=True draws action TOKENS: it is the discrete path's (no action head, no per-policy heads); L1 and diffusion "
+                             "heads are deterministic regressors / have their own noise")
+        st, A = self.engine.token_sample, self.cfg.num_action_tokens
+        keys = torch.arange(B, dtype=torch.int64) if sample_keys is None else torch.as_tensor(np.asarray(sample_keys)).to(torch.int64).reshape(-1)
+        if keys.numel() != B:
+            raise ValueError(f"sample_keys: {keys.numel()} keys for {B} observations")
+        rows = (keys[:, None] * A + torch.arange(A, dtype=torch.int64)[None, :]).reshape(-1) & 0xFFFFFFFF
+        rows = torch.where(rows >= 2 ** 31, rows - 2 ** 32, rows).to(torch.int32)
+        words = st.words(st.advance())
+        if sample_seed is not None:
+            words[0], words[1] = int(sample_seed) & 0xFFFFFFFF, (int(sample_seed) >> 32) & 0xFFFFFFFF
+        return dict(temperature=float(temperature), window=self.engine.token_window("actions"), words=words, keys=rows, out={})
+
+    def _decode(self, pred, bins, hidden, sample=None):
         """Normalised actions [B, chunk, action_dim] from whichever the forward produced: the head's prediction (:923-927); the bin indices, when
         the lm_head GEMM + ovla_argmax_bins ran inside a graph; otherwise the greedy token decode of the action hidden states (:929-942)."""
         cfg = self.cfg
         if pred is not None:
             normalized = pred.float().cpu().numpy()
         else:
+            if bins is None and sample is not None:   # the draw of ChunkGraph(sample=...), as eager launches
+                n = hidden.shape[0] * hidden.shape[1]
+                w = sample["words"]
+                tok, b, lp, ent = ops.sample_tokens(self.engine.lm_head_rows(hidden.view(-1, cfg.llm_dim))[:n], n_tokens=self.vocab_size,
+                                                    n_bins=self.bin_centers.shape[0], window=sample["window"], temperature=sample["temperature"],
+                                                    seed=w[0] | (w[1] << 32), call=w[2], row_key=sample["keys"].to(self.device))
+                sample["out"].update(tokens=tok, logprobs=lp, entropy=ent)
+                bins = b.cpu().numpy().astype(np.int64)
             if bins is None:
                 tok = self.logits_for(hidden.view(-1, cfg.llm_dim)).argmax(dim=1).cpu().numpy()
                 bins = np.clip(self.vocab_size - tok - 1, a_min=0, a_max=self.bin_centers.shape[0] - 1)
@@ -712,7 +753,7 @@ class OpenVLAForActionPrediction(_StoreModule):
         return normalized.reshape(hidden.shape[0], cfg.chunk, cfg.action_dim)
 
     def _infer(self, ids, mask, labels, pixel_values, prop, *, batch: bool, action_head=None, proprio_projector=None, noisy_action_projector=None,
-               noise=None, policy=None, attention: Optional[dict] = None):
+               noise=None, policy=None, attention: Optional[dict] = None, sample: Optional[dict] = None):
         """The forward on prepared ids / mask / labels [B, L], the action rows, the head (L1, or the DDIM sampler from `noise`) or the token
         decode -> (normalised actions ndarray [B, chunk, action_dim], action hidden states [B, A, D] in a tensor of their own).
         `batch` is the mode.  False (predict_action): the planner's GEMM schedules, FiLM's average over all L positions, a graph per key.
@@ -720,7 +761,9 @@ class OpenVLAForActionPrediction(_StoreModule):
         tokens, "batch" graph keys under the LRU rule, and the token decode inside the graph.
         `policy`: (adapter slot per observation, the policies' head components or None, their proprio projector components or None).
         `attention` (a dict to fill; output_attentions=True): the eager forward (routed with `policy`) with an AttnCapture of the action rows;
-        self._graphs is neither used nor touched.  It receives the capture's `mean` [n_layers, B*A, S] and the sequence's P and S."""
+        self._graphs is neither used nor touched.  It receives the capture's `mean` [n_layers, B*A, S] and the sequence's P and S.
+        `sample` (what _sample_spec returns; do_sample=True): the token decode draws instead of taking the maximum -- inside the batched
+        discrete graph, otherwise as the same launch after the forward -- and sample["out"] receives tokens / logprobs / entropy [B*A]."""
         cfg, eng = self.cfg, self.engine
         (B, L), A, D = ids.shape, cfg.num_action_tokens, cfg.llm_dim
         slots, heads, pps = policy if policy is not None else (None, None, None)
@@ -748,6 +791,8 @@ class OpenVLAForActionPrediction(_StoreModule):
                     noise = torch.randn((B, cfg.chunk, cfg.action_dim))
                 cur = torch.as_tensor(noise).to("cpu", torch.float32).reshape(B, cfg.chunk, cfg.action_dim).to(BF16).float()
                 ddim = (id(nap_comp), len(sched.timesteps), sched.config.num_train_timesteps)
+            # the batched discrete graph holds its decode: a sampled one is a graph of its own, keyed by temperature and window
+            graph_sample = (sample["temperature"], sample["window"]) if sample is not None and batch and discrete and policy is None else None
             if use_graph:
                 def build():
                     invariant = ops.BATCH_INVARIANT_DEFAULT if batch else False
@@ -761,11 +806,12 @@ class OpenVLAForActionPrediction(_StoreModule):
                         per_slot = [(None if heads is None else heads[s], None if pps is None else pps[s]) for s in range(eng.n_slots)]
                         keep = (heads, pps)
                     g = ChunkGraph(eng, B, L, pixel_values.shape, head=head_comp, use_proprio=use_proprio, proprio_projector=pp_comp, invariant=invariant,
-                                   film=film, discrete=batch and discrete, n_tokens=self.vocab_size, n_bins=self.bin_centers.shape[0], policies=per_slot)
+                                   film=film, discrete=batch and discrete, n_tokens=self.vocab_size, n_bins=self.bin_centers.shape[0], policies=per_slot,
+                                   sample=graph_sample)
                     return g, keep
 
                 key = self._graph_key(batch, B, L, pixel_values.shape, use_proprio=use_proprio, head_comp=head_comp, pp_comp=pp_comp, film=film,
-                                      discrete=discrete, ddim=ddim, n_policies=eng.n_slots if policy is not None else 0)
+                                      discrete=discrete, ddim=ddim, n_policies=eng.n_slots if policy is not None else 0, sample=graph_sample)
                 g = self._graph_for(key, build)
                 if use_diffusion:
                     # the whole loop from two captured graphs, no host work between the steps (engine.DiffusionGraph): same bits as the loop below
@@ -773,9 +819,13 @@ class OpenVLAForActionPrediction(_StoreModule):
                     cur = sample.reshape(B, cfg.chunk, cfg.action_dim)
                 else:
                     # one hipGraph per key: ~1.3 k launches -> one graph launch (engine.ChunkGraph)
-                    res = g(ids, mask, pixel_values, labels, prop, slots=slots)
+                    if graph_sample is not None:
+                        res = g(ids, mask, pixel_values, labels, prop, slots=slots, sample_state=sample["words"], row_key=sample["keys"])
+                        sample["out"].update(tokens=res[2].clone(), logprobs=res[4].clone(), entropy=res[5].clone())   # out of the static buffers
+                    else:
+                        res = g(ids, mask, pixel_values, labels, prop, slots=slots)
                     pred, ah = res[0], res[1]
-                    if len(res) > 2:        # lm_head GEMM + ovla_argmax_bins ran inside the graph: only the bin indices come back
+                    if len(res) > 2:        # lm_head GEMM + the token decode ran inside the graph: only the bin indices come back
                         bins = res[3].cpu().numpy().astype(np.int64)
                 hidden = ah.view(B, A, D).clone()   # out of the graph's static buffer
             elif use_diffusion:
@@ -806,7 +856,7 @@ class OpenVLAForActionPrediction(_StoreModule):
                         pred = eng.policy_heads_fwd(ah, heads)
                     elif action_head is not None:
                         pred = action_head.predict_action(hidden)
-            normalized = cur.numpy() if use_diffusion else self._decode(pred, bins, hidden)
+            normalized = cur.numpy() if use_diffusion else self._decode(pred, bins, hidden, sample)
         return normalized, hidden
 
     def _infer_pooled(self, ids, mask, labels, pixel_values, prop, policy, use_proprio, attention: Optional[dict] = None):
@@ -848,7 +898,12 @@ class OpenVLAForActionPrediction(_StoreModule):
     # -- predict_action (:946-1060) -------------------------------------------------------------------------------------
     @torch.no_grad()
     def predict_action(self, input_ids=None, unnorm_key=None, proprio=None, proprio_projector=None, action_head=None,
-                       noisy_action_projector=None, use_film: bool = False, output_attentions: bool = False, **kwargs):
+                       noisy_action_projector=None, use_film: bool = False, output_attentions: bool = False, do_sample: bool = False,
+                       temperature: float = 1.0, sample_seed: Optional[int] = None, sample_keys=None, return_tokens: bool = False, **kwargs):
+        """`do_sample=True` (the discrete token path only; ValueError with a head): the action tokens are DRAWN from softmax(logits[action ids] /
+        temperature) on the device (ovla_sample_tokens) and the actions come from the drawn bins; `return_tokens=True` appends a SampledTokens.
+        Every sampled call advances the engine's token stream by one; `sample_seed` replaces its seed for this call; `sample_keys` names the
+        observation's key in the generator (default 0).  With do_sample=False every launch is the one issued before."""
         cfg = self.cfg
         if use_film != self.engine.use_film:
             raise ValueError(f"use_film={use_film} but the model was built with use_film={self.engine.use_film}")
@@ -868,11 +923,19 @@ class OpenVLAForActionPrediction(_StoreModule):
         use_proprio = proprio_projector is not None and proprio is not None
         prop = torch.as_tensor(np.asarray(proprio), dtype=torch.float32) if use_proprio else None
         attention = {} if output_attentions else None   # -> a third result, an ActionAttention (the eager forward; no graph is used or built)
+        sample = self._sample_spec(do_sample, temperature, sample_seed, sample_keys, 1, action_head is None, return_tokens)
         normalized, hidden = self._infer(ids, mask, labels, pixel_values, prop, batch=False, action_head=action_head, proprio_projector=proprio_projector,
-                                         noisy_action_projector=noisy_action_projector, noise=kwargs.get("noise"), attention=attention)
+                                         noisy_action_projector=noisy_action_projector, noise=kwargs.get("noise"), attention=attention, sample=sample)
+        res = (self._unnormalize_actions(normalized[0], unnorm_key), hidden)
         if attention is not None:
-            return self._unnormalize_actions(normalized[0], unnorm_key), hidden, self._action_attention(attention, mask, pixel_values, use_proprio)
-        return self._unnormalize_actions(normalized[0], unnorm_key), hidden
+            res += (self._action_attention(attention, mask, pixel_values, use_proprio),)
+        return res + self._sampled_tokens(sample, 1, return_tokens)
+
+    def _sampled_tokens(self, sample, B: int, return_tokens: bool) -> tuple:
+        if not return_tokens:
+            return ()
+        o, A = sample["out"], self.cfg.num_action_tokens
+        return (SampledTokens(o["tokens"].view(B, A), o["logprobs"].view(B, A), o["entropy"].view(B, A)),)
 
     def _action_attention(self, attention: dict, mask, pixel_values, use_proprio: bool) -> ActionAttention:
         """The ActionAttention of an _infer(attention=...) call on text rows `mask` [B, L] (right-padded)."""
@@ -887,7 +950,8 @@ class OpenVLAForActionPrediction(_StoreModule):
     @torch.no_grad()
     def predict_action_batch(self, prompts, pixel_values, unnorm_key=None, proprio=None, proprio_projector=None, action_head=None,
                              noisy_action_projector=None, use_film: bool = False, noise=None, pad_to: Optional[int] = None, policy=None,
-                             output_attentions: bool = False):
+                             output_attentions: bool = False, do_sample: bool = False, temperature: float = 1.0, sample_seed: Optional[int] = None,
+                             sample_keys=None, return_tokens: bool = False):
         """predict_action for B observations in one forward.  prompts: list of B (input_ids, attention_mask) pairs ([1, L_b] or [L_b], lengths may
         differ; masks right-padded), pixel_values [B, 6 I, H, W], proprio [B, proprio_dim], noise [B, chunk, action_dim] (diffusion: each sample's
         DDIM trajectory starts from its own noise).  Returns (actions [B, chunk, action_dim] unnormalised with `unnorm_key`, action hidden states
@@ -904,8 +968,15 @@ class OpenVLAForActionPrediction(_StoreModule):
         its own FiLM Linears and diffusion heads are not supported with `policy`.
         `output_attentions=True` returns a third element, an ActionAttention: the head-averaged attention of every observation's action rows, from the
         eager forward (routed with `policy`; no graph is used or built).  An observation's maps are the same bits alone and in any batch, up to its own
-        key length; its padding keys are 0.  Not with a diffusion head (ValueError)."""
+        key length; its padding keys are 0.  Not with a diffusion head (ValueError).
+        `do_sample=True` (the discrete token path without `policy`; ValueError otherwise): every observation's action tokens are drawn from
+        softmax(logits[action ids] / temperature) on the device, inside the captured graph under graph replay (ovla_sample_tokens in place of
+        ovla_argmax_bins; each replay draws under the `call` its load() wrote).  `sample_keys` [B]: each observation's key in the generator (default
+        its index) -- an observation draws the same tokens alone and in any batch under the same key and call.  `return_tokens=True` appends a
+        SampledTokens.  Every sampled call advances the engine's token stream by one; `sample_seed` replaces its seed for this call."""
         cfg = self.cfg
+        if do_sample and policy is not None:
+            raise ValueError("predict_action_batch(do_sample=True) is not supported with per-request policies")
         per_policy_film = bool(getattr(self.engine, "film_per_policy", False))
         if use_film != self.engine.use_film:
             raise ValueError(f"use_film={use_film} but the model was built with use_film={self.engine.use_film}")
@@ -947,11 +1018,14 @@ class OpenVLAForActionPrediction(_StoreModule):
                                             proprio=None if prop_p is None else prop_p.cpu().numpy(), proprio_projector=proprio_projector,
                                             action_head=action_head, noisy_action_projector=noisy_action_projector, use_film=use_film,
                                             noise=rep(noise), policy=None if policy is None else policy + [policy[0]] * len(fill),
-                                            output_attentions=output_attentions)
+                                            output_attentions=output_attentions, do_sample=do_sample, temperature=temperature, sample_seed=sample_seed,
+                                            sample_keys=None if sample_keys is None else list(sample_keys) + [list(sample_keys)[0]] * len(fill),
+                                            return_tokens=return_tokens)
+            tail = (SampledTokens(*(t[:B] for t in res[-1])),) if return_tokens else ()
             if output_attentions:
                 att = res[2]
-                return res[0][:B], res[1][:B], ActionAttention(att.mean[:, :B], att.layout[:B], att.patches_per_image)
-            return res[0][:B], res[1][:B]
+                return (res[0][:B], res[1][:B], ActionAttention(att.mean[:, :B], att.layout[:B], att.patches_per_image)) + tail
+            return (res[0][:B], res[1][:B]) + tail
         use_proprio = proprio_projector is not None and proprio is not None
         if policy is not None:
             use_proprio = proprio is not None and next(iter(self._policies.values()))["pp"] is not None
@@ -985,6 +1059,7 @@ class OpenVLAForActionPrediction(_StoreModule):
             labels[b, len(r) - 1] = STOP_INDEX
         attention = {} if output_attentions else None
         extra = (lambda: (self._action_attention(attention, mask, pixel_values, use_proprio),)) if output_attentions else (lambda: ())
+        sample = self._sample_spec(do_sample, temperature, sample_seed, sample_keys, B, action_head is None and policy is None, return_tokens)
         if policy is not None and self._pool_resident:
             normalized, hidden = self._infer_pooled(ids, mask, labels, pixel_values, prop, policy, use_proprio, attention=attention)
             stats = [self.policy_norm_stats(p) for p in policy]
@@ -999,8 +1074,8 @@ class OpenVLAForActionPrediction(_StoreModule):
             stats = [self.policy_norm_stats(p) for p in policy]
             return (np.stack([self._unnormalize_actions(normalized[b], unnorm_key, stats[b]) for b in range(B)]), hidden) + extra()
         normalized, hidden = self._infer(ids, mask, labels, pixel_values, prop, batch=True, action_head=action_head, proprio_projector=proprio_projector,
-                                         noisy_action_projector=noisy_action_projector, noise=noise, attention=attention)
-        return (np.stack([self._unnormalize_actions(normalized[b], unnorm_key) for b in range(B)]), hidden) + extra()
+                                         noisy_action_projector=noisy_action_projector, noise=noise, attention=attention, sample=sample)
+        return (np.stack([self._unnormalize_actions(normalized[b], unnorm_key) for b in range(B)]), hidden) + extra() + self._sampled_tokens(sample, B, return_tokens)
 
     # -- statistics (:772-791, :1062-1087) -------------------------------------------------------------------------------
     @staticmethod

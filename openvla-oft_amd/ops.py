@@ -1001,6 +1001,78 @@ def argmax_bins(logits, *, n_tokens, n_bins, vocab=None, token=None, bins=None):
     return token, bins
 
 
+def _token_window(window, vocab):
+    lo, hi = (0, vocab) if window is None else (int(window[0]), int(window[1]))
+    return lo, hi
+
+
+def sample_tokens(logits, *, n_tokens, n_bins, vocab=None, window=None, temperature=1.0, seed=0, call=0, state_dev=None, row_key=None,
+                  entropy=True, token=None, bins=None, logprob=None, entropy_out=None):
+    """Stochastic action-token decode (ovla.h "Token sampling and the policy-gradient objective": ovla_sample_tokens): logits bf16 [rows, ld >= vocab]
+    -> (token int32, bin int32, logprob fp32, entropy fp32 or None), each [rows]: one Gumbel-max draw per row from softmax(logits[lo:hi] / T), a pure
+    function of (seed, call, row key, token id).  `window` = (lo, hi), default the whole vocabulary.  `state_dev` (uint32 [3] on the device: seed_lo,
+    seed_hi, call) overrides seed / call when the kernel runs; `row_key` int32 [rows] replaces the row index in the generator's counter."""
+    _chk(logits, name="logits")
+    assert logits.dim() == 2 and logits.stride(1) == 1
+    rows, dev = logits.shape[0], logits.device
+    vocab = logits.shape[1] if vocab is None else vocab
+    lo, hi = _token_window(window, vocab)
+    token = torch.empty(rows, dtype=torch.int32, device=dev) if token is None else token
+    bins = torch.empty(rows, dtype=torch.int32, device=dev) if bins is None else bins
+    logprob = torch.empty(rows, dtype=torch.float32, device=dev) if logprob is None else logprob
+    if entropy_out is None and entropy:
+        entropy_out = torch.empty(rows, dtype=torch.float32, device=dev)
+    for t, dt, name in ((token, torch.int32, "token"), (bins, torch.int32, "bins"), (logprob, torch.float32, "logprob"), (entropy_out, torch.float32, "entropy"),
+                        (row_key, torch.int32, "row_key")):
+        if t is not None:
+            _chk(t, dt, name)
+            assert t.numel() == rows and t.is_contiguous(), f"{name}: expected {rows} contiguous elements"
+    if state_dev is not None:
+        assert state_dev.is_cuda and state_dev.numel() == 3 and state_dev.is_contiguous() and state_dev.element_size() == 4 and not state_dev.is_floating_point(), \
+            "state_dev: three 32-bit integers on the device (seed_lo, seed_hi, call)"
+    g = STRUCTS["ovla_sample_tokens_args"]()
+    g.logits, g.ld, g.token, g.bin, g.logprob, g.entropy = logits.data_ptr(), logits.stride(0), token.data_ptr(), bins.data_ptr(), logprob.data_ptr(), _p(entropy_out)
+    g.state_dev, g.row_key = _p(state_dev), _p(row_key)
+    g.seed_lo, g.seed_hi, g.call = int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF, int(call) & 0xFFFFFFFF
+    g.temperature = float(temperature)
+    g.rows, g.vocab, g.lo, g.hi, g.n_tokens, g.n_bins = rows, vocab, lo, hi, n_tokens, n_bins
+    _lib.call("ovla_sample_tokens", g, _stream())
+    return token, bins, logprob, entropy_out
+
+
+def token_pg(logits, tokens, advantage, *, vocab=None, window=None, temperature=1.0, old_logprob=None, clip=(0.8, 1.2), grad_scale=None, inplace_grad=True,
+             dlogits=None, logprob=None, entropy=None, ratio=None, clipped=None):
+    """Clipped policy-gradient objective on given tokens (ovla.h: ovla_token_pg): logits bf16 [rows, ld >= vocab], tokens int32 [rows], advantage fp32
+    [rows] (and old_logprob fp32 [rows]) on the device -> (logprob, entropy, ratio fp32 [rows], clipped int32 [rows], dlogits bf16 or None).  With
+    grad_scale the gradient overwrites `logits` (inplace_grad), goes to `dlogits` when one is given, or to a new tensor, as in token_ce."""
+    _chk(logits, name="logits")
+    assert logits.dim() == 2 and logits.stride(1) == 1
+    rows, dev = logits.shape[0], logits.device
+    vocab = logits.shape[1] if vocab is None else vocab
+    lo, hi = _token_window(window, vocab)
+    logprob = torch.empty(rows, dtype=torch.float32, device=dev) if logprob is None else logprob
+    entropy = torch.empty(rows, dtype=torch.float32, device=dev) if entropy is None else entropy
+    ratio = torch.empty(rows, dtype=torch.float32, device=dev) if ratio is None else ratio
+    clipped = torch.empty(rows, dtype=torch.int32, device=dev) if clipped is None else clipped
+    for t, dt, name in ((tokens, torch.int32, "tokens"), (advantage, torch.float32, "advantage"), (old_logprob, torch.float32, "old_logprob"),
+                        (logprob, torch.float32, "logprob"), (entropy, torch.float32, "entropy"), (ratio, torch.float32, "ratio"), (clipped, torch.int32, "clipped")):
+        if t is not None:
+            _chk(t, dt, name)
+            assert t.numel() == rows and t.is_contiguous(), f"{name}: expected {rows} contiguous elements"
+    d = None
+    if grad_scale is not None:
+        d = dlogits if dlogits is not None else (logits if inplace_grad else torch.empty_like(logits))
+        assert d.dtype == BF16 and d.shape[0] == rows and d.shape[1] >= vocab and d.stride(1) == 1
+    g = STRUCTS["ovla_token_pg_args"]()
+    g.logits, g.ld, g.tokens, g.advantage, g.old_logprob = logits.data_ptr(), logits.stride(0), _p(tokens), _p(advantage), _p(old_logprob)
+    g.logprob, g.entropy, g.ratio, g.clipped = logprob.data_ptr(), entropy.data_ptr(), ratio.data_ptr(), clipped.data_ptr()
+    g.dlogits, g.ld_d = _p(d), (d.stride(0) if d is not None else 0)
+    g.temperature, g.clip_lo, g.clip_hi, g.grad_scale = float(temperature), float(clip[0]), float(clip[1]), float(grad_scale or 0.0)
+    g.rows, g.vocab, g.lo, g.hi = rows, vocab, lo, hi
+    _lib.call("ovla_token_pg", g, _stream())
+    return logprob, entropy, ratio, clipped, d
+
+
 def _chk_step(step):
     assert step.dtype == torch.int32 and step.numel() == 1 and step.is_cuda, "the DDIM step index is one int32 on the device"
 
