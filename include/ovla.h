@@ -906,7 +906,56 @@ int ovla_diffusion_noise(const ovla_diffusion_noise_args* a, void* stream);
  * ovla_token_ce's dlogits and loss_rows bit for bit.  advantage / old_logprob fp32 [rows] on the device; tokens int32 [rows].
  *
  * Both are stream-ordered and capturable, use no atomics and no workspace, and launch nothing on OVLA_EINVAL: a null pointer, rows or vocab
- * <= 0, ld < vocab, a window that is empty or leaves [0, vocab], T <= 0 or NaN or inf, clip_lo > clip_hi or a NaN bound. */
+ * <= 0, ld < vocab, a window that is empty or leaves [0, vocab], T <= 0 or NaN or inf, clip_lo > clip_hi or a NaN bound.
+ *
+ * THE GROUP FORMS (GRPO: G draws per observation from one forward; 1 <= G <= OVLA_PG_GROUP_MAX).
+ * ovla_sample_tokens_group: token / bin / logprob int32 / int32 / fp32 [rows, G], entropy fp32 [rows] (optional), row_key int32 [rows, G]
+ * (optional; without it the key of draw (r, g) is r * G + g).  Draw (r, g) is, bit for bit, what ovla_sample_tokens returns for logits row r
+ * under row key row_key[r, g], and entropy[r] is that kernel's entropy: it is the same kernel, one workgroup per (r, g).
+ *
+ * ovla_token_pg_group: G GIVEN samples per row in one launch, one workgroup per row.  tokens int32 / advantage fp32 [rows, G]; old_logprob /
+ * ref_logprob fp32 [rows, G] (optional); logprob / ratio fp32, clipped int32 [rows, G]; kl fp32 [rows, G], given exactly when ref_logprob is;
+ * entropy fp32 [rows]; dlogits bf16 [rows, ld_d] (optional; may alias logits).  The gradient with respect to the logits of
+ *   sum_{r,g} [ -min(ratio A, clip(ratio) A) + kl_coef * kl ]_{r,g} * grad_scale  -  ent_scale * sum_r H_r
+ * With m, sum, lse and H = entropy from token_row.h exactly as in ovla_token_pg, per sample g (each line one rounded fp32 operation per
+ * operator, left to right as bracketed, no FMA contraction):
+ *   logprob_g = s_tok_g - lse;  ratio_g, gate_g, clipped_g as in ovla_token_pg
+ *   c_g   = ((adv_g * gate_g) * grad_scale) * invT, and +0 (set, not multiplied) for a gated sample and for adv_g == 0 (a padding sample,
+ *           whatever its old_logprob holds)
+ *   with ref_logprob:  d_g = ref_g - logprob_g;  x_g = expm1f(d_g) (accurate);  kl_g = x_g - d_g  (Schulman's k3: exactly +0 on policy, >= 0);
+ *                      k_g = ((kl_coef * x_g) * grad_scale) * invT;  w_g = c_g + k_g.  The KL term is not gated.
+ *   without:           w_g = c_g (no add)
+ *   a sample with w_g == 0 is SKIPPED, never multiplied through (a NaN elsewhere in the row cannot leak in through it).
+ * Per column j of the window, e_j = __expf(s_j - m), inv = 1.0f / sum:
+ *   acc = t_{g1} + t_{g2} + ... in ascending g over the samples not skipped, t_g = fmaf(e_j, inv, -[j == token_g]) * w_g, the first term
+ *         taken as it is, each further term one rounded fp32 add;  acc = +0 when every sample is skipped
+ *   if ent_scale != 0 and e_j > 0:  acc = acc + ((ent_scale * invT) * (e_j * inv)) * ((s_j - lse) + H), added last
+ *   dlogits[r, j] = bf16(acc);  +0 for every j < vocab outside the window;  columns >= vocab are never touched.
+ * A row with every sample skipped and ent_scale == 0 is STORED as +0 on [0, vocab).  All G values s_tok_g are read, and a barrier passed,
+ * before any lane stores.  With G = 1, no ref_logprob, ent_scale == 0 and adv != 0: ovla_token_pg's outputs bit for bit.
+ * Refusals (OVLA_EINVAL, nothing launched): ovla_token_pg's / ovla_sample_tokens'; G outside [1, OVLA_PG_GROUP_MAX]; kl_coef negative or
+ * NaN; ent_scale NaN; ref_logprob without kl or kl without ref_logprob. */
+#define OVLA_PG_GROUP_MAX 64
+typedef struct {
+  const void* logits; int64_t ld;
+  int32_t* token; int32_t* bin; float* logprob; float* entropy;
+  const uint32_t* state_dev; const int32_t* row_key;
+  uint32_t seed_lo, seed_hi, call;
+  float temperature;
+  int32_t rows, vocab, lo, hi, n_tokens, n_bins, G;
+} ovla_sample_tokens_group_args;
+int ovla_sample_tokens_group(const ovla_sample_tokens_group_args* a, void* stream);
+
+typedef struct {
+  const void* logits; int64_t ld;
+  const int32_t* tokens; const float* advantage; const float* old_logprob; const float* ref_logprob;
+  float* logprob; float* ratio; int32_t* clipped; float* kl; float* entropy;
+  void* dlogits; int64_t ld_d;
+  float temperature, clip_lo, clip_hi, grad_scale, kl_coef, ent_scale;
+  int32_t rows, G, vocab, lo, hi;
+} ovla_token_pg_group_args;
+int ovla_token_pg_group(const ovla_token_pg_group_args* a, void* stream);
+
 typedef struct {
   const void* logits; int64_t ld;
   int32_t* token; int32_t* bin; float* logprob; float* entropy;

@@ -1458,6 +1458,8 @@ class VLAEngine:
     def _not_in_ema_scope(self, who: str):
         if self._ema_scope:
             raise RuntimeError(f"{who} inside ema_weights(): the flat buffers hold the averaged weights, not the ones being trained")
+        if self._ref_scope:
+            raise RuntimeError(f"{who} inside reference_policy(): the flat buffers hold the reference snapshot, not the weights being trained")
 
     def enable_ema(self):
         self._not_in_ema_scope("enable_ema")
@@ -2369,11 +2371,50 @@ class VLAEngine:
             raise ValueError(f"{what}: {tuple(t.shape)} for {B} observations of {A} action tokens")
         return t.reshape(B * A).contiguous()
 
-    def sample_action_tokens(self, batch: dict, temperature: float = 1.0, window="actions", row_keys=None):
+    def _group_rows(self, t, dtype, B: int, G: int, what: str, per_draw: bool = False):
+        """A per-token [B, G, A] (or, with `per_draw`, per-draw [B, G]) host or device tensor -> contiguous [B * A, G] on the device: the group
+        kernels' layout, one row of G samples per action row."""
+        A = self.cfg.num_action_tokens
+        t = torch.as_tensor(t).to(self.device, dtype)
+        if per_draw and tuple(t.shape) == (B, G):
+            t = t.reshape(B, G, 1).expand(B, G, A)
+        if tuple(t.shape) != (B, G, A):
+            raise ValueError(f"{what}: {tuple(t.shape)} for {B} observations of {G} draws of {A} action tokens")
+        return t.permute(0, 2, 1).reshape(B * A, G).contiguous()
+
+    def _group_out(self, t, B: int, G: int):
+        """[B * A, G] kernel output -> [B, G, A]."""
+        return t.view(B, self.cfg.num_action_tokens, G).permute(0, 2, 1).contiguous()
+
+    def _sample_action_tokens_group(self, batch: dict, G: int, temperature: float, window, row_keys):
+        """sample_action_tokens(num_samples=G): one forward, ONE ovla_sample_tokens_group launch.  Observation b's draw g has the key
+        row_keys[b, g] (default b * G + g), its token a the generator key `key * A + a` -- what the single-draw call gives an observation under
+        that key, so draw (b, g) is that call's draw bit for bit."""
+        cfg, B = self.cfg, batch["input_ids"].shape[0]
+        A, G = cfg.num_action_tokens, int(G)
+        if not 1 <= G <= ops.PG_GROUP_MAX:
+            raise ValueError(f"num_samples = {G} (1 .. {ops.PG_GROUP_MAX})")
+        lo, hi = self.token_window(window)
+        keys = torch.arange(B * G, dtype=torch.int32, device=self.device).view(B, G) if row_keys is None else torch.as_tensor(row_keys).to(self.device, torch.int32)
+        if tuple(keys.shape) == (B, G):
+            keys = keys.reshape(B, G, 1) * A + torch.arange(A, dtype=torch.int32, device=self.device)[None, None, :]
+        keys = self._group_rows(keys, torch.int32, B, G, "row_keys")
+        with torch.no_grad():
+            _, _, logits, n = self._action_logits(batch, False, "sample_action_tokens")
+            st = self.token_sample
+            tok, bins, lp, ent = ops.sample_tokens_group(logits[:n], G, n_tokens=cfg.vocab - cfg.pad_to_multiple_of, n_bins=cfg.n_action_bins - 1, window=(lo, hi),
+                                                         temperature=temperature, seed=st.seed, call=st.advance(), row_key=keys)
+        return dict(tokens=self._group_out(tok, B, G), bins=self._group_out(bins, B, G), logprob=self._group_out(lp, B, G), entropy=ent.view(B, A))
+
+    def sample_action_tokens(self, batch: dict, temperature: float = 1.0, window="actions", row_keys=None, num_samples: Optional[int] = None):
         """Draws the chunk's action tokens from softmax(logits[window] / temperature): one forward (inference mode) on the action rows, lm_head
         on them, ONE ovla_sample_tokens launch; nothing is read back.  `row_keys` int32 [B, A] (or [B]: key * A + a per token) replaces the
         row index in the generator's counter, so k draws of one observation in a batch differ and a draw does not depend on its position.
-        Advances the token stream's `call` by one.  -> dict(tokens, bins int32, logprob, entropy fp32), each [B, A] on the device."""
+        Advances the token stream's `call` by one.  -> dict(tokens, bins int32, logprob, entropy fp32), each [B, A] on the device.
+        `num_samples=G`: G draws per observation from the ONE forward (one ovla_sample_tokens_group launch, `call` advanced once): tokens / bins /
+        logprob [B, G, A], entropy [B, A]; `row_keys` [B, G] (key * A + a per token; default b * G + g) or [B, G, A]."""
+        if num_samples is not None:
+            return self._sample_action_tokens_group(batch, num_samples, temperature, window, row_keys)
         cfg, B = self.cfg, batch["input_ids"].shape[0]
         A = cfg.num_action_tokens
         lo, hi = self.token_window(window)
@@ -2394,8 +2435,17 @@ class VLAEngine:
 
     def policy_logprobs(self, batch: dict, tokens, temperature: float = 1.0, window="actions"):
         """Log-probability and entropy of given action tokens [B, A] under the current weights: the forward of sample_action_tokens, then
-        ovla_token_pg without a gradient -- for the tokens a draw returned, the bits that draw reported.  -> dict(logprob, entropy) [B, A]."""
+        ovla_token_pg without a gradient -- for the tokens a draw returned, the bits that draw reported.  -> dict(logprob, entropy) [B, A].
+        Tokens [B, G, A] (a group draw): one forward, one ovla_token_pg_group launch -> logprob [B, G, A], entropy [B, A]."""
         B, A = batch["input_ids"].shape[0], self.cfg.num_action_tokens
+        if torch.as_tensor(tokens).dim() == 3:
+            G = torch.as_tensor(tokens).shape[1]
+            tok = self._group_rows(tokens, torch.int32, B, G, "tokens")
+            with torch.no_grad():
+                _, _, logits, n = self._action_logits(batch, False, "policy_logprobs")
+                lp, _, _, _, ent, _ = ops.token_pg_group(logits[:n], tok, torch.ones((n, G), dtype=F32, device=self.device), window=self.token_window(window),
+                                                         temperature=temperature)
+            return dict(logprob=self._group_out(lp, B, G), entropy=ent.view(B, A))
         tok = self._rows_dev(tokens, torch.int32, B, "tokens")
         with torch.no_grad():
             _, _, logits, n = self._action_logits(batch, False, "policy_logprobs")
@@ -2429,6 +2479,123 @@ class VLAEngine:
         # the surrogate's value from the row outputs (device arithmetic, nothing read back): min(r A, clip(r) A)
         surr = torch.minimum(ratio * adv, ratio.clamp(float(clip[0]), float(clip[1])) * adv)
         return dict(loss=-surr.mean(), logprob=lp.mean(), entropy=ent.mean(), clip_frac=clipped.to(F32).mean(), ratio=ratio.mean())
+
+    def train_step_policy_gradient_group(self, batch: dict, tokens, advantages, old_logprobs=None, ref_logprobs=None, kl_coef: float = 0.0,
+                                         entropy_coef: float = 0.0, clip=(0.8, 1.2), temperature: float = 1.0, window="actions", loss_scale: float = 1.0):
+        """One GRPO / PPO micro-step on G drawn chunks per observation, from ONE forward and ONE backward:
+            loss = (1 / (B A G)) sum_{b, g, a} [ -min(ratio A_bg, clip(ratio) A_bg) + kl_coef kl ]  -  entropy_coef (1 / (B A)) sum_{b, a} H
+        with kl = expm1(d) - d, d = ref_logprob - logprob (Schulman's k3 estimator of KL(policy || reference)) and H the row entropy.  The forward
+        does not depend on the tokens, so the G surrogates share the logits and their gradients are summed in dlogits (ovla_token_pg_group, in
+        place) before lm_head's and the decoder's backward.  `tokens` int32 [B, G, A]; `advantages` [B, G] or [B, G, A]; `old_logprobs` /
+        `ref_logprobs` [B, G, A] (sample_action_tokens(num_samples=G) / reference_logprobs), host or device tensors.
+        -> dict of device scalars: loss, logprob, entropy, clip_frac, ratio, kl (means; kl is 0 without ref_logprobs)."""
+        self._not_in_ema_scope("train_step_policy_gradient_group")
+        self._refuse_per_policy_film_training(True)
+        B = batch["input_ids"].shape[0]
+        tokens = torch.as_tensor(tokens)
+        if tokens.dim() != 3:
+            raise ValueError(f"tokens: {tuple(tokens.shape)} ([B, G, A])")
+        G = tokens.shape[1]
+        tok = self._group_rows(tokens, torch.int32, B, G, "tokens")
+        adv = self._group_rows(advantages, F32, B, G, "advantages", per_draw=True)
+        old = None if old_logprobs is None else self._group_rows(old_logprobs, F32, B, G, "old_logprobs")
+        ref = None if ref_logprobs is None else self._group_rows(ref_logprobs, F32, B, G, "ref_logprobs")
+        lo, hi = self.token_window(window)
+        out, idx, logits, n = self._action_logits(batch, True, "train_step_policy_gradient_group")
+        lp, ratio, clipped, kl, ent, _ = ops.token_pg_group(logits[:n], tok, adv, window=(lo, hi), temperature=temperature, old_logprob=old, ref_logprob=ref,
+                                                            kl_coef=kl_coef, ent_scale=entropy_coef * loss_scale / n, clip=clip, grad_scale=loss_scale / (n * G),
+                                                            inplace_grad=True)
+        logits[n:].zero_()
+        dah = self.lm_loss_bwd(logits)
+        if getattr(self, "_overlap", False) and self.head is not None and hasattr(self.head, "store"):   # (no head trains here: its gradients are final)
+            for dt, g in self.head.store.flat_grad.items():
+                self.reducer.notify(self.head.store, dt, g.numel())
+        self.backward_from_rows(dah, idx, out)
+        surr = torch.minimum(ratio * adv, ratio.clamp(float(clip[0]), float(clip[1])) * adv)
+        kl_mean = kl.mean() if kl is not None else torch.zeros((), dtype=F32, device=self.device)
+        ent_mean = ent.mean()
+        return dict(loss=-surr.mean() + float(kl_coef) * kl_mean - float(entropy_coef) * ent_mean, logprob=lp.mean(), entropy=ent_mean,
+                    clip_frac=clipped.to(F32).mean(), ratio=ratio.mean(), kl=kl_mean)
+
+    # -- the frozen reference policy of the KL penalty: a snapshot of the trainables, swapped in for its log-probabilities ---------------------------
+    _reference: Optional[list] = None     # per store: {dtype: a copy of the flat parameter buffer}
+    _ref_scope = False
+
+    @property
+    def has_reference_policy(self) -> bool:
+        return self._reference is not None
+
+    @property
+    def in_reference_scope(self) -> bool:
+        return self._ref_scope
+
+    def set_reference_policy(self):
+        """Snapshots every store's flat parameter buffers, in their own dtype, as the reference policy ("the trainables as they are now").
+        Replaces an earlier snapshot.  Checkpoints do not hold it: export_reference_policy / load_reference_policy save it like an adapter."""
+        self._not_in_ema_scope("set_reference_policy")
+        self._reference = [{dt: flat.clone() for dt, flat in st.flat.items()} for st in self.stores]
+
+    def drop_reference_policy(self):
+        self._not_in_ema_scope("drop_reference_policy")
+        self._reference = None
+
+    def reference_policy_bytes(self) -> int:
+        return 0 if self._reference is None else sum(t.numel() * t.element_size() for snap in self._reference for t in snap.values())
+
+    @contextlib.contextmanager
+    def reference_policy(self):
+        """Scope in which the flat buffers hold the reference snapshot (as ema_weights() holds the averaged weights): inference entry points see
+        the reference policy with no change of their own.  On exit the live bits come back exactly; the derived copies are re-derived on both
+        sides.  The fp32 master of fp32-optimizer-state mode is not touched.  Training entry points raise inside; it nests neither with itself
+        nor with ema_weights()."""
+        if self._reference is None:
+            raise RuntimeError("reference_policy() without set_reference_policy() / load_reference_policy()")
+        self._not_in_ema_scope("reference_policy")
+        stash = [{dt: flat.clone() for dt, flat in st.flat.items()} for st in self.stores]
+        for st, snap in zip(self.stores, self._reference):
+            for dt, flat in st.flat.items():
+                flat.copy_(snap[dt])
+        self._ref_scope = True
+        try:
+            self.refresh_derived()
+            yield self
+        finally:
+            for st, live in zip(self.stores, stash):
+                for dt, flat in st.flat.items():
+                    flat.copy_(live[dt])
+            self._ref_scope = False
+            self.refresh_derived()
+
+    def reference_logprobs(self, batch: dict, tokens, temperature: float = 1.0, window="actions"):
+        """policy_logprobs under the reference policy: the two swaps around one forward."""
+        with self.reference_policy():
+            return self.policy_logprobs(batch, tokens, temperature=temperature, window=window)
+
+    def export_reference_policy(self) -> Dict[str, torch.Tensor]:
+        """The reference snapshot in export_trainable("data")'s key layout, as copies (save it like an adapter)."""
+        with self.reference_policy():
+            return {k: v.detach().clone() for k, v in self.export_trainable("data").items()}
+
+    def load_reference_policy(self, sd: Dict[str, torch.Tensor]):
+        """Sets the reference policy from a state dict in export_trainable("data")'s key layout (every trainable tensor must be present).  The
+        live parameters, their derived copies and the optimizer state keep their bits."""
+        self._not_in_ema_scope("load_reference_policy")
+        views = self.export_trainable("data")
+        missing = [k for k in views if k not in sd]
+        if missing:
+            raise KeyError(f"{len(missing)} trainable tensors missing from the reference policy, e.g. {missing[:3]}")
+        for name, view in views.items():
+            if tuple(sd[name].shape) != tuple(view.shape):
+                raise ValueError(f"{name}: reference shape {tuple(sd[name].shape)} != model shape {tuple(view.shape)}")
+        stash = [{dt: flat.clone() for dt, flat in st.flat.items()} for st in self.stores]
+        try:
+            for name, view in views.items():
+                view.copy_(sd[name].to(view.device, view.dtype))
+            self._reference = [{dt: flat.clone() for dt, flat in st.flat.items()} for st in self.stores]
+        finally:
+            for st, live in zip(self.stores, stash):
+                for dt, flat in st.flat.items():
+                    flat.copy_(live[dt])
 
     # -- the next-token cross entropy on the counted rows: train_step_discrete above and modeling._LMLossFn (`output.loss`) ------------------
     def counted_rows(self, labels, S: int, P: int):

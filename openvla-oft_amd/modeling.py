@@ -709,27 +709,41 @@ class OpenVLAForActionPrediction(_StoreModule):
         if len(batched) >= self.max_batch_graphs:   # B and the bucket come from callers (/act_batch): keep the most recent few
             del self._graphs[batched[0]]
 
-    def _sample_spec(self, do_sample, temperature, sample_seed, sample_keys, B, discrete: bool, return_tokens: bool):
+    def _sample_spec(self, do_sample, temperature, sample_seed, sample_keys, B, discrete: bool, return_tokens: bool, num_samples=None):
         """The `sample` argument of _infer for a do_sample=True call (None otherwise): temperature, the action-token window, the generator's
         three words (the engine's token stream, advanced by one; `sample_seed` replaces its seed for this draw), and the int32 key of every
-        action row -- observation key k_b (sample_keys[b], default b) gives k_b * A + a."""
+        action row -- observation key k_b (sample_keys[b], default b) gives k_b * A + a.  `num_samples=G`: G draws per observation from the one
+        forward; sample_keys [B, G] (default b * G + g), the keys int32 [B * A, G] (ovla_sample_tokens_group's layout) and "G" in the dict."""
         if not do_sample:
             if return_tokens:
                 raise ValueError("return_tokens=True goes with do_sample=True (the greedy decode reports no log-probabilities)")
+            if num_samples is not None:
+                raise ValueError("num_samples goes with do_sample=True (the greedy decode has one result)")
             return None
         if not discrete:
             raise ValueError("do_sample=True draws action TOKENS: it is the discrete path's (no action head, no per-policy heads); L1 and diffusion "
                              "heads are deterministic regressors / have their own noise")
         st, A = self.engine.token_sample, self.cfg.num_action_tokens
-        keys = torch.arange(B, dtype=torch.int64) if sample_keys is None else torch.as_tensor(np.asarray(sample_keys)).to(torch.int64).reshape(-1)
-        if keys.numel() != B:
-            raise ValueError(f"sample_keys: {keys.numel()} keys for {B} observations")
-        rows = (keys[:, None] * A + torch.arange(A, dtype=torch.int64)[None, :]).reshape(-1) & 0xFFFFFFFF
+        group = {}
+        if num_samples is not None:
+            G = int(num_samples)
+            if not 1 <= G <= ops.PG_GROUP_MAX:
+                raise ValueError(f"num_samples = {G} (1 .. {ops.PG_GROUP_MAX})")
+            keys = torch.arange(B * G, dtype=torch.int64).view(B, G) if sample_keys is None else torch.as_tensor(np.asarray(sample_keys)).to(torch.int64)
+            if tuple(keys.shape) != (B, G):
+                raise ValueError(f"sample_keys: {tuple(keys.shape)} for {B} observations of {G} draws")
+            rows = (keys[:, None, :] * A + torch.arange(A, dtype=torch.int64)[None, :, None]).reshape(B * A, G) & 0xFFFFFFFF
+            group = dict(G=G)
+        else:
+            keys = torch.arange(B, dtype=torch.int64) if sample_keys is None else torch.as_tensor(np.asarray(sample_keys)).to(torch.int64).reshape(-1)
+            if keys.numel() != B:
+                raise ValueError(f"sample_keys: {keys.numel()} keys for {B} observations")
+            rows = (keys[:, None] * A + torch.arange(A, dtype=torch.int64)[None, :]).reshape(-1) & 0xFFFFFFFF
         rows = torch.where(rows >= 2 ** 31, rows - 2 ** 32, rows).to(torch.int32)
         words = st.words(st.advance())
         if sample_seed is not None:
             words[0], words[1] = int(sample_seed) & 0xFFFFFFFF, (int(sample_seed) >> 32) & 0xFFFFFFFF
-        return dict(temperature=float(temperature), window=self.engine.token_window("actions"), words=words, keys=rows, out={})
+        return dict(temperature=float(temperature), window=self.engine.token_window("actions"), words=words, keys=rows, out={}, **group)
 
     def _decode(self, pred, bins, hidden, sample=None):
         """Normalised actions [B, chunk, action_dim] from whichever the forward produced: the head's prediction (:923-927); the bin indices, when
@@ -738,6 +752,14 @@ class OpenVLAForActionPrediction(_StoreModule):
         if pred is not None:
             normalized = pred.float().cpu().numpy()
         else:
+            if bins is None and sample is not None and "G" in sample:   # G draws per action row from the one forward: [B * A, G] -> [B, G, A]
+                (B, A), G, w = hidden.shape[:2], sample["G"], sample["words"]
+                tok, b, lp, ent = ops.sample_tokens_group(self.engine.lm_head_rows(hidden.view(-1, cfg.llm_dim))[:B * A], G, n_tokens=self.vocab_size,
+                                                          n_bins=self.bin_centers.shape[0], window=sample["window"], temperature=sample["temperature"],
+                                                          seed=w[0] | (w[1] << 32), call=w[2], row_key=sample["keys"].contiguous().to(self.device))
+                per_draw = lambda t: t.view(B, A, G).permute(0, 2, 1).contiguous()
+                sample["out"].update(tokens=per_draw(tok), logprobs=per_draw(lp), entropy=ent)
+                return self.bin_centers[per_draw(b).cpu().numpy().astype(np.int64)].reshape(B, G, cfg.chunk, cfg.action_dim)
             if bins is None and sample is not None:   # the draw of ChunkGraph(sample=...), as eager launches
                 n = hidden.shape[0] * hidden.shape[1]
                 w = sample["words"]
@@ -935,6 +957,8 @@ class OpenVLAForActionPrediction(_StoreModule):
         if not return_tokens:
             return ()
         o, A = sample["out"], self.cfg.num_action_tokens
+        if "G" in sample:
+            return (SampledTokens(o["tokens"], o["logprobs"], o["entropy"].view(B, A)),)
         return (SampledTokens(o["tokens"].view(B, A), o["logprobs"].view(B, A), o["entropy"].view(B, A)),)
 
     def _action_attention(self, attention: dict, mask, pixel_values, use_proprio: bool) -> ActionAttention:
@@ -951,7 +975,7 @@ class OpenVLAForActionPrediction(_StoreModule):
     def predict_action_batch(self, prompts, pixel_values, unnorm_key=None, proprio=None, proprio_projector=None, action_head=None,
                              noisy_action_projector=None, use_film: bool = False, noise=None, pad_to: Optional[int] = None, policy=None,
                              output_attentions: bool = False, do_sample: bool = False, temperature: float = 1.0, sample_seed: Optional[int] = None,
-                             sample_keys=None, return_tokens: bool = False):
+                             sample_keys=None, return_tokens: bool = False, num_samples: Optional[int] = None):
         """predict_action for B observations in one forward.  prompts: list of B (input_ids, attention_mask) pairs ([1, L_b] or [L_b], lengths may
         differ; masks right-padded), pixel_values [B, 6 I, H, W], proprio [B, proprio_dim], noise [B, chunk, action_dim] (diffusion: each sample's
         DDIM trajectory starts from its own noise).  Returns (actions [B, chunk, action_dim] unnormalised with `unnorm_key`, action hidden states
@@ -973,10 +997,17 @@ class OpenVLAForActionPrediction(_StoreModule):
         softmax(logits[action ids] / temperature) on the device, inside the captured graph under graph replay (ovla_sample_tokens in place of
         ovla_argmax_bins; each replay draws under the `call` its load() wrote).  `sample_keys` [B]: each observation's key in the generator (default
         its index) -- an observation draws the same tokens alone and in any batch under the same key and call.  `return_tokens=True` appends a
-        SampledTokens.  Every sampled call advances the engine's token stream by one; `sample_seed` replaces its seed for this call."""
+        SampledTokens.  Every sampled call advances the engine's token stream by one; `sample_seed` replaces its seed for this call.
+        `num_samples=G` (with do_sample=True, the eager path only): G draws per observation from the ONE forward (one ovla_sample_tokens_group
+        launch): actions [B, G, chunk, action_dim], SampledTokens with tokens / logprobs [B, G, A] and entropy [B, A]; `sample_keys` [B, G]
+        (default b * G + g) -- draw (b, g) is the num_samples=None draw of observation b under the key sample_keys[b, g].  Under graph replay it
+        raises: the captured decode holds one draw per observation."""
         cfg = self.cfg
         if do_sample and policy is not None:
             raise ValueError("predict_action_batch(do_sample=True) is not supported with per-request policies")
+        if num_samples is not None and self.use_graph:
+            raise ValueError("predict_action_batch(num_samples=...) is not supported under graph replay (the captured decode draws once per "
+                             "observation): enable_graph_replay(False), or call it once per draw with sample_keys")
         per_policy_film = bool(getattr(self.engine, "film_per_policy", False))
         if use_film != self.engine.use_film:
             raise ValueError(f"use_film={use_film} but the model was built with use_film={self.engine.use_film}")
@@ -1020,7 +1051,7 @@ class OpenVLAForActionPrediction(_StoreModule):
                                             noise=rep(noise), policy=None if policy is None else policy + [policy[0]] * len(fill),
                                             output_attentions=output_attentions, do_sample=do_sample, temperature=temperature, sample_seed=sample_seed,
                                             sample_keys=None if sample_keys is None else list(sample_keys) + [list(sample_keys)[0]] * len(fill),
-                                            return_tokens=return_tokens)
+                                            return_tokens=return_tokens, num_samples=num_samples)
             tail = (SampledTokens(*(t[:B] for t in res[-1])),) if return_tokens else ()
             if output_attentions:
                 att = res[2]
@@ -1059,7 +1090,7 @@ class OpenVLAForActionPrediction(_StoreModule):
             labels[b, len(r) - 1] = STOP_INDEX
         attention = {} if output_attentions else None
         extra = (lambda: (self._action_attention(attention, mask, pixel_values, use_proprio),)) if output_attentions else (lambda: ())
-        sample = self._sample_spec(do_sample, temperature, sample_seed, sample_keys, B, action_head is None and policy is None, return_tokens)
+        sample = self._sample_spec(do_sample, temperature, sample_seed, sample_keys, B, action_head is None and policy is None, return_tokens, num_samples)
         if policy is not None and self._pool_resident:
             normalized, hidden = self._infer_pooled(ids, mask, labels, pixel_values, prop, policy, use_proprio, attention=attention)
             stats = [self.policy_norm_stats(p) for p in policy]

@@ -1073,6 +1073,82 @@ def token_pg(logits, tokens, advantage, *, vocab=None, window=None, temperature=
     return logprob, entropy, ratio, clipped, d
 
 
+PG_GROUP_MAX = 64          # ovla.h: OVLA_PG_GROUP_MAX
+
+
+def sample_tokens_group(logits, G, *, n_tokens, n_bins, vocab=None, window=None, temperature=1.0, seed=0, call=0, state_dev=None, row_key=None,
+                        entropy=True, token=None, bins=None, logprob=None, entropy_out=None):
+    """G draws per row in one launch (ovla.h: ovla_sample_tokens_group): logits bf16 [rows, ld >= vocab] -> (token int32, bin int32, logprob fp32,
+    each [rows, G]; entropy fp32 [rows] or None).  Draw (r, g) is sample_tokens' draw of row r under row key row_key[r, g] (default r * G + g),
+    bit for bit.  The remaining arguments are sample_tokens'."""
+    _chk(logits, name="logits")
+    assert logits.dim() == 2 and logits.stride(1) == 1
+    rows, dev, G = logits.shape[0], logits.device, int(G)
+    vocab = logits.shape[1] if vocab is None else vocab
+    lo, hi = _token_window(window, vocab)
+    token = torch.empty((rows, G), dtype=torch.int32, device=dev) if token is None else token
+    bins = torch.empty((rows, G), dtype=torch.int32, device=dev) if bins is None else bins
+    logprob = torch.empty((rows, G), dtype=torch.float32, device=dev) if logprob is None else logprob
+    if entropy_out is None and entropy:
+        entropy_out = torch.empty(rows, dtype=torch.float32, device=dev)
+    for t, dt, name, n in ((token, torch.int32, "token", rows * G), (bins, torch.int32, "bins", rows * G), (logprob, torch.float32, "logprob", rows * G),
+                           (entropy_out, torch.float32, "entropy", rows), (row_key, torch.int32, "row_key", rows * G)):
+        if t is not None:
+            _chk(t, dt, name)
+            assert t.numel() == n and t.is_contiguous(), f"{name}: expected {n} contiguous elements"
+    if state_dev is not None:
+        assert state_dev.is_cuda and state_dev.numel() == 3 and state_dev.is_contiguous() and state_dev.element_size() == 4 and not state_dev.is_floating_point(), \
+            "state_dev: three 32-bit integers on the device (seed_lo, seed_hi, call)"
+    g = STRUCTS["ovla_sample_tokens_group_args"]()
+    g.logits, g.ld, g.token, g.bin, g.logprob, g.entropy = logits.data_ptr(), logits.stride(0), token.data_ptr(), bins.data_ptr(), logprob.data_ptr(), _p(entropy_out)
+    g.state_dev, g.row_key = _p(state_dev), _p(row_key)
+    g.seed_lo, g.seed_hi, g.call = int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF, int(call) & 0xFFFFFFFF
+    g.temperature = float(temperature)
+    g.rows, g.vocab, g.lo, g.hi, g.n_tokens, g.n_bins, g.G = rows, vocab, lo, hi, n_tokens, n_bins, G
+    _lib.call("ovla_sample_tokens_group", g, _stream())
+    return token, bins, logprob, entropy_out
+
+
+def token_pg_group(logits, tokens, advantage, *, vocab=None, window=None, temperature=1.0, old_logprob=None, ref_logprob=None, kl_coef=0.0, ent_scale=0.0,
+                   clip=(0.8, 1.2), grad_scale=None, inplace_grad=True, dlogits=None, logprob=None, ratio=None, clipped=None, kl=None, entropy=None):
+    """Clipped policy-gradient objective with a KL penalty and an entropy bonus on G given samples per row (ovla.h: ovla_token_pg_group): logits bf16
+    [rows, ld >= vocab], tokens int32 / advantage fp32 [rows, G] (and old_logprob / ref_logprob fp32 [rows, G]) on the device -> (logprob, ratio fp32
+    [rows, G], clipped int32 [rows, G], kl fp32 [rows, G] or None, entropy fp32 [rows], dlogits bf16 or None).  `kl` exists exactly when ref_logprob is
+    given.  The gradient's destination follows token_pg."""
+    _chk(logits, name="logits")
+    assert logits.dim() == 2 and logits.stride(1) == 1 and tokens.dim() == 2 and tokens.shape[0] == logits.shape[0]
+    rows, dev, G = logits.shape[0], logits.device, tokens.shape[1]
+    vocab = logits.shape[1] if vocab is None else vocab
+    lo, hi = _token_window(window, vocab)
+    logprob = torch.empty((rows, G), dtype=torch.float32, device=dev) if logprob is None else logprob
+    ratio = torch.empty((rows, G), dtype=torch.float32, device=dev) if ratio is None else ratio
+    clipped = torch.empty((rows, G), dtype=torch.int32, device=dev) if clipped is None else clipped
+    entropy = torch.empty(rows, dtype=torch.float32, device=dev) if entropy is None else entropy
+    if kl is None and ref_logprob is not None:
+        kl = torch.empty((rows, G), dtype=torch.float32, device=dev)
+    for t, dt, name, n in ((tokens, torch.int32, "tokens", rows * G), (advantage, torch.float32, "advantage", rows * G),
+                           (old_logprob, torch.float32, "old_logprob", rows * G), (ref_logprob, torch.float32, "ref_logprob", rows * G),
+                           (logprob, torch.float32, "logprob", rows * G), (ratio, torch.float32, "ratio", rows * G), (clipped, torch.int32, "clipped", rows * G),
+                           (kl, torch.float32, "kl", rows * G), (entropy, torch.float32, "entropy", rows)):
+        if t is not None:
+            _chk(t, dt, name)
+            assert t.numel() == n and t.is_contiguous(), f"{name}: expected {n} contiguous elements"
+    d = None
+    if grad_scale is not None:
+        d = dlogits if dlogits is not None else (logits if inplace_grad else torch.empty_like(logits))
+        assert d.dtype == BF16 and d.shape[0] == rows and d.shape[1] >= vocab and d.stride(1) == 1
+    g = STRUCTS["ovla_token_pg_group_args"]()
+    g.logits, g.ld, g.tokens, g.advantage = logits.data_ptr(), logits.stride(0), _p(tokens), _p(advantage)
+    g.old_logprob, g.ref_logprob = _p(old_logprob), _p(ref_logprob)
+    g.logprob, g.ratio, g.clipped, g.kl, g.entropy = logprob.data_ptr(), ratio.data_ptr(), clipped.data_ptr(), _p(kl), entropy.data_ptr()
+    g.dlogits, g.ld_d = _p(d), (d.stride(0) if d is not None else 0)
+    g.temperature, g.clip_lo, g.clip_hi, g.grad_scale = float(temperature), float(clip[0]), float(clip[1]), float(grad_scale or 0.0)
+    g.kl_coef, g.ent_scale = float(kl_coef), float(ent_scale)
+    g.rows, g.G, g.vocab, g.lo, g.hi = rows, G, vocab, lo, hi
+    _lib.call("ovla_token_pg_group", g, _stream())
+    return logprob, ratio, clipped, kl, entropy, d
+
+
 def _chk_step(step):
     assert step.dtype == torch.int32 and step.numel() == 1 and step.is_cuda, "the DDIM step index is one int32 on the device"
 
