@@ -976,6 +976,76 @@ typedef struct {
 } ovla_token_pg_args;
 int ovla_token_pg(const ovla_token_pg_args* a, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Laplace policy on the L1 head (the continuous path beyond regression: L1 regression is maximum likelihood for a Laplace distribution of
+ * fixed scale b around the head's prediction mu, so that distribution is the policy the L1 head already is -- the modes coincide and the L1
+ * loss gradient is the policy's score up to 1 / b).  ovla_laplace_sample draws G chunks per row around mu and reports their log-probabilities;
+ * ovla_laplace_pg computes, for GIVEN draws, the same log-probabilities, the PPO / GRPO clipped surrogate, the closed-form KL to a reference
+ * prediction of the same scale, and their gradient with respect to mu: the `dpred` ovla_head_out_bwd takes.  The forward does not depend on the
+ * draws, so G draws per observation share one forward and one backward.  Everything stays on the device; the generator is the token
+ * sampler's (seed, `call` advanced once per draw by the caller) on a stream word of its own.
+ * Shared conventions: pred (mu) bf16 [rows, adim], rows = B * chunk, what ovla_head_out_fwd stores; 1 <= adim <= 16; 1 <= G <= OVLA_PG_GROUP_MAX;
+ * scale[d] = b_d > 0 and finite, log_norm[d] = float32(log(2 b_d)) formed by the caller in double (no logf enters the log-probability), both by
+ * value, entries >= adim ignored; inv_b_d = 1.0f / b_d (IEEE division).  Every operator below is one rounded fp32 operation in the bracketing
+ * written, no FMA contraction.  THE CONTRACT (identical in csrc/laplace_policy.hip and in the numpy restatement
+ * tests/laplace_policy_reference.py):
+ *   logprob     q_d = fabsf(a_d - mu_d) * inv_b_d;  acc = 0;  acc = acc - (q_d + log_norm[d]) for ascending d;  logprob = acc.
+ *
+ * ovla_laplace_sample: action fp32 [rows, G, adim], logprob fp32 [rows, G]; row_key int32 [rows, G] (optional; without it the key of draw
+ * (r, g) is r * G + g).  For dimension d of the draw with key `key`:
+ *   generator   Philox4x32-10 as in "LoRA dropout" above: word w = o[d & 3] of o = philox(d >> 2, key, 4, call) with key (seed_lo, seed_hi).
+ *               (Stream word 4: the token sampler uses 3 on the same seed.)
+ *   uniform     u = float(2 (w >> 9) + 1) * 2^-24: exact in fp32, strictly inside (0, 1), symmetric about 1/2.
+ *   variate     x = u - 0.5f;  t = 1.0f - 2.0f * fabsf(x): both exact, x != 0, t in [2^-23, 1 - 2^-23];  the variate is exactly symmetric.
+ *   noise       e = copysignf(-logf(t), x) with the accurate logf: a unit Laplace variate (E|e| = 1, E e^2 = 2), |e| <= 15.943.
+ *   action      a_d = mu_d + b_d * e, stored;  the log-probability is computed from the STORED a_d, not from e: the bits ovla_laplace_pg
+ *               recomputes from the stored draw.
+ * state_dev (optional, DEVICE uint32[3] = seed_lo, seed_hi, call) overrides the three host values when the kernel runs, as in ovla_sample_tokens.
+ *
+ * ovla_laplace_pg: G GIVEN samples per row in one launch, one workgroup of 64 lanes per row.  actions fp32 [rows, G, adim]; advantage fp32
+ * [rows, G]; old_logprob fp32 [rows, G] (optional); ref_pred bf16 [rows, adim] (optional: the KL term exists exactly when it is given);
+ * logprob / ratio fp32, clipped int32 [rows, G]; kl fp32 [rows], given exactly when ref_pred is; dpred bf16 [rows, adim] (optional).
+ * Per sample g:
+ *   logprob_g as above;  ratio_g = expf(logprob_g - old_g) (accurate expf), or exactly 1 without old_logprob
+ *   gate_g, clipped_g by ovla_token_pg's rule;  c_g = (adv_g * gate_g) * grad_scale, and +0 (set, not multiplied) for a gated sample and for
+ *   adv_g == 0.  A sample with c_g == 0 is SKIPPED, never multiplied through, and its actions are not read for the gradient: a padding draw
+ *   full of NaN cannot leak into the row.
+ * Per (r, d):
+ *   acc = t_{g1,d} + t_{g2,d} + ... in ascending g over the samples not skipped, t_{g,d} = (sgn(mu_d - a_{g,d}) * inv_b_d) * c_g with
+ *         sgn(0) = 0 (taken from comparisons: a NaN action gives 0), the first term taken as it is, each further term one rounded fp32 add;
+ *         acc = +0 when every sample is skipped
+ *   with ref_pred:  D = mu_d - ref_d;  q = fabsf(D) * inv_b_d;  x = -expm1f(-q) (accurate expm1f);  kl_d = q - x, which is
+ *         KL(Laplace(mu, b) || Laplace(ref, b)) of the dimension, exactly +0 on policy and >= 0;  kl[r] = kl_0 + kl_1 + ... in ascending d;
+ *         k_d = ((kl_coef * x) * kl_scale) * (sgn(D) * inv_b_d);  acc = acc + k_d, added last.  The KL term is not gated.
+ *   dpred[r, d] = bf16(acc)
+ * the gradient with respect to mu of  sum_{r,g} -min(ratio A, clip(ratio) A) * grad_scale  +  kl_coef * kl_scale * sum_r kl[r].  With G = 1,
+ * adv = 1, b = 1, no old_logprob and no ref_pred: dpred = bf16(sgn(mu - a) * grad_scale), the bits ovla_head_out_bwd forms for the L1 loss.
+ *
+ * Both are stream-ordered and capturable, use no atomics and no workspace; a row's bits depend on its inputs and its row keys only, never on
+ * `rows` or the row's position.  Refusals (OVLA_EINVAL, nothing launched): a null required pointer; rows <= 0; adim outside [1, 16]; G outside
+ * [1, OVLA_PG_GROUP_MAX]; a scale that is not positive and finite; clip_lo > clip_hi or a NaN bound; kl_coef negative or NaN; ref_pred
+ * without kl or kl without ref_pred. */
+typedef struct {
+  const void* pred;
+  float* action; float* logprob;
+  const uint32_t* state_dev; const int32_t* row_key;
+  uint32_t seed_lo, seed_hi, call;
+  float scale[16], log_norm[16];
+  int32_t rows, adim, G;
+} ovla_laplace_sample_args;
+int ovla_laplace_sample(const ovla_laplace_sample_args* a, void* stream);
+
+typedef struct {
+  const void* pred; const void* ref_pred;
+  const float* actions; const float* advantage; const float* old_logprob;
+  float* logprob; float* ratio; int32_t* clipped; float* kl;
+  void* dpred;
+  float scale[16], log_norm[16];
+  float clip_lo, clip_hi, grad_scale, kl_coef, kl_scale;
+  int32_t rows, adim, G;
+} ovla_laplace_pg_args;
+int ovla_laplace_pg(const ovla_laplace_pg_args* a, void* stream);
+
 /* fp32 -> bf16 convert with scale (publishes .grad views), and fill */
 typedef struct { const float* src; void* dst; int64_t n; float scale; } ovla_cvt_args;
 int ovla_cvt_f32_to_bf16(const ovla_cvt_args* a, void* stream);

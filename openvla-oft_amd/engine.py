@@ -2597,6 +2597,134 @@ class VLAEngine:
                 for dt, flat in st.flat.items():
                     flat.copy_(live[dt])
 
+    # -- the Laplace policy on the L1 head (ovla.h "Laplace policy on the L1 head"): draws around the head's prediction, their log-probabilities,
+    # -- and the group policy-gradient step on them ------------------------------------------------------------------------------------------
+    def _l1_head(self, who: str, action_head=None):
+        if self.head_kind != "l1" or (self.head is None and action_head is None):
+            raise RuntimeError(f"{who} needs an engine built with head='l1' (the Laplace policy is the L1 head's; this one has head={self.head_kind!r})")
+        return action_head if action_head is not None else self.head
+
+    def _action_means(self, batch: dict, train: bool, head, proprio_projector=None):
+        """The forward on the action rows and the L1 head on them -> (out, rows_idx, pred bf16 [B * chunk, action_dim], the head's saved state)."""
+        kw = {} if proprio_projector is None else dict(proprio_projector=proprio_projector)
+        out = self.forward(batch["input_ids"], batch["attention_mask"], batch["pixel_values"], batch["labels"], proprio=batch.get("proprio"),
+                           train=train, sel="actions", **kw)
+        ah, idx = self.action_hidden(out)
+        pred, _, hsaved = head.fwd(ah, train=train)
+        return out, idx, pred, hsaved
+
+    def _chunk_rows(self, t, dtype, B: int, G: int, what: str, per_draw: bool = False, per_dim: bool = False):
+        """A per-step [B, G, chunk] (with `per_draw` also per-draw [B, G]; with `per_dim` [B, G, chunk, action_dim]) host or device tensor ->
+        contiguous [B * chunk, G (, action_dim)] on the device: the Laplace kernels' layout, one row of G samples per chunk step."""
+        C, Ad = self.cfg.chunk, self.cfg.action_dim
+        t = torch.as_tensor(t).to(self.device, dtype)
+        if per_draw and tuple(t.shape) == (B, G):
+            t = t.reshape(B, G, 1).expand(B, G, C)
+        want = (B, G, C, Ad) if per_dim else (B, G, C)
+        if tuple(t.shape) != want:
+            raise ValueError(f"{what}: {tuple(t.shape)} for {B} observations of {G} draws of {C} steps" + (f" of {Ad} dimensions" if per_dim else ""))
+        if per_dim:
+            return t.permute(0, 2, 1, 3).reshape(B * C, G, Ad).contiguous()
+        return t.permute(0, 2, 1).reshape(B * C, G).contiguous()
+
+    def _chunk_out(self, t, B: int, G: int):
+        """[B * chunk, G (, action_dim)] kernel output -> [B, G, chunk (, action_dim)]."""
+        C = self.cfg.chunk
+        if t.dim() == 3:
+            return t.view(B, C, G, t.shape[2]).permute(0, 2, 1, 3).contiguous()
+        return t.view(B, C, G).permute(0, 2, 1).contiguous()
+
+    def sample_actions_laplace(self, batch: dict, scale, num_samples: int = 1, row_keys=None):
+        """Draws G = num_samples chunks per observation from the Laplace policy of scale `scale` (a scalar or one value per action dimension,
+        in normalised action units) around the L1 head's prediction: one forward (inference mode) on the action rows, the head, ONE
+        ovla_laplace_sample launch; nothing is read back.  Advances the token stream's `call` by one.  `row_keys` int32 [B, G] (observation draw
+        key k gives its step c the generator key k * chunk + c; default b * G + g) or [B, G, chunk]: a draw does not depend on its position.
+        -> dict(actions fp32 [B, G, chunk, action_dim], logprob fp32 [B, G, chunk], mean bf16 [B, chunk, action_dim]) on the device."""
+        head = self._l1_head("sample_actions_laplace")
+        cfg, B, G = self.cfg, batch["input_ids"].shape[0], int(num_samples)
+        C = cfg.chunk
+        if not 1 <= G <= ops.PG_GROUP_MAX:
+            raise ValueError(f"num_samples = {G} (1 .. {ops.PG_GROUP_MAX})")
+        ops.laplace_scales(scale, cfg.action_dim)                # (raises before anything advances)
+        keys = torch.arange(B * G, dtype=torch.int32, device=self.device).view(B, G) if row_keys is None else torch.as_tensor(row_keys).to(self.device, torch.int32)
+        if tuple(keys.shape) == (B, G):
+            keys = keys.reshape(B, G, 1) * C + torch.arange(C, dtype=torch.int32, device=self.device)[None, None, :]
+        keys = self._chunk_rows(keys, torch.int32, B, G, "row_keys")
+        with torch.no_grad():
+            _, _, pred, _ = self._action_means(batch, False, head)
+            st = self.token_sample
+            act, lp = ops.laplace_sample(pred, scale, G, seed=st.seed, call=st.advance(), row_key=keys)
+        return dict(actions=self._chunk_out(act, B, G), logprob=self._chunk_out(lp, B, G), mean=pred.view(B, C, cfg.action_dim))
+
+    def action_logprobs(self, batch: dict, actions, scale):
+        """Log-probability of given chunks [B, G, chunk, action_dim] under the Laplace policy around the current weights' prediction: the
+        forward of sample_actions_laplace, then ovla_laplace_pg without a gradient -- for the chunks a draw returned, the bits that draw
+        reported.  -> dict(logprob fp32 [B, G, chunk], mean bf16 [B, chunk, action_dim])."""
+        head = self._l1_head("action_logprobs")
+        cfg, B = self.cfg, batch["input_ids"].shape[0]
+        actions = torch.as_tensor(actions)
+        if actions.dim() != 4:
+            raise ValueError(f"actions: {tuple(actions.shape)} ([B, G, chunk, action_dim])")
+        G = actions.shape[1]
+        act = self._chunk_rows(actions, F32, B, G, "actions", per_dim=True)
+        with torch.no_grad():
+            _, _, pred, _ = self._action_means(batch, False, head)
+            lp, _, _, _, _ = ops.laplace_pg(pred, act, torch.ones((pred.shape[0], G), dtype=F32, device=self.device), scale)
+        return dict(logprob=self._chunk_out(lp, B, G), mean=pred.view(B, cfg.chunk, cfg.action_dim))
+
+    def reference_action_means(self, batch: dict) -> torch.Tensor:
+        """The L1 head's prediction under the reference policy, bf16 [B, chunk, action_dim]: train_step_action_pg_group's `ref_means` (the two swaps
+        around one forward)."""
+        head = self._l1_head("reference_action_means")
+        with self.reference_policy():
+            with torch.no_grad():
+                _, _, pred, _ = self._action_means(batch, False, head)
+        return pred.view(batch["input_ids"].shape[0], self.cfg.chunk, self.cfg.action_dim)
+
+    def train_step_action_pg_group(self, batch: dict, actions, advantages, scale, old_logprobs=None, ref_means=None, kl_coef: float = 0.0, clip=(0.8, 1.2),
+                                   loss_scale: float = 1.0, action_head=None, proprio_projector=None):
+        """One GRPO / PPO micro-step on G drawn chunks per observation under the Laplace policy of the L1 head, from ONE forward and ONE backward:
+            loss = (1 / (B chunk G)) sum_{b, g, c} -min(ratio A_bg, clip(ratio) A_bg)  +  kl_coef (1 / (B chunk)) sum_{b, c} kl
+        with ratio = exp(logprob - old_logprob) per chunk step (1 without old_logprobs) and kl the closed-form KL(policy || reference) of two
+        Laplace distributions of the same scale, summed over the action dimensions.  The forward does not depend on the draws: the training
+        forward on the action rows, the head, one ovla_laplace_pg launch that forms the gradient with respect to the head's prediction, then the
+        head's and the decoder's backward into the flat gradient buffers.  `actions` fp32 [B, G, chunk, action_dim] (RAW draws, normalised units);
+        `advantages` [B, G] or [B, G, chunk]; `old_logprobs` [B, G, chunk] (sample_actions_laplace / action_logprobs); `ref_means`
+        [B, chunk, action_dim] (reference_action_means), required with kl_coef > 0; host or device tensors.
+        -> dict of device scalars: loss, logprob, ratio, clip_frac, kl (means; kl is 0 without ref_means)."""
+        self._not_in_ema_scope("train_step_action_pg_group")
+        self._refuse_per_policy_film_training(True)
+        head = self._l1_head("train_step_action_pg_group", action_head)
+        cfg, B = self.cfg, batch["input_ids"].shape[0]
+        actions = torch.as_tensor(actions)
+        if actions.dim() != 4:
+            raise ValueError(f"actions: {tuple(actions.shape)} ([B, G, chunk, action_dim])")
+        G = actions.shape[1]
+        act = self._chunk_rows(actions, F32, B, G, "actions", per_dim=True)
+        adv = self._chunk_rows(advantages, F32, B, G, "advantages", per_draw=True)
+        old = None if old_logprobs is None else self._chunk_rows(old_logprobs, F32, B, G, "old_logprobs")
+        ref = None
+        if ref_means is not None:
+            ref = torch.as_tensor(ref_means).to(self.device, BF16)
+            if ref.numel() != B * cfg.chunk * cfg.action_dim:
+                raise ValueError(f"ref_means: {tuple(ref.shape)} for {B} observations of {cfg.chunk} steps of {cfg.action_dim} dimensions")
+            ref = ref.reshape(B * cfg.chunk, cfg.action_dim).contiguous()
+        elif kl_coef > 0.0:
+            raise ValueError("kl_coef > 0 needs ref_means (reference_action_means)")
+        ops.laplace_scales(scale, cfg.action_dim)
+        out, idx, pred, hsaved = self._action_means(batch, True, head, proprio_projector)
+        n = pred.shape[0]
+        lp, ratio, clipped, kl, dpred = ops.laplace_pg(pred, act, adv, scale, old_logprob=old, ref_pred=ref, kl_coef=kl_coef, clip=clip,
+                                                       grad_scale=loss_scale / (n * G), kl_scale=loss_scale / n)
+        dah = head.bwd(hsaved, dpred=dpred)
+        if getattr(self, "_overlap", False) and hasattr(head, "store"):
+            for dt, g in head.store.flat_grad.items():
+                self.reducer.notify(head.store, dt, g.numel())
+        self.backward_from_rows(dah, idx, out)
+        surr = torch.minimum(ratio * adv, ratio.clamp(float(clip[0]), float(clip[1])) * adv)
+        kl_mean = kl.mean() if kl is not None else torch.zeros((), dtype=F32, device=self.device)
+        return dict(loss=-surr.mean() + float(kl_coef) * kl_mean, logprob=lp.mean(), ratio=ratio.mean(), clip_frac=clipped.to(F32).mean(), kl=kl_mean)
+
     # -- the next-token cross entropy on the counted rows: train_step_discrete above and modeling._LMLossFn (`output.loss`) ------------------
     def counted_rows(self, labels, S: int, P: int):
         """Host int64 labels [B, L] -> (bb, jj, rows_idx int32 [n_tok] device, targets int64 [n_tok] device).  Text position j + 1 with

@@ -218,11 +218,15 @@ def device_pixel_values(images: List[np.ndarray], cfg: Any) -> torch.Tensor:
 
 
 def get_vla_action(cfg: Any, vla, processor: Any, obs: Dict[str, Any], task_label: str, action_head=None, proprio_projector=None,
-                   noisy_action_projector=None, use_film: bool = False, *, return_attention: bool = False):
+                   noisy_action_projector=None, use_film: bool = False, *, return_attention: bool = False, action_noise_scale=None):
     """openvla_utils.py:711-796.  Note: like the reference, overwrites obs["state"] with the normalised proprio.
     `return_attention=True` -> (actions, modeling.ActionAttention): which camera, patches and prompt tokens each action row looked at
-    (predict_action(output_attentions=True): the eager forward; not with a diffusion head)."""
+    (predict_action(output_attentions=True): the eager forward; not with a diffusion head).
+    `action_noise_scale` (an L1 action head, no graph replay): the chunk is one draw from the Laplace policy of that scale around the head's
+    prediction (predict_action(action_noise_scale=...)): exploration noise for collecting rollouts."""
     extra = dict(output_attentions=True) if return_attention else {}
+    if action_noise_scale is not None:
+        extra["action_noise_scale"] = action_noise_scale
     with torch.inference_mode():
         all_images = [obs["full_image"]]
         if cfg.num_images_in_input > 1:

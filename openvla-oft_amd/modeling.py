@@ -319,6 +319,16 @@ class SampledTokens(NamedTuple):
     entropy: torch.Tensor
 
 
+class SampledActions(NamedTuple):
+    """What a noisy L1 decode drew (predict_action / predict_action_batch with action_noise_scale, return_sample=True): device tensors in
+    NORMALISED action units -- the draw fp32 [B, chunk, action_dim], its log-probability per chunk step fp32 [B, chunk] under the Laplace
+    policy around the head's prediction, and that prediction bf16 [B, chunk, action_dim].  `actions[:, None]` / `logprobs[:, None]` are the
+    `actions` / `old_logprobs` of VLAEngine.train_step_action_pg_group."""
+    actions: torch.Tensor
+    logprobs: torch.Tensor
+    mean: torch.Tensor
+
+
 class ActionAttention:
     """What the rows that predict the action slots look at: the third element of predict_action / predict_action_batch with
     `output_attentions=True`.
@@ -745,6 +755,57 @@ class OpenVLAForActionPrediction(_StoreModule):
             words[0], words[1] = int(sample_seed) & 0xFFFFFFFF, (int(sample_seed) >> 32) & 0xFFFFFFFF
         return dict(temperature=float(temperature), window=self.engine.token_window("actions"), words=words, keys=rows, out={}, **group)
 
+    def _laplace_spec(self, action_noise_scale, sample_keys, B, *, action_head, noisy_action_projector=None, return_sample: bool = False):
+        """The `laplace` argument of _infer for a call with action_noise_scale (None otherwise): the per-dimension scale and the int32 key of
+        every chunk step -- observation key k_b (sample_keys[b], default b) gives k_b * chunk + c.  Everything is validated here and nothing
+        advances: _laplace_advance takes the generator's words once the call can no longer be refused."""
+        if action_noise_scale is None:
+            if return_sample:
+                raise ValueError("return_sample=True goes with action_noise_scale (the plain L1 decode draws nothing)")
+            return None
+        if action_head is None:
+            raise ValueError("action_noise_scale draws around an L1 head's prediction: pass action_head (the token path draws with do_sample=True)")
+        if noisy_action_projector is not None or hasattr(action_head, "noise_scheduler"):
+            raise ValueError("action_noise_scale is the L1 head's Laplace policy: a diffusion head has its own noise")
+        if self.use_graph:
+            raise ValueError("action_noise_scale is not supported under graph replay (the captured chunk holds no draw): enable_graph_replay(False)")
+        C = self.cfg.chunk
+        b, _ = ops.laplace_scales(action_noise_scale, self.cfg.action_dim)
+        if not bool(np.all((b > 0) & np.isfinite(b))):
+            raise ValueError(f"action_noise_scale = {action_noise_scale!r} (positive and finite)")
+        keys = torch.arange(B, dtype=torch.int64) if sample_keys is None else torch.as_tensor(np.asarray(sample_keys)).to(torch.int64).reshape(-1)
+        if keys.numel() != B:
+            raise ValueError(f"sample_keys: {keys.numel()} keys for {B} observations")
+        rows = (keys[:, None] * C + torch.arange(C, dtype=torch.int64)[None, :]).reshape(-1, 1) & 0xFFFFFFFF
+        rows = torch.where(rows >= 2 ** 31, rows - 2 ** 32, rows).to(torch.int32)
+        return dict(scale=b, keys=rows, out={})
+
+    def _laplace_advance(self, laplace, sample_seed):
+        """The generator's three words of this draw (the engine's token stream, advanced by one; `sample_seed` replaces its seed)."""
+        if laplace is not None:
+            st = self.engine.token_sample
+            words = st.words(st.advance())
+            if sample_seed is not None:
+                words[0], words[1] = int(sample_seed) & 0xFFFFFFFF, (int(sample_seed) >> 32) & 0xFFFFFFFF
+            laplace["words"] = words
+        return laplace
+
+    def _laplace_draw(self, pred, laplace):
+        """One ovla_laplace_sample launch around the head's prediction [B, chunk, action_dim] -> the draw, fp32 of the same shape."""
+        B, C, Ad = pred.shape
+        w = laplace["words"]
+        mean = pred.reshape(B * C, Ad).contiguous()
+        act, lp = ops.laplace_sample(mean, laplace["scale"], 1, seed=w[0] | (w[1] << 32), call=w[2], row_key=laplace["keys"].to(self.device))
+        laplace["out"].update(actions=act.view(B, C, Ad), logprobs=lp.view(B, C), mean=mean.view(B, C, Ad))
+        return laplace["out"]["actions"]
+
+    @staticmethod
+    def _sampled_actions(laplace, return_sample: bool) -> tuple:
+        if not return_sample:
+            return ()
+        o = laplace["out"]
+        return (SampledActions(o["actions"], o["logprobs"], o["mean"]),)
+
     def _decode(self, pred, bins, hidden, sample=None):
         """Normalised actions [B, chunk, action_dim] from whichever the forward produced: the head's prediction (:923-927); the bin indices, when
         the lm_head GEMM + ovla_argmax_bins ran inside a graph; otherwise the greedy token decode of the action hidden states (:929-942)."""
@@ -775,7 +836,7 @@ class OpenVLAForActionPrediction(_StoreModule):
         return normalized.reshape(hidden.shape[0], cfg.chunk, cfg.action_dim)
 
     def _infer(self, ids, mask, labels, pixel_values, prop, *, batch: bool, action_head=None, proprio_projector=None, noisy_action_projector=None,
-               noise=None, policy=None, attention: Optional[dict] = None, sample: Optional[dict] = None):
+               noise=None, policy=None, attention: Optional[dict] = None, sample: Optional[dict] = None, laplace: Optional[dict] = None):
         """The forward on prepared ids / mask / labels [B, L], the action rows, the head (L1, or the DDIM sampler from `noise`) or the token
         decode -> (normalised actions ndarray [B, chunk, action_dim], action hidden states [B, A, D] in a tensor of their own).
         `batch` is the mode.  False (predict_action): the planner's GEMM schedules, FiLM's average over all L positions, a graph per key.
@@ -785,7 +846,9 @@ class OpenVLAForActionPrediction(_StoreModule):
         `attention` (a dict to fill; output_attentions=True): the eager forward (routed with `policy`) with an AttnCapture of the action rows;
         self._graphs is neither used nor touched.  It receives the capture's `mean` [n_layers, B*A, S] and the sequence's P and S.
         `sample` (what _sample_spec returns; do_sample=True): the token decode draws instead of taking the maximum -- inside the batched
-        discrete graph, otherwise as the same launch after the forward -- and sample["out"] receives tokens / logprobs / entropy [B*A]."""
+        discrete graph, otherwise as the same launch after the forward -- and sample["out"] receives tokens / logprobs / entropy [B*A].
+        `laplace` (what _laplace_spec returns; action_noise_scale, the eager L1 path only): the actions are one Laplace draw around the head's
+        prediction (one ovla_laplace_sample launch after the head) and laplace["out"] receives actions / logprobs / mean."""
         cfg, eng = self.cfg, self.engine
         (B, L), A, D = ids.shape, cfg.num_action_tokens, cfg.llm_dim
         slots, heads, pps = policy if policy is not None else (None, None, None)
@@ -878,6 +941,8 @@ class OpenVLAForActionPrediction(_StoreModule):
                         pred = eng.policy_heads_fwd(ah, heads)
                     elif action_head is not None:
                         pred = action_head.predict_action(hidden)
+                        if laplace is not None:
+                            pred = self._laplace_draw(pred, laplace)
             normalized = cur.numpy() if use_diffusion else self._decode(pred, bins, hidden, sample)
         return normalized, hidden
 
@@ -921,11 +986,17 @@ class OpenVLAForActionPrediction(_StoreModule):
     @torch.no_grad()
     def predict_action(self, input_ids=None, unnorm_key=None, proprio=None, proprio_projector=None, action_head=None,
                        noisy_action_projector=None, use_film: bool = False, output_attentions: bool = False, do_sample: bool = False,
-                       temperature: float = 1.0, sample_seed: Optional[int] = None, sample_keys=None, return_tokens: bool = False, **kwargs):
+                       temperature: float = 1.0, sample_seed: Optional[int] = None, sample_keys=None, return_tokens: bool = False,
+                       action_noise_scale=None, return_sample: bool = False, **kwargs):
         """`do_sample=True` (the discrete token path only; ValueError with a head): the action tokens are DRAWN from softmax(logits[action ids] /
         temperature) on the device (ovla_sample_tokens) and the actions come from the drawn bins; `return_tokens=True` appends a SampledTokens.
         Every sampled call advances the engine's token stream by one; `sample_seed` replaces its seed for this call; `sample_keys` names the
-        observation's key in the generator (default 0).  With do_sample=False every launch is the one issued before."""
+        observation's key in the generator (default 0).  With do_sample=False every launch is the one issued before.
+        `action_noise_scale` (an L1 `action_head`, the eager path only; ValueError under graph replay, with a diffusion head or with no head,
+        before anything advances): the returned actions are ONE draw from the Laplace policy of that scale (a scalar or one value per action
+        dimension, normalised units) around the head's prediction (ovla_laplace_sample), un-normalised as always; `return_sample=True` appends a
+        SampledActions holding the normalised draw.  The call advances the engine's token stream by one; `sample_seed` / `sample_keys` as above.
+        With action_noise_scale=None every launch is the one issued before."""
         cfg = self.cfg
         if use_film != self.engine.use_film:
             raise ValueError(f"use_film={use_film} but the model was built with use_film={self.engine.use_film}")
@@ -945,13 +1016,16 @@ class OpenVLAForActionPrediction(_StoreModule):
         use_proprio = proprio_projector is not None and proprio is not None
         prop = torch.as_tensor(np.asarray(proprio), dtype=torch.float32) if use_proprio else None
         attention = {} if output_attentions else None   # -> a third result, an ActionAttention (the eager forward; no graph is used or built)
+        laplace = self._laplace_spec(action_noise_scale, sample_keys, 1, action_head=action_head, noisy_action_projector=noisy_action_projector,
+                                     return_sample=return_sample)
         sample = self._sample_spec(do_sample, temperature, sample_seed, sample_keys, 1, action_head is None, return_tokens)
         normalized, hidden = self._infer(ids, mask, labels, pixel_values, prop, batch=False, action_head=action_head, proprio_projector=proprio_projector,
-                                         noisy_action_projector=noisy_action_projector, noise=kwargs.get("noise"), attention=attention, sample=sample)
+                                         noisy_action_projector=noisy_action_projector, noise=kwargs.get("noise"), attention=attention, sample=sample,
+                                         laplace=self._laplace_advance(laplace, sample_seed))
         res = (self._unnormalize_actions(normalized[0], unnorm_key), hidden)
         if attention is not None:
             res += (self._action_attention(attention, mask, pixel_values, use_proprio),)
-        return res + self._sampled_tokens(sample, 1, return_tokens)
+        return res + self._sampled_tokens(sample, 1, return_tokens) + self._sampled_actions(laplace, return_sample)
 
     def _sampled_tokens(self, sample, B: int, return_tokens: bool) -> tuple:
         if not return_tokens:
@@ -975,7 +1049,8 @@ class OpenVLAForActionPrediction(_StoreModule):
     def predict_action_batch(self, prompts, pixel_values, unnorm_key=None, proprio=None, proprio_projector=None, action_head=None,
                              noisy_action_projector=None, use_film: bool = False, noise=None, pad_to: Optional[int] = None, policy=None,
                              output_attentions: bool = False, do_sample: bool = False, temperature: float = 1.0, sample_seed: Optional[int] = None,
-                             sample_keys=None, return_tokens: bool = False, num_samples: Optional[int] = None):
+                             sample_keys=None, return_tokens: bool = False, num_samples: Optional[int] = None, action_noise_scale=None,
+                             return_sample: bool = False):
         """predict_action for B observations in one forward.  prompts: list of B (input_ids, attention_mask) pairs ([1, L_b] or [L_b], lengths may
         differ; masks right-padded), pixel_values [B, 6 I, H, W], proprio [B, proprio_dim], noise [B, chunk, action_dim] (diffusion: each sample's
         DDIM trajectory starts from its own noise).  Returns (actions [B, chunk, action_dim] unnormalised with `unnorm_key`, action hidden states
@@ -1001,10 +1076,16 @@ class OpenVLAForActionPrediction(_StoreModule):
         `num_samples=G` (with do_sample=True, the eager path only): G draws per observation from the ONE forward (one ovla_sample_tokens_group
         launch): actions [B, G, chunk, action_dim], SampledTokens with tokens / logprobs [B, G, A] and entropy [B, A]; `sample_keys` [B, G]
         (default b * G + g) -- draw (b, g) is the num_samples=None draw of observation b under the key sample_keys[b, g].  Under graph replay it
-        raises: the captured decode holds one draw per observation."""
+        raises: the captured decode holds one draw per observation.
+        `action_noise_scale` (an L1 `action_head` without `policy`, the eager path only; ValueError otherwise, before anything advances): every
+        observation's actions are ONE draw from the Laplace policy of that scale around the head's prediction (one ovla_laplace_sample launch for
+        the batch); `sample_keys` [B] as above -- an observation draws the same chunk alone and in any batch under the same key and call.
+        `return_sample=True` appends a SampledActions.  The call advances the engine's token stream by one."""
         cfg = self.cfg
         if do_sample and policy is not None:
             raise ValueError("predict_action_batch(do_sample=True) is not supported with per-request policies")
+        if action_noise_scale is not None and policy is not None:
+            raise ValueError("predict_action_batch(action_noise_scale=...) is not supported with per-request policies")
         if num_samples is not None and self.use_graph:
             raise ValueError("predict_action_batch(num_samples=...) is not supported under graph replay (the captured decode draws once per "
                              "observation): enable_graph_replay(False), or call it once per draw with sample_keys")
@@ -1051,8 +1132,13 @@ class OpenVLAForActionPrediction(_StoreModule):
                                             noise=rep(noise), policy=None if policy is None else policy + [policy[0]] * len(fill),
                                             output_attentions=output_attentions, do_sample=do_sample, temperature=temperature, sample_seed=sample_seed,
                                             sample_keys=None if sample_keys is None else list(sample_keys) + [list(sample_keys)[0]] * len(fill),
-                                            return_tokens=return_tokens, num_samples=num_samples)
-            tail = (SampledTokens(*(t[:B] for t in res[-1])),) if return_tokens else ()
+                                            return_tokens=return_tokens, num_samples=num_samples, action_noise_scale=action_noise_scale,
+                                            return_sample=return_sample)
+            tail = ()
+            if return_sample:
+                tail, res = (SampledActions(*(t[:B] for t in res[-1])),), res[:-1]
+            if return_tokens:
+                tail = (SampledTokens(*(t[:B] for t in res[-1])),) + tail
             if output_attentions:
                 att = res[2]
                 return (res[0][:B], res[1][:B], ActionAttention(att.mean[:, :B], att.layout[:B], att.patches_per_image)) + tail
@@ -1090,7 +1176,10 @@ class OpenVLAForActionPrediction(_StoreModule):
             labels[b, len(r) - 1] = STOP_INDEX
         attention = {} if output_attentions else None
         extra = (lambda: (self._action_attention(attention, mask, pixel_values, use_proprio),)) if output_attentions else (lambda: ())
+        laplace = self._laplace_spec(action_noise_scale, sample_keys, B, action_head=action_head, noisy_action_projector=noisy_action_projector,
+                                     return_sample=return_sample)
         sample = self._sample_spec(do_sample, temperature, sample_seed, sample_keys, B, action_head is None and policy is None, return_tokens, num_samples)
+        laplace = self._laplace_advance(laplace, sample_seed)
         if policy is not None and self._pool_resident:
             normalized, hidden = self._infer_pooled(ids, mask, labels, pixel_values, prop, policy, use_proprio, attention=attention)
             stats = [self.policy_norm_stats(p) for p in policy]
@@ -1105,8 +1194,9 @@ class OpenVLAForActionPrediction(_StoreModule):
             stats = [self.policy_norm_stats(p) for p in policy]
             return (np.stack([self._unnormalize_actions(normalized[b], unnorm_key, stats[b]) for b in range(B)]), hidden) + extra()
         normalized, hidden = self._infer(ids, mask, labels, pixel_values, prop, batch=True, action_head=action_head, proprio_projector=proprio_projector,
-                                         noisy_action_projector=noisy_action_projector, noise=noise, attention=attention, sample=sample)
-        return (np.stack([self._unnormalize_actions(normalized[b], unnorm_key) for b in range(B)]), hidden) + extra() + self._sampled_tokens(sample, B, return_tokens)
+                                         noisy_action_projector=noisy_action_projector, noise=noise, attention=attention, sample=sample, laplace=laplace)
+        return ((np.stack([self._unnormalize_actions(normalized[b], unnorm_key) for b in range(B)]), hidden) + extra() + self._sampled_tokens(sample, B, return_tokens)
+                + self._sampled_actions(laplace, return_sample))
 
     # -- statistics (:772-791, :1062-1087) -------------------------------------------------------------------------------
     @staticmethod

@@ -8,6 +8,7 @@ import contextlib
 import ctypes
 import threading
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1147,6 +1148,89 @@ def token_pg_group(logits, tokens, advantage, *, vocab=None, window=None, temper
     g.rows, g.G, g.vocab, g.lo, g.hi = rows, G, vocab, lo, hi
     _lib.call("ovla_token_pg_group", g, _stream())
     return logprob, ratio, clipped, kl, entropy, d
+
+
+LAPLACE_MAX_ADIM = 16      # ovla.h "Laplace policy on the L1 head": 1 <= adim <= 16
+
+
+def laplace_scales(scale, adim):
+    """A scalar or per-dimension scale b -> (b fp32 [adim], log_norm fp32 [adim] = float32(log(2 b)) formed in double), numpy arrays: the by-value
+    arguments of the two Laplace kernels.  The kernels refuse a scale that is not positive and finite."""
+    b = np.asarray(scale.detach().cpu().numpy() if torch.is_tensor(scale) else scale, dtype=np.float64).reshape(-1)
+    if b.size == 1:
+        b = np.repeat(b, adim)
+    if b.size != adim:
+        raise ValueError(f"scale: {b.size} values for {adim} action dimensions (a scalar or one per dimension)")
+    b32 = b.astype(np.float32)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        log_norm = np.log(2.0 * b32.astype(np.float64)).astype(np.float32)
+    return b32, log_norm
+
+
+def _set_laplace_scales(g, scale, adim):
+    b, ln = laplace_scales(scale, adim)
+    for d in range(adim):
+        g.scale[d], g.log_norm[d] = float(b[d]), float(ln[d])
+
+
+def laplace_sample(pred, scale, G=1, *, seed=0, call=0, state_dev=None, row_key=None, action=None, logprob=None):
+    """G Laplace draws per row around the L1 head's prediction (ovla.h "Laplace policy on the L1 head": ovla_laplace_sample): pred bf16 [rows, adim],
+    scale a scalar or [adim] -> (action fp32 [rows, G, adim], logprob fp32 [rows, G]), a pure function of (seed, call, row key, dimension) and the
+    prediction.  `row_key` int32 [rows, G] replaces r * G + g in the generator's counter; `state_dev` as in sample_tokens."""
+    _chk(pred, name="pred")
+    assert pred.dim() == 2 and pred.is_contiguous()
+    (rows, adim), dev, G = pred.shape, pred.device, int(G)
+    action = torch.empty((rows, G, adim), dtype=torch.float32, device=dev) if action is None else action
+    logprob = torch.empty((rows, G), dtype=torch.float32, device=dev) if logprob is None else logprob
+    for t, dt, name, n in ((action, torch.float32, "action", rows * G * adim), (logprob, torch.float32, "logprob", rows * G), (row_key, torch.int32, "row_key", rows * G)):
+        if t is not None:
+            _chk(t, dt, name)
+            assert t.numel() == n and t.is_contiguous(), f"{name}: expected {n} contiguous elements"
+    if state_dev is not None:
+        assert state_dev.is_cuda and state_dev.numel() == 3 and state_dev.is_contiguous() and state_dev.element_size() == 4 and not state_dev.is_floating_point(), \
+            "state_dev: three 32-bit integers on the device (seed_lo, seed_hi, call)"
+    g = STRUCTS["ovla_laplace_sample_args"]()
+    g.pred, g.action, g.logprob, g.state_dev, g.row_key = pred.data_ptr(), action.data_ptr(), logprob.data_ptr(), _p(state_dev), _p(row_key)
+    g.seed_lo, g.seed_hi, g.call = int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF, int(call) & 0xFFFFFFFF
+    g.rows, g.adim, g.G = rows, adim, G
+    if 1 <= adim <= LAPLACE_MAX_ADIM:                      # (otherwise the kernel's own refusal speaks)
+        _set_laplace_scales(g, scale, adim)
+    _lib.call("ovla_laplace_sample", g, _stream())
+    return action, logprob
+
+
+def laplace_pg(pred, actions, advantage, scale, *, old_logprob=None, ref_pred=None, kl_coef=0.0, clip=(0.8, 1.2), grad_scale=None, kl_scale=0.0, dpred=None,
+               logprob=None, ratio=None, clipped=None, kl=None):
+    """Clipped policy-gradient objective and closed-form KL of the Laplace policy on G given draws per row (ovla.h: ovla_laplace_pg): pred bf16
+    [rows, adim], actions fp32 [rows, G, adim], advantage fp32 [rows, G] (and old_logprob fp32 [rows, G], ref_pred bf16 [rows, adim]) on the device
+    -> (logprob, ratio fp32 [rows, G], clipped int32 [rows, G], kl fp32 [rows] or None, dpred bf16 [rows, adim] or None).  `kl` exists exactly when
+    ref_pred is given; with grad_scale the gradient with respect to pred goes to `dpred` (a new tensor without one)."""
+    _chk(pred, name="pred")
+    assert pred.dim() == 2 and pred.is_contiguous() and actions.dim() == 3 and actions.shape[0] == pred.shape[0] and actions.shape[2] == pred.shape[1]
+    (rows, adim), dev, G = pred.shape, pred.device, actions.shape[1]
+    logprob = torch.empty((rows, G), dtype=torch.float32, device=dev) if logprob is None else logprob
+    ratio = torch.empty((rows, G), dtype=torch.float32, device=dev) if ratio is None else ratio
+    clipped = torch.empty((rows, G), dtype=torch.int32, device=dev) if clipped is None else clipped
+    if kl is None and ref_pred is not None:
+        kl = torch.empty(rows, dtype=torch.float32, device=dev)
+    if grad_scale is not None and dpred is None:
+        dpred = torch.empty((rows, adim), dtype=BF16, device=dev)
+    for t, dt, name, n in ((actions, torch.float32, "actions", rows * G * adim), (advantage, torch.float32, "advantage", rows * G),
+                           (old_logprob, torch.float32, "old_logprob", rows * G), (ref_pred, BF16, "ref_pred", rows * adim),
+                           (logprob, torch.float32, "logprob", rows * G), (ratio, torch.float32, "ratio", rows * G), (clipped, torch.int32, "clipped", rows * G),
+                           (kl, torch.float32, "kl", rows), (dpred, BF16, "dpred", rows * adim)):
+        if t is not None:
+            _chk(t, dt, name)
+            assert t.numel() == n and t.is_contiguous(), f"{name}: expected {n} contiguous elements"
+    g = STRUCTS["ovla_laplace_pg_args"]()
+    g.pred, g.ref_pred, g.actions, g.advantage, g.old_logprob = pred.data_ptr(), _p(ref_pred), actions.data_ptr(), advantage.data_ptr(), _p(old_logprob)
+    g.logprob, g.ratio, g.clipped, g.kl, g.dpred = logprob.data_ptr(), ratio.data_ptr(), clipped.data_ptr(), _p(kl), _p(dpred)
+    g.clip_lo, g.clip_hi, g.grad_scale, g.kl_coef, g.kl_scale = float(clip[0]), float(clip[1]), float(grad_scale or 0.0), float(kl_coef), float(kl_scale)
+    g.rows, g.adim, g.G = rows, adim, G
+    if 1 <= adim <= LAPLACE_MAX_ADIM:
+        _set_laplace_scales(g, scale, adim)
+    _lib.call("ovla_laplace_pg", g, _stream())
+    return logprob, ratio, clipped, kl, dpred
 
 
 def _chk_step(step):
