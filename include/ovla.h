@@ -1046,6 +1046,71 @@ typedef struct {
 } ovla_laplace_pg_args;
 int ovla_laplace_pg(const ovla_laplace_pg_args* a, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Laplace policy with a learned scale (the fixed-scale pair above with the scale per chunk step and action dimension: a scale head predicts
+ * s = log b beside the L1 head's mu; maximum likelihood fits it on demonstrations, the policy gradient moves mu and s together, the
+ * closed-form KL to a frozen reference of its own scale and an entropy bonus keep it in place).  ovla_laplace_sample_rows is
+ * ovla_laplace_sample with the scale per element; ovla_laplace_pg_rows is ovla_laplace_pg with the scale per element, the gradient with
+ * respect to s, the KL between two Laplace distributions of different scale, and the entropy.  Everything of "Laplace policy on the L1 head"
+ * carries over: pred bf16 [rows, adim], 1 <= adim <= 16, 1 <= G <= OVLA_PG_GROUP_MAX; stream-ordered, capturable, no atomics, no workspace;
+ * every operator one rounded fp32 operation in the bracketing written, no FMA contraction; a row's bits depend on its own inputs and keys
+ * only.  THE CONTRACT (identical in csrc/laplace_scale.hip and in the numpy restatement tests/laplace_scale_reference.py):
+ * log_scale (s) bf16 [rows, adim], the scale head's raw output; s_lo <= s_hi finite floats by value.  Per element
+ *   s_c      = fminf(fmaxf(s, s_lo), s_hi)            (a NaN s acts as s_lo)
+ *   inside   = (s >= s_lo && s <= s_hi)               (false for NaN)
+ *   b        = expf(s_c) (accurate expf);  inv_b = 1.0f / b (IEEE division);  log_norm = s_c + LN2F, LN2F = float32(ln 2) = 0x1.62e43p-1f
+ * Where s_c == 0: b = inv_b = 1, log_norm = LN2F -- what the fixed-scale kernels are handed for scale 1.
+ *
+ * ovla_laplace_sample_rows: generator, uniform, variate, noise, state_dev and the default keys r * G + g exactly as ovla_laplace_sample (the
+ * SAME stream word 4: the same noise at another width).  a_d = mu_d + b_{r,d} * e, stored;  logprob: acc = 0;  acc = acc - (fabsf(a_d - mu_d)
+ * * inv_b + log_norm) for ascending d, from the STORED a_d.  entropy fp32 [rows] (optional): the entropy below, stored by the row's draw
+ * g = 0.  With log_scale == 0 everywhere: ovla_laplace_sample's bits at scale 1.
+ *
+ * ovla_laplace_pg_rows: G GIVEN samples per row, one workgroup of 64 lanes per row.  Inputs as ovla_laplace_pg, and log_scale; ref_pred
+ * and ref_log_scale bf16 [rows, adim] and the output kl fp32 [rows] come all three or not at all.  Outputs logprob / ratio fp32, clipped
+ * int32 [rows, G]; entropy fp32 [rows] (always); dpred, dlog_scale bf16 [rows, adim] (each optional, independently).
+ * Per sample g: logprob_g as above; ratio_g, gate_g, clipped_g and c_g = (adv_g * gate_g) * grad_scale by ovla_laplace_pg's rules: c_g is
+ * +0 (set, not multiplied) for a gated sample and for adv_g == 0, such a sample is SKIPPED and its actions are not read for any gradient.
+ * Per (r, d), with q_g = fabsf(a_{g,d} - mu_d) * inv_b, over the samples not skipped in ascending g, the first term taken as it is, each
+ * further term one rounded fp32 add, +0 when every sample is skipped:
+ *   acc_mu = sum of (sgn(mu_d - a_{g,d}) * inv_b) * c_g                                  (ovla_laplace_pg's sum)
+ *   acc_s  = sum of (1.0f - q_g) * c_g                                                   (d(-c logprob)/ds: d logprob / d s = q - 1)
+ * with a reference (s_rc: ref_log_scale clamped by the same bounds):
+ *   u = s_c - s_rc;  D = mu_d - ref_d;  q = fabsf(D) * inv_b;  x = -expm1f(-q);  rho = expf(u)      (accurate expm1f, expf)
+ *   kl_d   = (expm1f(u) - u) + rho * (q - x)         KL(Laplace(mu, b) || Laplace(ref, b_ref)) of the dimension;  kl[r] = kl_0 + kl_1 + ...
+ *   acc_mu = acc_mu + (((kl_coef * x) * kl_scale) * (sgn(D) * inv_b)) * rho              (d kl_d / d mu = sgn(D) x inv_b rho)
+ *   acc_s  = acc_s + (kl_coef * kl_scale) * (((rho * (1.0f - x)) * (1.0f + q)) - 1.0f)   (d kl_d / d s = rho (1 - x)(1 + q) - 1)
+ *   added after the sample sum and not gated.  At equal scales (u = 0, rho = 1) kl_d and the mean's term are ovla_laplace_pg's bits; on
+ *   policy (u = 0, D = 0) kl_d and both gradient terms are exactly +0.
+ * entropy[r] = (1.0f + log_norm_0) + (1.0f + log_norm_1) + ... in ascending d (the Laplace entropy; it does not depend on mu); the loss
+ * carries -entropy_coef * ent_scale * entropy[r]:
+ *   if entropy_coef != 0:  acc_s = acc_s - (entropy_coef * ent_scale), last.
+ * dpred[r, d] = bf16(acc_mu);  dlog_scale[r, d] = inside ? bf16(acc_s) : +0  (a clamped or NaN log-scale takes no gradient from any term).
+ * The gradient with respect to (mu, s) of  sum_{r,g} -min(ratio A, clip(ratio) A) * grad_scale  +  kl_coef * kl_scale * sum_r kl[r]
+ * - entropy_coef * ent_scale * sum_r entropy[r].  With G = 1, adv = 1, no old_logprob, no reference and entropy_coef = 0 it is the gradient
+ * of the Laplace negative log-likelihood of a target chunk: dlog_scale = bf16((1 - q) * grad_scale), dpred the L1 gradient divided by b.
+ * Refusals (OVLA_EINVAL, nothing launched): those of the fixed-scale pair; a null log_scale; s_lo > s_hi or a bound that is not finite;
+ * ref_pred / ref_log_scale / kl not all given or all absent; a null entropy (ovla_laplace_pg_rows); entropy_coef negative or NaN. */
+typedef struct {
+  const void* pred; const void* log_scale;
+  float* action; float* logprob; float* entropy;
+  const uint32_t* state_dev; const int32_t* row_key;
+  uint32_t seed_lo, seed_hi, call;
+  float s_lo, s_hi;
+  int32_t rows, adim, G;
+} ovla_laplace_sample_rows_args;
+int ovla_laplace_sample_rows(const ovla_laplace_sample_rows_args* a, void* stream);
+
+typedef struct {
+  const void* pred; const void* log_scale; const void* ref_pred; const void* ref_log_scale;
+  const float* actions; const float* advantage; const float* old_logprob;
+  float* logprob; float* ratio; int32_t* clipped; float* kl; float* entropy;
+  void* dpred; void* dlog_scale;
+  float s_lo, s_hi, clip_lo, clip_hi, grad_scale, kl_coef, kl_scale, entropy_coef, ent_scale;
+  int32_t rows, adim, G;
+} ovla_laplace_pg_rows_args;
+int ovla_laplace_pg_rows(const ovla_laplace_pg_rows_args* a, void* stream);
+
 /* fp32 -> bf16 convert with scale (publishes .grad views), and fill */
 typedef struct { const float* src; void* dst; int64_t n; float scale; } ovla_cvt_args;
 int ovla_cvt_f32_to_bf16(const ovla_cvt_args* a, void* stream);

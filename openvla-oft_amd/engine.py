@@ -22,6 +22,7 @@ from typing import Any, Dict, List, NamedTuple, Optional, Tuple
 
 import os
 
+import numpy as np
 import torch
 
 from . import _lib, ops
@@ -1115,9 +1116,10 @@ class ActionHead:
         for b in self.blocks:
             yield from (b["ln_w"], b["ln_b"])
 
-    def fwd(self, actions_hidden, target=None, mse=False, train=False):
+    def fwd(self, actions_hidden, target=None, mse=False, train=False, return_hidden=False):
         """actions_hidden bf16 [B*A_tokens, D] (row-major (b, token)) == reshape(B, chunk, action_dim*D).
-        Returns (pred [B*chunk, action_dim], loss_sum fp32[1] or None, saved)."""
+        Returns (pred [B*chunk, action_dim], loss_sum fp32[1] or None, saved); with `return_hidden` also the post-layer_norm2 activations
+        bf16 [B*chunk, D] the output layer reads (what ActionScaleHead takes; in training mode a view of what `saved` holds anyway)."""
         cfg = self.cfg
         rows = actions_hidden.shape[0] // cfg.action_dim
         x0 = actions_hidden.view(rows, cfg.action_dim * cfg.llm_dim)
@@ -1143,6 +1145,8 @@ class ActionHead:
         loss_sum = torch.zeros(1, dtype=F32, device=x0.device) if target is not None else None
         pred = ops.head_out_fwd(h2[:rows_real], self.out_w.data, self.out_b.data, target, loss_sum, mse=mse)
         saved = (x0, m0, r0, z1, s1, blocks_saved, x, m2, r2, h2, pred, target, mse, rows_real) if train else None
+        if return_hidden:
+            return pred, loss_sum, saved, h2[:rows_real]
         return pred, loss_sum, saved
 
     def check_fused_tail(self):   # bench.py still calls this after its timed steps; it goes when that call does
@@ -1170,6 +1174,39 @@ class ActionHead:
         dh0 = self.fc1.bwd(dz1, s1)
         dx0 = ops.norm_bwd(x0, dh0, self.ln1_w.data, m0, r0, rms=False, dweight=self.ln1_w.grad, dbias=self.ln1_b.grad)
         return dx0[:rows_real].reshape(rows_real * cfg.action_dim, cfg.llm_dim)
+
+
+class ActionScaleHead:
+    """The learned Laplace scale of the L1 head (ovla.h "Laplace policy with a learned scale"): one linear map on the head's post-layer_norm2
+    activations h2 [rows, llm_dim] -> the log-scale s bf16 [rows, action_dim], beside the head's own output layer.  Its gradient STOPS at h2:
+    the backward forms dW and db and discards dx, so the mean's path keeps the bits it has without a scale head."""
+
+    def __init__(self, store, get, prefix: str, cfg: VLAConfig):
+        self.cfg, self.prefix = cfg, prefix
+        self.w = store.add(prefix + "log_scale.weight", get(prefix + "log_scale.weight"))
+        self.b = store.add(prefix + "log_scale.bias", get(prefix + "log_scale.bias"))
+
+    def linears(self):
+        return ()
+
+    def plain_params(self):
+        yield from (self.w, self.b)
+
+    def fwd(self, h2):
+        return ops.head_out_fwd(h2, self.w.data, self.b.data)
+
+    def bwd(self, h2, dlog_scale):
+        ops.head_out_bwd(h2, self.w.data, None, None, 0.0, self.w.grad, self.b.grad, dpred=dlog_scale)   # (dx is dropped: the gradient stops at h2)
+
+    @staticmethod
+    def init_tensors(cfg: VLAConfig, init_scale, device, prefix: str = "action_scale_head.") -> Dict[str, torch.Tensor]:
+        """weight 0, bias log(b0) (b0 a scalar or one value per action dimension): exactly the fixed-scale policy of scale b0, up to the bias's
+        bf16 rounding."""
+        b0, _ = ops.laplace_scales(init_scale, cfg.action_dim)
+        if not bool(np.all((b0 > 0) & np.isfinite(b0))):
+            raise ValueError(f"init_scale = {init_scale}: positive and finite")
+        return {prefix + "log_scale.weight": torch.zeros((cfg.action_dim, cfg.llm_dim), dtype=BF16, device=device),
+                prefix + "log_scale.bias": torch.from_numpy(np.log(b0.astype(np.float64)).astype(np.float32)).to(device, BF16)}
 
 
 class MlpProjector:
@@ -1298,7 +1335,51 @@ class VLAEngine:
 
     @property
     def stores(self):
-        return [self.store] + [m.store for m in (self.proprio, self.noisy, self.head) if m is not None]
+        return [self.store] + [m.store for m in (self.proprio, self.noisy, self.head, self.scale_head) if m is not None]
+
+    # -- the learned Laplace scale of the L1 head (ActionScaleHead): opt-in, a store of its own -----------------------------------------------------
+    scale_head: Optional["ActionScaleHead"] = None
+    scale_bounds: Tuple[float, float] = ops.LAPLACE_SCALE_BOUNDS
+
+    def attach_scale_head(self, init_scale=0.1, bounds=ops.LAPLACE_SCALE_BOUNDS, state_dict: Optional[Dict[str, torch.Tensor]] = None):
+        """Attaches the scale head: weight 0 and bias log(init_scale) (or `state_dict`'s `action_scale_head.log_scale.{weight, bias}`), its
+        log-scale clamped to `bounds` by the kernels (the default, b in about [0.0025, 2.7] normalised units, is a design choice).  Its store joins
+        `stores`: zero_grad, adamw_step, export_trainable / load_trainable, the optimizer-state dict see it like the head's.  The clip slots, the
+        tensor-statistics tables, the EMA shadows, fp32 optimizer state, the reference snapshot and a reducer enumerate `stores` when they are
+        enabled, so this comes BEFORE any of them (RuntimeError otherwise).  Needs head='l1'."""
+        self._l1_head("attach_scale_head")
+        self._not_in_ema_scope("attach_scale_head")
+        if self.scale_head is not None:
+            raise RuntimeError("attach_scale_head: a scale head is attached already")
+        late = [what for what, on in (("enable_grad_clip", self._grad_clip is not None), ("enable_tensor_stats", self._tensor_stats is not None),
+                                      ("enable_ema", self.ema_enabled), ("enable_fp32_optimizer_state", self.store.fp32_state),
+                                      ("set_reference_policy", self._reference is not None), ("attach_reducer", getattr(self, "reducer", None) is not None)) if on]
+        if late:
+            raise RuntimeError(f"attach_scale_head after {', '.join(late)}: they enumerate the stores when they are enabled; attach the scale head first")
+        lo, hi = float(bounds[0]), float(bounds[1])
+        if not (math.isfinite(lo) and math.isfinite(hi) and lo <= hi):
+            raise ValueError(f"bounds = {bounds}: two finite log-scales, lo <= hi")
+        prefix = "action_scale_head."
+        sd = ActionScaleHead.init_tensors(self.cfg, init_scale, self.device, prefix)
+        if state_dict is not None:
+            for k, v in sd.items():
+                src = state_dict[k] if k in state_dict else state_dict[k[len(prefix):]]
+                if tuple(src.shape) != tuple(v.shape):
+                    raise ValueError(f"{k}: shape {tuple(src.shape)} != {tuple(v.shape)}")
+                sd[k] = src.to(self.device, BF16)
+        self.scale_head = build_component(ActionScaleHead, self.device, sd.__getitem__, prefix, cfg=self.cfg)
+        self.scale_bounds = (lo, hi)
+        return self.scale_head
+
+    def _learned(self, scale, who: str) -> bool:
+        """True for scale == "learned" (ValueError without a scale head); a numeric scale takes the fixed-scale code whether or not one is attached."""
+        if not isinstance(scale, str):
+            return False
+        if scale != "learned":
+            raise ValueError(f'{who}: scale = {scale!r} (a number, one per action dimension, or "learned")')
+        if self.scale_head is None:
+            raise ValueError(f'{who}: scale="learned" needs attach_scale_head()')
+        return True
 
     def zero_grad(self):
         for st in self.stores:
@@ -1790,6 +1871,9 @@ class VLAEngine:
         if self.head is not None:
             for p in self.head.plain_params():
                 out[p.name] = getattr(p, kind)
+        if self.scale_head is not None:
+            for p in self.scale_head.plain_params():
+                out[p.name] = getattr(p, kind)
         return out
 
     def load_trainable(self, sd: Dict[str, torch.Tensor], strict: bool = True) -> List[str]:
@@ -2215,14 +2299,23 @@ class VLAEngine:
         self.llm.on_grads_ready = llm_layer_done
 
     def train_step_fwd_bwd(self, batch: dict, loss_scale: float = 1.0, action_head=None, proprio_projector=None, diffusion=None,
-                           noisy_action_projector=None, film_avg=None, attn_capture=None):
+                           noisy_action_projector=None, film_avg=None, attn_capture=None, fit_scale: bool = False):
         """One run_forward_pass (finetune.py:280-451) + backward.  L1 branch by default; with
         `diffusion = dict(noise, noisy_actions, timestep_emb)` the noise-prediction MSE branch (:402-407).
         Gradients accumulate in the flat buffers.  `film_avg` (what language_average returns) replaces the FiLM conditioning vector the forward
         would compute from the batch's own ids.  `attn_capture` (an AttnCapture): filled by the step's forward (read its result() afterwards); loss and
-        gradients keep their bits.  Returns (loss_sum fp32[1] device, element count, predictions)."""
+        gradients keep their bits.  Returns (loss_sum fp32[1] device, element count, predictions).
+        `fit_scale` (L1 only, attach_scale_head): after the L1 backward, the maximum-likelihood side step of the scale head on the step's own
+        hidden output and predictions (_nll_of_target: three launches into the scale head's store alone; its dict(nll, scale) is left in
+        `self.last_scale_fit`).  The L1 step's loss, predictions and every other gradient accumulator keep their bits."""
         self._not_in_ema_scope("train_step_fwd_bwd")
+        if fit_scale:
+            if diffusion is not None or self.head_kind != "l1":
+                raise ValueError("fit_scale fits the Laplace scale of the L1 head: not with a diffusion objective")
+            self._learned("learned", "train_step_fwd_bwd(fit_scale=True)")
         extra = {} if attn_capture is None else dict(attn_capture=attn_capture)
+        if fit_scale:
+            extra["fit_scale"] = True
         return self._head_step(batch, diffusion, action_head if action_head is not None else self.head, loss_scale,
                                proprio_projector=proprio_projector, noisy_action_projector=noisy_action_projector, film_avg=film_avg, **extra)
 
@@ -2233,9 +2326,12 @@ class VLAEngine:
             return self.train_step_discrete(batch, backward=False)
         return self._head_step(batch, diffusion, self.head, None)
 
-    def _head_step(self, batch: dict, diffusion, head, loss_scale: Optional[float], noisy_action_projector=None, **fwd_kw):
+    last_scale_fit: Optional[Dict[str, torch.Tensor]] = None   # dict(nll, scale) of the last train_step_fwd_bwd(fit_scale=True), device scalars
+
+    def _head_step(self, batch: dict, diffusion, head, loss_scale: Optional[float], noisy_action_projector=None, fit_scale: bool = False, **fwd_kw):
         """The L1 / noise-prediction MSE objective of one batch: the forward on the action rows, the head and its loss; with a `loss_scale`
-        (the training step) also the backward of both.  -> (loss_sum fp32[1] device, element count, predictions)."""
+        (the training step) also the backward of both, and with `fit_scale` the scale head's side step after them.
+        -> (loss_sum fp32[1] device, element count, predictions)."""
         cfg, train = self.cfg, loss_scale is not None
         if diffusion is not None:
             fwd_kw.update(noisy_actions=diffusion["noisy_actions"], timestep_emb=diffusion["timestep_emb"], noisy_action_projector=noisy_action_projector)
@@ -2244,13 +2340,19 @@ class VLAEngine:
         ah, idx = self.action_hidden(out)
         tgt_src = diffusion["noise"] if diffusion is not None else batch["actions"]
         target = tgt_src.to(self.device, BF16).reshape(batch["input_ids"].shape[0] * cfg.chunk, cfg.action_dim).contiguous()
-        pred, loss_sum, hsaved = head.fwd(ah, target=target, mse=diffusion is not None, train=train)
+        if fit_scale:
+            pred, loss_sum, hsaved, h2 = head.fwd(ah, target=target, mse=False, train=train, return_hidden=True)
+        else:
+            pred, loss_sum, hsaved = head.fwd(ah, target=target, mse=diffusion is not None, train=train)
         if train:
             dah = head.bwd(hsaved, dloss=loss_scale)
             if getattr(self, "_overlap", False) and hasattr(head, "store"):
                 for dt, g in head.store.flat_grad.items():
                     self.reducer.notify(head.store, dt, g.numel())
             self.backward_from_rows(dah, idx, out)
+            if fit_scale:
+                with torch.no_grad():
+                    self.last_scale_fit = self._nll_of_target(pred, h2, target, loss_scale)
         return loss_sum, pred.numel(), pred
 
     # -- the diffusion objective on the device ------------------------------------------------------------------------------
@@ -2604,14 +2706,18 @@ class VLAEngine:
             raise RuntimeError(f"{who} needs an engine built with head='l1' (the Laplace policy is the L1 head's; this one has head={self.head_kind!r})")
         return action_head if action_head is not None else self.head
 
-    def _action_means(self, batch: dict, train: bool, head, proprio_projector=None):
-        """The forward on the action rows and the L1 head on them -> (out, rows_idx, pred bf16 [B * chunk, action_dim], the head's saved state)."""
+    def _action_means(self, batch: dict, train: bool, head, proprio_projector=None, learned: bool = False):
+        """The forward on the action rows and the L1 head on them -> (out, rows_idx, pred bf16 [B * chunk, action_dim], the head's saved state);
+        with `learned` also (h2, log_scale): the head's post-layer_norm2 activations and the scale head's output bf16 [B * chunk, action_dim]."""
         kw = {} if proprio_projector is None else dict(proprio_projector=proprio_projector)
         out = self.forward(batch["input_ids"], batch["attention_mask"], batch["pixel_values"], batch["labels"], proprio=batch.get("proprio"),
                            train=train, sel="actions", **kw)
         ah, idx = self.action_hidden(out)
-        pred, _, hsaved = head.fwd(ah, train=train)
-        return out, idx, pred, hsaved
+        if not learned:
+            pred, _, hsaved = head.fwd(ah, train=train)
+            return out, idx, pred, hsaved
+        pred, _, hsaved, h2 = head.fwd(ah, train=train, return_hidden=True)
+        return out, idx, pred, hsaved, h2, self.scale_head.fwd(h2)
 
     def _chunk_rows(self, t, dtype, B: int, G: int, what: str, per_draw: bool = False, per_dim: bool = False):
         """A per-step [B, G, chunk] (with `per_draw` also per-draw [B, G]; with `per_dim` [B, G, chunk, action_dim]) host or device tensor ->
@@ -2639,28 +2745,40 @@ class VLAEngine:
         in normalised action units) around the L1 head's prediction: one forward (inference mode) on the action rows, the head, ONE
         ovla_laplace_sample launch; nothing is read back.  Advances the token stream's `call` by one.  `row_keys` int32 [B, G] (observation draw
         key k gives its step c the generator key k * chunk + c; default b * G + g) or [B, G, chunk]: a draw does not depend on its position.
-        -> dict(actions fp32 [B, G, chunk, action_dim], logprob fp32 [B, G, chunk], mean bf16 [B, chunk, action_dim]) on the device."""
+        -> dict(actions fp32 [B, G, chunk, action_dim], logprob fp32 [B, G, chunk], mean bf16 [B, chunk, action_dim]) on the device.
+        scale="learned" (attach_scale_head): the widths are the scale head's, per chunk step and dimension -- the head with its hidden output,
+        the scale head, ONE ovla_laplace_sample_rows launch; the dict gains log_scale bf16 [B, chunk, action_dim] (the raw, unclamped output) and
+        entropy fp32 [B, chunk]."""
         head = self._l1_head("sample_actions_laplace")
+        learned = self._learned(scale, "sample_actions_laplace")
         cfg, B, G = self.cfg, batch["input_ids"].shape[0], int(num_samples)
         C = cfg.chunk
         if not 1 <= G <= ops.PG_GROUP_MAX:
             raise ValueError(f"num_samples = {G} (1 .. {ops.PG_GROUP_MAX})")
-        ops.laplace_scales(scale, cfg.action_dim)                # (raises before anything advances)
+        if not learned:
+            ops.laplace_scales(scale, cfg.action_dim)            # (raises before anything advances)
         keys = torch.arange(B * G, dtype=torch.int32, device=self.device).view(B, G) if row_keys is None else torch.as_tensor(row_keys).to(self.device, torch.int32)
         if tuple(keys.shape) == (B, G):
             keys = keys.reshape(B, G, 1) * C + torch.arange(C, dtype=torch.int32, device=self.device)[None, None, :]
         keys = self._chunk_rows(keys, torch.int32, B, G, "row_keys")
         with torch.no_grad():
-            _, _, pred, _ = self._action_means(batch, False, head)
             st = self.token_sample
+            if learned:
+                _, _, pred, _, _, ls = self._action_means(batch, False, head, learned=True)
+                act, lp, ent = ops.laplace_sample_rows(pred, ls, self.scale_bounds, G, seed=st.seed, call=st.advance(), row_key=keys)
+                return dict(actions=self._chunk_out(act, B, G), logprob=self._chunk_out(lp, B, G), mean=pred.view(B, C, cfg.action_dim),
+                            log_scale=ls.view(B, C, cfg.action_dim), entropy=ent.view(B, C))
+            _, _, pred, _ = self._action_means(batch, False, head)
             act, lp = ops.laplace_sample(pred, scale, G, seed=st.seed, call=st.advance(), row_key=keys)
         return dict(actions=self._chunk_out(act, B, G), logprob=self._chunk_out(lp, B, G), mean=pred.view(B, C, cfg.action_dim))
 
     def action_logprobs(self, batch: dict, actions, scale):
         """Log-probability of given chunks [B, G, chunk, action_dim] under the Laplace policy around the current weights' prediction: the
         forward of sample_actions_laplace, then ovla_laplace_pg without a gradient -- for the chunks a draw returned, the bits that draw
-        reported.  -> dict(logprob fp32 [B, G, chunk], mean bf16 [B, chunk, action_dim])."""
+        reported.  -> dict(logprob fp32 [B, G, chunk], mean bf16 [B, chunk, action_dim]).  scale="learned": ovla_laplace_pg_rows at the scale head's
+        widths; the dict gains log_scale bf16 [B, chunk, action_dim] and entropy fp32 [B, chunk]."""
         head = self._l1_head("action_logprobs")
+        learned = self._learned(scale, "action_logprobs")
         cfg, B = self.cfg, batch["input_ids"].shape[0]
         actions = torch.as_tensor(actions)
         if actions.dim() != 4:
@@ -2668,6 +2786,11 @@ class VLAEngine:
         G = actions.shape[1]
         act = self._chunk_rows(actions, F32, B, G, "actions", per_dim=True)
         with torch.no_grad():
+            if learned:
+                _, _, pred, _, _, ls = self._action_means(batch, False, head, learned=True)
+                lp, _, _, _, ent, _, _ = ops.laplace_pg_rows(pred, ls, self.scale_bounds, act, torch.ones((pred.shape[0], G), dtype=F32, device=self.device))
+                return dict(logprob=self._chunk_out(lp, B, G), mean=pred.view(B, cfg.chunk, cfg.action_dim), log_scale=ls.view(B, cfg.chunk, cfg.action_dim),
+                            entropy=ent.view(B, cfg.chunk))
             _, _, pred, _ = self._action_means(batch, False, head)
             lp, _, _, _, _ = ops.laplace_pg(pred, act, torch.ones((pred.shape[0], G), dtype=F32, device=self.device), scale)
         return dict(logprob=self._chunk_out(lp, B, G), mean=pred.view(B, cfg.chunk, cfg.action_dim))
@@ -2681,8 +2804,55 @@ class VLAEngine:
                 _, _, pred, _ = self._action_means(batch, False, head)
         return pred.view(batch["input_ids"].shape[0], self.cfg.chunk, self.cfg.action_dim)
 
+    def reference_action_policy(self, batch: dict) -> Dict[str, torch.Tensor]:
+        """Mean and log-scale under the reference policy (the scale head's store is snapshotted with the others), dict(mean, log_scale) bf16
+        [B, chunk, action_dim]: train_step_action_pg_group(scale="learned")'s `ref_means` / `ref_log_scales`."""
+        head = self._l1_head("reference_action_policy")
+        self._learned("learned", "reference_action_policy")
+        with self.reference_policy():
+            with torch.no_grad():
+                _, _, pred, _, _, ls = self._action_means(batch, False, head, learned=True)
+        shape = (batch["input_ids"].shape[0], self.cfg.chunk, self.cfg.action_dim)
+        return dict(mean=pred.view(shape), log_scale=ls.view(shape))
+
+    def _scale_bwd(self, h2, dlog_scale):
+        """The scale head's backward into its own store (and the reducer's notification, as for the head's)."""
+        sh = self.scale_head
+        sh.bwd(h2, dlog_scale)
+        if getattr(self, "_overlap", False):
+            for dt, g in sh.store.flat_grad.items():
+                self.reducer.notify(sh.store, dt, g.numel())
+
+    def _nll_of_target(self, pred, h2, target, loss_scale: float = 1.0):
+        """The maximum-likelihood side step of the scale head on a target chunk bf16 [rows, action_dim]: the scale head on h2, ovla_laplace_pg_rows
+        at G = 1 (adv = 1, no ratio, no reference, no entropy bonus, no dpred) with grad_scale = loss_scale / rows, the scale head's backward.  Three
+        launches; nothing but the scale head's store is written.  -> dict(nll, scale) device scalars: the mean negative log-likelihood per chunk
+        step and the mean b."""
+        n = pred.shape[0]
+        ls = self.scale_head.fwd(h2)
+        lp, _, _, _, _, _, dls = ops.laplace_pg_rows(pred, ls, self.scale_bounds, target.float().view(n, 1, -1), torch.ones((n, 1), dtype=F32, device=self.device),
+                                                     grad_scale=loss_scale / n, want_dpred=False)
+        self._scale_bwd(h2, dls)
+        return dict(nll=-lp.mean(), scale=ls.float().clamp(*self.scale_bounds).exp().mean())
+
+    def train_step_scale_nll(self, batch: dict, loss_scale: float = 1.0):
+        """The post-hoc maximum-likelihood fit of the scale head on a FROZEN policy: the inference-mode forward on the action rows, the head with
+        its hidden output, then the three launches of the side step on the batch's bf16 target chunk.  No decoder backward, no LoRA or head
+        gradient is touched, nothing is read back.  -> dict(nll, scale) device scalars."""
+        self._not_in_ema_scope("train_step_scale_nll")
+        head = self._l1_head("train_step_scale_nll")
+        self._learned("learned", "train_step_scale_nll")
+        cfg = self.cfg
+        target = batch["actions"].to(self.device, BF16).reshape(batch["input_ids"].shape[0] * cfg.chunk, cfg.action_dim).contiguous()
+        with torch.no_grad():
+            out = self.forward(batch["input_ids"], batch["attention_mask"], batch["pixel_values"], batch["labels"], proprio=batch.get("proprio"),
+                               train=False, sel="actions")
+            ah, _ = self.action_hidden(out)
+            pred, _, _, h2 = head.fwd(ah, return_hidden=True)
+            return self._nll_of_target(pred, h2, target, loss_scale)
+
     def train_step_action_pg_group(self, batch: dict, actions, advantages, scale, old_logprobs=None, ref_means=None, kl_coef: float = 0.0, clip=(0.8, 1.2),
-                                   loss_scale: float = 1.0, action_head=None, proprio_projector=None):
+                                   loss_scale: float = 1.0, action_head=None, proprio_projector=None, entropy_coef: float = 0.0, ref_log_scales=None):
         """One GRPO / PPO micro-step on G drawn chunks per observation under the Laplace policy of the L1 head, from ONE forward and ONE backward:
             loss = (1 / (B chunk G)) sum_{b, g, c} -min(ratio A_bg, clip(ratio) A_bg)  +  kl_coef (1 / (B chunk)) sum_{b, c} kl
         with ratio = exp(logprob - old_logprob) per chunk step (1 without old_logprobs) and kl the closed-form KL(policy || reference) of two
@@ -2691,10 +2861,22 @@ class VLAEngine:
         head's and the decoder's backward into the flat gradient buffers.  `actions` fp32 [B, G, chunk, action_dim] (RAW draws, normalised units);
         `advantages` [B, G] or [B, G, chunk]; `old_logprobs` [B, G, chunk] (sample_actions_laplace / action_logprobs); `ref_means`
         [B, chunk, action_dim] (reference_action_means), required with kl_coef > 0; host or device tensors.
-        -> dict of device scalars: loss, logprob, ratio, clip_frac, kl (means; kl is 0 without ref_means)."""
+        -> dict of device scalars: loss, logprob, ratio, clip_frac, kl (means; kl is 0 without ref_means).
+        scale="learned" (attach_scale_head): the scale head runs on the head's hidden output, ONE ovla_laplace_pg_rows launch takes the place of
+        ovla_laplace_pg and also forms the gradient with respect to the log-scale, the scale head's backward follows it (two launches more), and
+        the mean's path -- the head's backward, the reducer's notification, the decoder's backward -- is unchanged: the scale's gradient stops at
+        the head's hidden output.  The KL is between Laplace distributions of different scale (`ref_log_scales` [B, chunk, action_dim] beside
+        `ref_means`: reference_action_policy), and the loss gains - entropy_coef (1 / (B chunk)) sum_{b, c} entropy, the bonus that keeps the scale
+        from collapsing.  The statistics gain entropy (mean per chunk step) and scale (mean b).  entropy_coef and ref_log_scales belong to the
+        learned scale alone (ValueError with a numeric one)."""
         self._not_in_ema_scope("train_step_action_pg_group")
         self._refuse_per_policy_film_training(True)
         head = self._l1_head("train_step_action_pg_group", action_head)
+        learned = self._learned(scale, "train_step_action_pg_group")
+        if not learned and (entropy_coef != 0.0 or ref_log_scales is not None):
+            raise ValueError('entropy_coef and ref_log_scales belong to scale="learned"')
+        if learned and (ref_means is None) != (ref_log_scales is None):
+            raise ValueError('scale="learned": ref_means and ref_log_scales come together (reference_action_policy)')
         cfg, B = self.cfg, batch["input_ids"].shape[0]
         actions = torch.as_tensor(actions)
         if actions.dim() != 4:
@@ -2711,11 +2893,27 @@ class VLAEngine:
             ref = ref.reshape(B * cfg.chunk, cfg.action_dim).contiguous()
         elif kl_coef > 0.0:
             raise ValueError("kl_coef > 0 needs ref_means (reference_action_means)")
-        ops.laplace_scales(scale, cfg.action_dim)
-        out, idx, pred, hsaved = self._action_means(batch, True, head, proprio_projector)
-        n = pred.shape[0]
-        lp, ratio, clipped, kl, dpred = ops.laplace_pg(pred, act, adv, scale, old_logprob=old, ref_pred=ref, kl_coef=kl_coef, clip=clip,
-                                                       grad_scale=loss_scale / (n * G), kl_scale=loss_scale / n)
+        ref_ls = None
+        if ref_log_scales is not None:
+            ref_ls = torch.as_tensor(ref_log_scales).to(self.device, BF16)
+            if ref_ls.numel() != B * cfg.chunk * cfg.action_dim:
+                raise ValueError(f"ref_log_scales: {tuple(ref_ls.shape)} for {B} observations of {cfg.chunk} steps of {cfg.action_dim} dimensions")
+            ref_ls = ref_ls.reshape(B * cfg.chunk, cfg.action_dim).contiguous()
+        extra = {}
+        if learned:
+            out, idx, pred, hsaved, h2, ls = self._action_means(batch, True, head, proprio_projector, learned=True)
+            n = pred.shape[0]
+            lp, ratio, clipped, kl, ent, dpred, dls = ops.laplace_pg_rows(pred, ls, self.scale_bounds, act, adv, old_logprob=old, ref_pred=ref, ref_log_scale=ref_ls,
+                                                                          kl_coef=kl_coef, clip=clip, grad_scale=loss_scale / (n * G), kl_scale=loss_scale / n,
+                                                                          entropy_coef=entropy_coef, ent_scale=loss_scale / n)
+            self._scale_bwd(h2, dls)
+            extra = dict(entropy=ent.mean(), scale=ls.float().clamp(*self.scale_bounds).exp().mean())
+        else:
+            ops.laplace_scales(scale, cfg.action_dim)
+            out, idx, pred, hsaved = self._action_means(batch, True, head, proprio_projector)
+            n = pred.shape[0]
+            lp, ratio, clipped, kl, dpred = ops.laplace_pg(pred, act, adv, scale, old_logprob=old, ref_pred=ref, kl_coef=kl_coef, clip=clip,
+                                                           grad_scale=loss_scale / (n * G), kl_scale=loss_scale / n)
         dah = head.bwd(hsaved, dpred=dpred)
         if getattr(self, "_overlap", False) and hasattr(head, "store"):
             for dt, g in head.store.flat_grad.items():
@@ -2723,7 +2921,10 @@ class VLAEngine:
         self.backward_from_rows(dah, idx, out)
         surr = torch.minimum(ratio * adv, ratio.clamp(float(clip[0]), float(clip[1])) * adv)
         kl_mean = kl.mean() if kl is not None else torch.zeros((), dtype=F32, device=self.device)
-        return dict(loss=-surr.mean() + float(kl_coef) * kl_mean, logprob=lp.mean(), ratio=ratio.mean(), clip_frac=clipped.to(F32).mean(), kl=kl_mean)
+        loss = -surr.mean() + float(kl_coef) * kl_mean
+        if learned:
+            loss = loss - float(entropy_coef) * extra["entropy"]
+        return dict(loss=loss, logprob=lp.mean(), ratio=ratio.mean(), clip_frac=clipped.to(F32).mean(), kl=kl_mean, **extra)
 
     # -- the next-token cross entropy on the counted rows: train_step_discrete above and modeling._LMLossFn (`output.loss`) ------------------
     def counted_rows(self, labels, S: int, P: int):

@@ -223,7 +223,8 @@ def get_vla_action(cfg: Any, vla, processor: Any, obs: Dict[str, Any], task_labe
     `return_attention=True` -> (actions, modeling.ActionAttention): which camera, patches and prompt tokens each action row looked at
     (predict_action(output_attentions=True): the eager forward; not with a diffusion head).
     `action_noise_scale` (an L1 action head, no graph replay): the chunk is one draw from the Laplace policy of that scale around the head's
-    prediction (predict_action(action_noise_scale=...)): exploration noise for collecting rollouts."""
+    prediction (predict_action(action_noise_scale=...)): exploration noise for collecting rollouts; "learned" takes the widths of the model's
+    scale head (vla.load_scale_head)."""
     extra = dict(output_attentions=True) if return_attention else {}
     if action_noise_scale is not None:
         extra["action_noise_scale"] = action_noise_scale

@@ -23,7 +23,7 @@ import torch.nn as nn
 from . import ops
 from .config import VLAConfig
 from .diffusion import DDIMScheduler, SinusoidalPositionalEncoding
-from .engine import MAX_SLOTS, AttnCapture, ChunkGraph, DiffusionGraph, ActionHead, MlpProjector, ParamStore, SlotProjectors, VLAEngine, build_component
+from .engine import MAX_SLOTS, AttnCapture, ChunkGraph, DiffusionGraph, ActionHead, ActionScaleHead, MlpProjector, ParamStore, SlotProjectors, VLAEngine, build_component
 from .policy_pool import split_passes
 from .weights import make_getter
 
@@ -323,10 +323,12 @@ class SampledActions(NamedTuple):
     """What a noisy L1 decode drew (predict_action / predict_action_batch with action_noise_scale, return_sample=True): device tensors in
     NORMALISED action units -- the draw fp32 [B, chunk, action_dim], its log-probability per chunk step fp32 [B, chunk] under the Laplace
     policy around the head's prediction, and that prediction bf16 [B, chunk, action_dim].  `actions[:, None]` / `logprobs[:, None]` are the
-    `actions` / `old_logprobs` of VLAEngine.train_step_action_pg_group."""
+    `actions` / `old_logprobs` of VLAEngine.train_step_action_pg_group.  With action_noise_scale="learned" also the scale head's raw log-scale
+    bf16 [B, chunk, action_dim] (None with a numeric scale)."""
     actions: torch.Tensor
     logprobs: torch.Tensor
     mean: torch.Tensor
+    log_scale: Optional[torch.Tensor] = None
 
 
 class ActionAttention:
@@ -770,15 +772,23 @@ class OpenVLAForActionPrediction(_StoreModule):
         if self.use_graph:
             raise ValueError("action_noise_scale is not supported under graph replay (the captured chunk holds no draw): enable_graph_replay(False)")
         C = self.cfg.chunk
-        b, _ = ops.laplace_scales(action_noise_scale, self.cfg.action_dim)
-        if not bool(np.all((b > 0) & np.isfinite(b))):
-            raise ValueError(f"action_noise_scale = {action_noise_scale!r} (positive and finite)")
+        learned = isinstance(action_noise_scale, str)
+        if learned:
+            if action_noise_scale != "learned":
+                raise ValueError(f'action_noise_scale = {action_noise_scale!r} (a number, one per action dimension, or "learned")')
+            if self.scale_head is None:
+                raise ValueError('action_noise_scale="learned" needs attach_scale_head() / load_scale_head()')
+            b = None
+        else:
+            b, _ = ops.laplace_scales(action_noise_scale, self.cfg.action_dim)
+            if not bool(np.all((b > 0) & np.isfinite(b))):
+                raise ValueError(f"action_noise_scale = {action_noise_scale!r} (positive and finite)")
         keys = torch.arange(B, dtype=torch.int64) if sample_keys is None else torch.as_tensor(np.asarray(sample_keys)).to(torch.int64).reshape(-1)
         if keys.numel() != B:
             raise ValueError(f"sample_keys: {keys.numel()} keys for {B} observations")
         rows = (keys[:, None] * C + torch.arange(C, dtype=torch.int64)[None, :]).reshape(-1, 1) & 0xFFFFFFFF
         rows = torch.where(rows >= 2 ** 31, rows - 2 ** 32, rows).to(torch.int32)
-        return dict(scale=b, keys=rows, out={})
+        return dict(scale=b, learned=learned, keys=rows, out={})
 
     def _laplace_advance(self, laplace, sample_seed):
         """The generator's three words of this draw (the engine's token stream, advanced by one; `sample_seed` replaces its seed)."""
@@ -799,12 +809,52 @@ class OpenVLAForActionPrediction(_StoreModule):
         laplace["out"].update(actions=act.view(B, C, Ad), logprobs=lp.view(B, C), mean=mean.view(B, C, Ad))
         return laplace["out"]["actions"]
 
+    def _laplace_draw_learned(self, hidden, action_head, laplace):
+        """The learned-scale draw from the action hidden states [B, chunk * action_dim, D]: the L1 head with its hidden output, the scale head,
+        one ovla_laplace_sample_rows launch -> the draw fp32 [B, chunk, action_dim] (what VLAEngine.sample_actions_laplace(scale="learned")
+        issues after its forward)."""
+        comp, C, Ad = action_head.comp, self.cfg.chunk, self.cfg.action_dim
+        B, w = hidden.shape[0], laplace["words"]
+        with torch.no_grad():
+            mean, _, _, h2 = comp.fwd(hidden.detach().to(BF16).contiguous().view(-1, hidden.shape[-1]), return_hidden=True)
+            ls = self.scale_head.fwd(h2)
+            act, lp, _ = ops.laplace_sample_rows(mean, ls, self.scale_bounds, 1, seed=w[0] | (w[1] << 32), call=w[2], row_key=laplace["keys"].to(self.device))
+        laplace["out"].update(actions=act.view(B, C, Ad), logprobs=lp.view(B, C), mean=mean.view(B, C, Ad), log_scale=ls.view(B, C, Ad))
+        return laplace["out"]["actions"]
+
+    # -- the learned Laplace scale (engine.ActionScaleHead): a component of the model beside whichever L1 head a call passes ---------------------
+    scale_head = None
+    scale_bounds = ops.LAPLACE_SCALE_BOUNDS
+
+    def attach_scale_head(self, init_scale=0.1, bounds=ops.LAPLACE_SCALE_BOUNDS, state_dict: Optional[Dict[str, torch.Tensor]] = None):
+        """Gives the model a scale head (weight 0 and bias log(init_scale), or `state_dict`'s `log_scale.weight` / `log_scale.bias`, with or
+        without the `action_scale_head.` prefix): what action_noise_scale="learned" draws with.  Replaces an earlier one."""
+        lo, hi = float(bounds[0]), float(bounds[1])
+        if not (math.isfinite(lo) and math.isfinite(hi) and lo <= hi):
+            raise ValueError(f"bounds = {bounds}: two finite log-scales, lo <= hi")
+        prefix = "action_scale_head."
+        sd = ActionScaleHead.init_tensors(self.cfg, init_scale, self.device, prefix)
+        if state_dict is not None:
+            given = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in state_dict.items()}
+            for k, v in sd.items():
+                src = given[k] if k in given else given[k[len(prefix):]]
+                if tuple(src.shape) != tuple(v.shape):
+                    raise ValueError(f"{k}: shape {tuple(src.shape)} != {tuple(v.shape)}")
+                sd[k] = src.to(self.device, BF16)
+        self.scale_head = build_component(ActionScaleHead, self.device, sd.__getitem__, prefix, cfg=self.cfg)
+        self.scale_bounds = (lo, hi)
+        return self.scale_head
+
+    def load_scale_head(self, path, bounds=ops.LAPLACE_SCALE_BOUNDS):
+        """attach_scale_head from a fine-tuning run's `action_scale_head--{step}_checkpoint.pt`."""
+        return self.attach_scale_head(bounds=bounds, state_dict=torch.load(path, map_location="cpu", weights_only=True))
+
     @staticmethod
     def _sampled_actions(laplace, return_sample: bool) -> tuple:
         if not return_sample:
             return ()
         o = laplace["out"]
-        return (SampledActions(o["actions"], o["logprobs"], o["mean"]),)
+        return (SampledActions(o["actions"], o["logprobs"], o["mean"], o.get("log_scale")),)
 
     def _decode(self, pred, bins, hidden, sample=None):
         """Normalised actions [B, chunk, action_dim] from whichever the forward produced: the head's prediction (:923-927); the bin indices, when
@@ -939,6 +989,8 @@ class OpenVLAForActionPrediction(_StoreModule):
                     hidden = ah.view(B, A, D).clone()
                     if heads is not None:
                         pred = eng.policy_heads_fwd(ah, heads)
+                    elif action_head is not None and laplace is not None and laplace["learned"]:
+                        pred = self._laplace_draw_learned(hidden, action_head, laplace)
                     elif action_head is not None:
                         pred = action_head.predict_action(hidden)
                         if laplace is not None:
@@ -996,7 +1048,9 @@ class OpenVLAForActionPrediction(_StoreModule):
         before anything advances): the returned actions are ONE draw from the Laplace policy of that scale (a scalar or one value per action
         dimension, normalised units) around the head's prediction (ovla_laplace_sample), un-normalised as always; `return_sample=True` appends a
         SampledActions holding the normalised draw.  The call advances the engine's token stream by one; `sample_seed` / `sample_keys` as above.
-        With action_noise_scale=None every launch is the one issued before."""
+        With action_noise_scale=None every launch is the one issued before.  action_noise_scale="learned" (attach_scale_head / load_scale_head):
+        the widths are the scale head's, per chunk step and dimension (ovla_laplace_sample_rows); same refusals, and the SampledActions also
+        holds the log-scale."""
         cfg = self.cfg
         if use_film != self.engine.use_film:
             raise ValueError(f"use_film={use_film} but the model was built with use_film={self.engine.use_film}")
@@ -1080,7 +1134,8 @@ class OpenVLAForActionPrediction(_StoreModule):
         `action_noise_scale` (an L1 `action_head` without `policy`, the eager path only; ValueError otherwise, before anything advances): every
         observation's actions are ONE draw from the Laplace policy of that scale around the head's prediction (one ovla_laplace_sample launch for
         the batch); `sample_keys` [B] as above -- an observation draws the same chunk alone and in any batch under the same key and call.
-        `return_sample=True` appends a SampledActions.  The call advances the engine's token stream by one."""
+        `return_sample=True` appends a SampledActions.  The call advances the engine's token stream by one.  action_noise_scale="learned": the
+        model's scale head (attach_scale_head / load_scale_head) sets the widths, as in predict_action."""
         cfg = self.cfg
         if do_sample and policy is not None:
             raise ValueError("predict_action_batch(do_sample=True) is not supported with per-request policies")
@@ -1136,7 +1191,7 @@ class OpenVLAForActionPrediction(_StoreModule):
                                             return_sample=return_sample)
             tail = ()
             if return_sample:
-                tail, res = (SampledActions(*(t[:B] for t in res[-1])),), res[:-1]
+                tail, res = (SampledActions(*(None if t is None else t[:B] for t in res[-1])),), res[:-1]
             if return_tokens:
                 tail = (SampledTokens(*(t[:B] for t in res[-1])),) + tail
             if output_attentions:

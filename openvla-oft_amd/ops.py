@@ -1233,6 +1233,79 @@ def laplace_pg(pred, actions, advantage, scale, *, old_logprob=None, ref_pred=No
     return logprob, ratio, clipped, kl, dpred
 
 
+LAPLACE_SCALE_BOUNDS = (-6.0, 1.0)     # the default clamp of a learned log-scale: b in about [0.0025, 2.7] normalised units (a design choice)
+
+
+def laplace_sample_rows(pred, log_scale, bounds, G=1, *, seed=0, call=0, state_dev=None, row_key=None, action=None, logprob=None, entropy=None):
+    """laplace_sample with a scale per element (ovla.h "Laplace policy with a learned scale": ovla_laplace_sample_rows): pred, log_scale bf16
+    [rows, adim], bounds = (s_lo, s_hi) the clamp of the log-scale -> (action fp32 [rows, G, adim], logprob fp32 [rows, G], entropy fp32 [rows]).
+    With log_scale == 0 the first two are laplace_sample(pred, 1.0, ...)'s bits."""
+    _chk(pred, name="pred"), _chk(log_scale, name="log_scale")
+    assert pred.dim() == 2 and pred.is_contiguous() and log_scale.shape == pred.shape and log_scale.is_contiguous()
+    (rows, adim), dev, G = pred.shape, pred.device, int(G)
+    action = torch.empty((rows, G, adim), dtype=torch.float32, device=dev) if action is None else action
+    logprob = torch.empty((rows, G), dtype=torch.float32, device=dev) if logprob is None else logprob
+    entropy = torch.empty(rows, dtype=torch.float32, device=dev) if entropy is None else entropy
+    for t, dt, name, n in ((action, torch.float32, "action", rows * G * adim), (logprob, torch.float32, "logprob", rows * G),
+                           (entropy, torch.float32, "entropy", rows), (row_key, torch.int32, "row_key", rows * G)):
+        if t is not None:
+            _chk(t, dt, name)
+            assert t.numel() == n and t.is_contiguous(), f"{name}: expected {n} contiguous elements"
+    if state_dev is not None:
+        assert state_dev.is_cuda and state_dev.numel() == 3 and state_dev.is_contiguous() and state_dev.element_size() == 4 and not state_dev.is_floating_point(), \
+            "state_dev: three 32-bit integers on the device (seed_lo, seed_hi, call)"
+    g = STRUCTS["ovla_laplace_sample_rows_args"]()
+    g.pred, g.log_scale, g.action, g.logprob, g.entropy = pred.data_ptr(), log_scale.data_ptr(), action.data_ptr(), logprob.data_ptr(), entropy.data_ptr()
+    g.state_dev, g.row_key = _p(state_dev), _p(row_key)
+    g.seed_lo, g.seed_hi, g.call = int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF, int(call) & 0xFFFFFFFF
+    g.s_lo, g.s_hi = float(bounds[0]), float(bounds[1])
+    g.rows, g.adim, g.G = rows, adim, G
+    _lib.call("ovla_laplace_sample_rows", g, _stream())
+    return action, logprob, entropy
+
+
+def laplace_pg_rows(pred, log_scale, bounds, actions, advantage, *, old_logprob=None, ref_pred=None, ref_log_scale=None, kl_coef=0.0, clip=(0.8, 1.2),
+                    grad_scale=None, kl_scale=0.0, entropy_coef=0.0, ent_scale=0.0, dpred=None, dlog_scale=None, want_dpred=True, want_dlog_scale=True,
+                    logprob=None, ratio=None, clipped=None, kl=None, entropy=None):
+    """laplace_pg with a scale per element and its gradient (ovla.h: ovla_laplace_pg_rows): pred, log_scale bf16 [rows, adim], bounds = (s_lo,
+    s_hi), actions fp32 [rows, G, adim], advantage fp32 [rows, G] (and old_logprob fp32 [rows, G]; ref_pred with ref_log_scale bf16 [rows, adim])
+    -> (logprob, ratio fp32 [rows, G], clipped int32 [rows, G], kl fp32 [rows] or None, entropy fp32 [rows], dpred, dlog_scale bf16 [rows, adim] or
+    None).  `kl` exists exactly when the reference is given; with grad_scale the gradients go to `dpred` / `dlog_scale` (new tensors without
+    them; want_dpred=False / want_dlog_scale=False leaves that one out of the launch)."""
+    _chk(pred, name="pred"), _chk(log_scale, name="log_scale")
+    assert pred.dim() == 2 and pred.is_contiguous() and actions.dim() == 3 and actions.shape[0] == pred.shape[0] and actions.shape[2] == pred.shape[1]
+    assert log_scale.shape == pred.shape and log_scale.is_contiguous()
+    (rows, adim), dev, G = pred.shape, pred.device, actions.shape[1]
+    logprob = torch.empty((rows, G), dtype=torch.float32, device=dev) if logprob is None else logprob
+    ratio = torch.empty((rows, G), dtype=torch.float32, device=dev) if ratio is None else ratio
+    clipped = torch.empty((rows, G), dtype=torch.int32, device=dev) if clipped is None else clipped
+    entropy = torch.empty(rows, dtype=torch.float32, device=dev) if entropy is None else entropy
+    if kl is None and ref_pred is not None:
+        kl = torch.empty(rows, dtype=torch.float32, device=dev)
+    if grad_scale is not None and dpred is None and want_dpred:
+        dpred = torch.empty((rows, adim), dtype=BF16, device=dev)
+    if grad_scale is not None and dlog_scale is None and want_dlog_scale:
+        dlog_scale = torch.empty((rows, adim), dtype=BF16, device=dev)
+    for t, dt, name, n in ((actions, torch.float32, "actions", rows * G * adim), (advantage, torch.float32, "advantage", rows * G),
+                           (old_logprob, torch.float32, "old_logprob", rows * G), (ref_pred, BF16, "ref_pred", rows * adim),
+                           (ref_log_scale, BF16, "ref_log_scale", rows * adim), (logprob, torch.float32, "logprob", rows * G),
+                           (ratio, torch.float32, "ratio", rows * G), (clipped, torch.int32, "clipped", rows * G), (kl, torch.float32, "kl", rows),
+                           (entropy, torch.float32, "entropy", rows), (dpred, BF16, "dpred", rows * adim), (dlog_scale, BF16, "dlog_scale", rows * adim)):
+        if t is not None:
+            _chk(t, dt, name)
+            assert t.numel() == n and t.is_contiguous(), f"{name}: expected {n} contiguous elements"
+    g = STRUCTS["ovla_laplace_pg_rows_args"]()
+    g.pred, g.log_scale, g.ref_pred, g.ref_log_scale = pred.data_ptr(), log_scale.data_ptr(), _p(ref_pred), _p(ref_log_scale)
+    g.actions, g.advantage, g.old_logprob = actions.data_ptr(), advantage.data_ptr(), _p(old_logprob)
+    g.logprob, g.ratio, g.clipped, g.kl, g.entropy = logprob.data_ptr(), ratio.data_ptr(), clipped.data_ptr(), _p(kl), entropy.data_ptr()
+    g.dpred, g.dlog_scale = _p(dpred), _p(dlog_scale)
+    g.s_lo, g.s_hi, g.clip_lo, g.clip_hi = float(bounds[0]), float(bounds[1]), float(clip[0]), float(clip[1])
+    g.grad_scale, g.kl_coef, g.kl_scale, g.entropy_coef, g.ent_scale = float(grad_scale or 0.0), float(kl_coef), float(kl_scale), float(entropy_coef), float(ent_scale)
+    g.rows, g.adim, g.G = rows, adim, G
+    _lib.call("ovla_laplace_pg_rows", g, _stream())
+    return logprob, ratio, clipped, kl, entropy, dpred, dlog_scale
+
+
 def _chk_step(step):
     assert step.dtype == torch.int32 and step.numel() == 1 and step.is_cuda, "the DDIM step index is one int32 on the device"
 

@@ -219,6 +219,7 @@ def run_forward_pass(vla, action_head, noisy_action_projector, proprio_projector
 
 
 _COMPONENT_PREFIXES = {"proprio_projector": "proprio_projector.", "noisy_action_projector": "noisy_action_projector.", "action_head": "action_head.",
+                       "action_scale_head": "action_scale_head.",   # the learned Laplace scale (finetune(action_scale="fit")); absent without it
                        "vision_backbone": "vision_backbone."}   # FiLM scale/shift Linears (finetune.py:640-645 saves the wrapped backbone)
 
 
@@ -394,7 +395,8 @@ def finetune(cfg: FinetuneConfig, *, model_config: VLAConfig = OPENVLA_7B, state
              dataset: Optional[Iterable[dict]] = None, dataset_statistics: Optional[dict] = None, log=print, tokenizer=None,
              val_dataset=None, diffusion_noise: str = "host", ema_decay: Optional[float] = None, ema_power: Optional[float] = 0.75,
              ema_inv_gamma: float = 1.0, ema_update_after: int = 0, max_grad_norm: Optional[float] = None,
-             skip_nonfinite_steps: bool = True, optimizer_state: str = "param", tensor_stats_freq: Optional[int] = None) -> Dict[str, list]:
+             skip_nonfinite_steps: bool = True, optimizer_state: str = "param", tensor_stats_freq: Optional[int] = None,
+             action_scale: Optional[str] = None, init_action_scale=0.1, action_scale_bounds=(-6.0, 1.0)) -> Dict[str, list]:
     """finetune.py:763-1154.  Returns the logged metric history.  Data source, in this order: `dataset` (any iterable of collated
     batches); an episode store at `cfg.data_root_dir / cfg.dataset_name` (prismatic/vla/datasets/rlds_free.py: the reference's
     RLDSDataset + RLDSBatchTransform + collator, finetune.py:981-1016, with the frames augmented and normalised on the device --
@@ -433,7 +435,20 @@ def finetune(cfg: FinetuneConfig, *, model_config: VLAConfig = OPENVLA_7B, state
     has been non-finite on a collected step so far; rank 0 appends one JSON line {"step", "tensors": {name: {...}}} with the full table to
     `run_dir/tensor_stats.jsonl`.  With the step guard on, a log line whose skipped count rose names up to three tensors whose n_bad_steps
     rose with it.  The statistics are rank-local and identical on every rank (they are taken of the reduced gradient), so only rank 0 writes.
-    The n_bad_steps counters are NOT checkpointed: they restart at 0 on resume."""
+    The n_bad_steps counters are NOT checkpointed: they restart at 0 on resume.
+    `action_scale="fit"` (L1 objective only; None: nothing of this runs) attaches the learned Laplace scale head (VLAEngine.attach_scale_head with
+    `init_action_scale`, a scalar or one value per action dimension, and `action_scale_bounds`, the clamp of its log-scale) before the resume
+    load and before fp32 state, EMA, clipping and tensor statistics are enabled, and fits it by maximum likelihood on the demonstrations beside
+    the L1 step (train_step_fwd_bwd(fit_scale=True): three small launches after each backward).  Its gradient stops at the head's hidden
+    output: loss, LoRA factors and action head keep the bits of a run without it, as long as `max_grad_norm` does not clip -- the global norm
+    counts the scale head's gradient too.  The history gains `scale_nll` (mean negative log-likelihood per chunk step) and `action_scale` (mean
+    b) at the logging steps; checkpoints gain `action_scale_head--{step}_checkpoint.pt` (what vla.load_scale_head reads) and the
+    optimizer-state file its moments, and a resumed run continues both."""
+    if action_scale not in (None, "fit"):
+        raise ValueError(f'action_scale = {action_scale!r} (None or "fit")')
+    if action_scale is not None and not cfg.use_l1_regression:
+        raise ValueError('action_scale="fit" fits the Laplace scale of the L1 head: it needs cfg.use_l1_regression (not the diffusion or the discrete objective)')
+    fit_scale = action_scale == "fit"
     if tensor_stats_freq is not None and (isinstance(tensor_stats_freq, bool) or not isinstance(tensor_stats_freq, int) or tensor_stats_freq < 1):
         raise ValueError(f"tensor_stats_freq = {tensor_stats_freq!r} (an integer >= 1, or None)")
     if optimizer_state not in ("param", "fp32"):
@@ -478,6 +493,8 @@ def finetune(cfg: FinetuneConfig, *, model_config: VLAConfig = OPENVLA_7B, state
 
         sched, time_enc = DDIMScheduler(cfg.num_diffusion_steps), SinusoidalPositionalEncoding(model_config.llm_dim)
         noise_gen = torch.Generator().manual_seed(7 + rank)
+    if fit_scale:   # its store joins engine.stores: before everything below that enumerates them
+        engine.attach_scale_head(init_action_scale, bounds=action_scale_bounds)
     log(f"# total trainable params: {engine.num_trainable()}")
     if optimizer_state == "fp32":   # before the resume load (which then fills master and fp32 moments), the EMA shadows and the clip state
         engine.enable_fp32_optimizer_state()
@@ -563,7 +580,10 @@ def finetune(cfg: FinetuneConfig, *, model_config: VLAConfig = OPENVLA_7B, state
         history.update({"grad_norm": [], "grad_clip_coef": [], "skipped_steps": []})
     if tensor_stats_freq is not None:
         history.update({"tensor_stats": [], "nonfinite_tensors": []})
-    stats_step = None                    # the step of a collection not yet read back
+    if fit_scale:
+        history.update({"scale_nll": [], "action_scale": []})
+    step_kw = dict(fit_scale=True) if fit_scale else {}
+    stats_step = None                   # the step of a collection not yet read back
     stats_table, bad_seen = {}, {}       # the last table read back; each tensor's n_bad_steps at the last logging step
     skipped_seen = engine.grad_clip_stats()["skipped"] if grad_clip and tensor_stats_freq is not None else 0
 
@@ -594,7 +614,7 @@ def finetune(cfg: FinetuneConfig, *, model_config: VLAConfig = OPENVLA_7B, state
         if discrete:
             loss_sum, count, pred_ids = engine.train_step_discrete(batch, loss_scale=1.0 / cfg.grad_accumulation_steps)
         else:
-            loss_sum, count, _ = engine.train_step_fwd_bwd(batch, loss_scale=1.0 / cfg.grad_accumulation_steps, diffusion=diffusion)
+            loss_sum, count, _ = engine.train_step_fwd_bwd(batch, loss_scale=1.0 / cfg.grad_accumulation_steps, diffusion=diffusion, **step_kw)
         gradient_step_idx = batch_idx // cfg.grad_accumulation_steps
         log_step = gradient_step_idx if not cfg.resume else cfg.resume_step + gradient_step_idx
         if (batch_idx + 1) % cfg.grad_accumulation_steps == 0:
@@ -615,6 +635,9 @@ def finetune(cfg: FinetuneConfig, *, model_config: VLAConfig = OPENVLA_7B, state
                 history["learning_rate"].append(lr)
                 if ema_decay is not None:
                     history["ema_decay"].append(decay)
+                if fit_scale:   # of this step's last micro-batch, read where the loss was just read
+                    history["scale_nll"].append(engine.last_scale_fit["nll"].item())
+                    history["action_scale"].append(engine.last_scale_fit["scale"].item())
                 if discrete:
                     for k, v in token_metrics(batch, pred_ids).items():
                         history[k].append(v)
