@@ -1111,6 +1111,89 @@ typedef struct {
 } ovla_laplace_pg_rows_args;
 int ovla_laplace_pg_rows(const ovla_laplace_pg_rows_args* a, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Value head and generalised advantage estimation (PPO on the L1 head: the Laplace kernels above are the policy's side; these are the
+ * critic's).  A value head -- one linear map with adim = 1 on the head's post-layer_norm2 activations -- predicts one number per chunk
+ * step; ovla_value_loss pools them into one value per observation and forms the clipped squared-error loss against a return with its
+ * gradient; ovla_gae turns a rollout buffer [N trajectories, T steps] into advantages and returns; ovla_advantage_normalize standardises the
+ * advantages in place.  All three: stream-ordered, capturable, no atomics, no workspace, nothing read back; every operator written below is
+ * one rounded operation of the type named (fp32 unless "double" is said), in the bracketing written, no FMA contraction; a result's bits
+ * depend on its own observation / trajectory only, never on where it sits in the batch or on how many others there are (the statistics and
+ * the normalisation, which are sums over the batch, in the fixed order written).  THE CONTRACT (identical in csrc/value_gae.hip and in the
+ * numpy restatement tests/value_gae_reference.py):
+ *
+ * ovla_value_loss: u bf16 [B * chunk, 1] (what ovla_head_out_fwd stores for adim = 1; observation b owns rows b * chunk .. + chunk - 1);
+ * returns, old_value fp32 [B], valid int32 [B] (each optional); outputs value fp32 [B], du bf16 [B * chunk, 1] (optional; the dpred
+ * ovla_head_out_bwd takes), stats fp32 [8].  One workgroup of 64 lanes.  Per observation b:
+ *   value    acc = 0;  acc = acc + float(u[b, c]) for ascending c;  v = acc / float(chunk);  value[b] = v, ALWAYS (valid or not).
+ *            Without `returns` the launch ends here: du and stats are not touched.
+ *   valid    valid[b] != 0, or no `valid`.  Of an observation that is not valid neither returns[b] nor old_value[b] is read, its du rows are
+ *            stored as +0 and it enters NO statistic: padding may hold NaN.
+ *   error    R = returns[b];  e = v - R;  l = e * e;  dl = e
+ *   clipping (value_clip > 0; with value_clip == 0 old_value is not read):  old = old_value[b];  d = v - old;
+ *            vc = old + fminf(fmaxf(d, -value_clip), value_clip);  ec = vc - R;  lc = ec * ec;
+ *            if lc > l (false on equality and for a NaN): the observation is CLIPPED, l = lc and dl = +0 exactly.
+ *   loss     0.5f * l
+ *   gradient dl == 0 (clipped, or v == R): the observation's du rows are stored as +0, nothing is multiplied.  Otherwise w = dl * grad_scale
+ *            and du[b, c] = bf16_rne(w * inv_chunk) for every c, inv_chunk = 1.0f / float(chunk) formed once on the host.  du is the
+ *            gradient with respect to u of  grad_scale * sum_b loss_b.
+ *   stats    one lane, over the VALID observations in ascending b, every sum in double (each term converted to double first, each + and
+ *            each * one rounded double operation), each rounded to fp32 once at the end:
+ *            [0] their number  [1] the number clipped  [2] sum loss  [3] sum v  [4] sum R  [5] sum r * r with r = double(R) - double(v)
+ *            [6] sum double(R) * double(R)  [7] +0.   mean loss = [2] / [0], clip fraction = [1] / [0], explained variance =
+ *            1 - [5] / ([6] - [4]^2 / [0]).
+ * Refusals (OVLA_EINVAL, nothing launched): a null u or value; B <= 0; chunk <= 0; value_clip negative or NaN; with returns: a null stats,
+ * a null old_value while value_clip > 0.
+ *
+ * ovla_gae: reward, value fp32 [N, T], bootstrap fp32 [N] (the value after the last step), done uint8 [N, T] (non-zero: the episode ended
+ * AFTER this step), length int32 [N] (optional, default T); gamma and gamma_lambda by value, gamma_lambda = float32(double(gamma) *
+ * double(lam)) formed on the host; outputs adv, ret fp32 [N, T].  One lane per trajectory n, len = length[n]:
+ *   carry = 0;  for t = len - 1 down to 0:
+ *     nd    = done[n, t] ? 0.0f : 1.0f
+ *     vnext = (t == len - 1) ? bootstrap[n] : value[n, t + 1]
+ *     delta = (reward[n, t] + (gamma * vnext) * nd) - value[n, t]
+ *     carry = delta + (gamma_lambda * nd) * carry
+ *     adv[n, t] = carry;  ret[n, t] = carry + value[n, t]
+ *   Elements t >= len: adv and ret stored as +0, no input of theirs read (with len == 0 not even bootstrap[n]).
+ * WHO CHECKS length: the launch reads nothing back, so the HOST side of the call does, on length_host (optional: the same N values in host
+ * memory, which the caller that built the buffer holds anyway): an entry outside [0, T] is refused.  The device clamps length[n] to [0, T]
+ * before it forms any index, so a bad device value without a host copy cannot leave a buffer; its result is the clamped length's.
+ * Refusals: a null reward, value, bootstrap, done, adv or ret; N <= 0; T <= 0; gamma or gamma_lambda outside [0, 1] or NaN; length_host
+ * without length; a length_host entry outside [0, T].
+ *
+ * ovla_advantage_normalize: adv fp32 [N, T] in place, length / length_host as above; the VALID elements are e = n * T + t with t < len_n.
+ * One workgroup of 256 lanes; every sum below is taken in this order: lane i adds its valid elements e = i, i + 256, i + 512, ... in
+ * ascending e to a double that starts at 0; then the 256 lane sums s[0 .. 255] are folded by s[i] = s[i] + s[i + h] for i < h, h = 128, 64,
+ * ..., 1, and the total is s[0].  In double:  count = sum of 1;  mean = (sum of double(x)) / count;  var = (sum of d * d, d = double(x) -
+ * mean) / count;  std = sqrt(var) (correctly rounded).  Then in fp32, for every valid element:
+ *   adv = (adv - float(mean)) / (float(std) + eps)          (IEEE division)
+ * count == 0: nothing is written.  count == 1: mean is the element itself, the result exactly +0.  Elements that are not valid are neither
+ * read nor written.  Refusals: a null adv; N <= 0; T <= 0; N * T > 2^20 (one workgroup's reach); eps not positive and finite; length_host
+ * as above. */
+typedef struct {
+  const void* u; const float* returns; const float* old_value; const int32_t* valid;
+  float* value; void* du; float* stats;
+  float value_clip, grad_scale;
+  int32_t B, chunk;
+} ovla_value_loss_args;
+int ovla_value_loss(const ovla_value_loss_args* a, void* stream);
+
+typedef struct {
+  const float* reward; const float* value; const float* bootstrap; const uint8_t* done;
+  const int32_t* length; const int32_t* length_host;
+  float* adv; float* ret;
+  float gamma, gamma_lambda;
+  int32_t N, T;
+} ovla_gae_args;
+int ovla_gae(const ovla_gae_args* a, void* stream);
+
+typedef struct {
+  float* adv; const int32_t* length; const int32_t* length_host;
+  float eps;
+  int32_t N, T;
+} ovla_advantage_normalize_args;
+int ovla_advantage_normalize(const ovla_advantage_normalize_args* a, void* stream);
+
 /* fp32 -> bf16 convert with scale (publishes .grad views), and fill */
 typedef struct { const float* src; void* dst; int64_t n; float scale; } ovla_cvt_args;
 int ovla_cvt_f32_to_bf16(const ovla_cvt_args* a, void* stream);

@@ -1209,6 +1209,36 @@ class ActionScaleHead:
                 prefix + "log_scale.bias": torch.from_numpy(np.log(b0.astype(np.float64)).astype(np.float32)).to(device, BF16)}
 
 
+class ActionValueHead:
+    """The critic of PPO on the L1 head (ovla.h "Value head and generalised advantage estimation"): one linear map on the head's
+    post-layer_norm2 activations h2 [rows, llm_dim] -> u bf16 [rows, 1], one number per chunk step, which ovla_value_loss pools into one value
+    per observation.  Like the scale head's, its gradient STOPS at h2: the backward forms dW and db and discards dx, so every accumulator of
+    the policy keeps the bits it has without a critic (a design choice; a critic that shapes the trunk is not built)."""
+
+    def __init__(self, store, get, prefix: str, cfg: VLAConfig):
+        self.cfg, self.prefix = cfg, prefix
+        self.w = store.add(prefix + "value.weight", get(prefix + "value.weight"))
+        self.b = store.add(prefix + "value.bias", get(prefix + "value.bias"))
+
+    def linears(self):
+        return ()
+
+    def plain_params(self):
+        yield from (self.w, self.b)
+
+    def fwd(self, h2):
+        return ops.head_out_fwd(h2, self.w.data, self.b.data)
+
+    def bwd(self, h2, du):
+        ops.head_out_bwd(h2, self.w.data, None, None, 0.0, self.w.grad, self.b.grad, dpred=du)   # (dx is dropped: the gradient stops at h2)
+
+    @staticmethod
+    def init_tensors(cfg: VLAConfig, device, prefix: str = "action_value_head.") -> Dict[str, torch.Tensor]:
+        """weight 0 and bias 0: a fresh critic values every observation at exactly +0."""
+        return {prefix + "value.weight": torch.zeros((1, cfg.llm_dim), dtype=BF16, device=device),
+                prefix + "value.bias": torch.zeros(1, dtype=BF16, device=device)}
+
+
 class MlpProjector:
     """fc1 -> GELU -> fc2 with fully trainable fp32 parameters (ProprioProjector / NoisyActionProjector,
     prismatic/models/projectors.py:6-49)."""
@@ -1335,7 +1365,7 @@ class VLAEngine:
 
     @property
     def stores(self):
-        return [self.store] + [m.store for m in (self.proprio, self.noisy, self.head, self.scale_head) if m is not None]
+        return [self.store] + [m.store for m in (self.proprio, self.noisy, self.head, self.scale_head, self.value_head) if m is not None]
 
     # -- the learned Laplace scale of the L1 head (ActionScaleHead): opt-in, a store of its own -----------------------------------------------------
     scale_head: Optional["ActionScaleHead"] = None
@@ -1351,11 +1381,7 @@ class VLAEngine:
         self._not_in_ema_scope("attach_scale_head")
         if self.scale_head is not None:
             raise RuntimeError("attach_scale_head: a scale head is attached already")
-        late = [what for what, on in (("enable_grad_clip", self._grad_clip is not None), ("enable_tensor_stats", self._tensor_stats is not None),
-                                      ("enable_ema", self.ema_enabled), ("enable_fp32_optimizer_state", self.store.fp32_state),
-                                      ("set_reference_policy", self._reference is not None), ("attach_reducer", getattr(self, "reducer", None) is not None)) if on]
-        if late:
-            raise RuntimeError(f"attach_scale_head after {', '.join(late)}: they enumerate the stores when they are enabled; attach the scale head first")
+        self._attach_before_enumerators("attach_scale_head", "scale head")
         lo, hi = float(bounds[0]), float(bounds[1])
         if not (math.isfinite(lo) and math.isfinite(hi) and lo <= hi):
             raise ValueError(f"bounds = {bounds}: two finite log-scales, lo <= hi")
@@ -1370,6 +1396,42 @@ class VLAEngine:
         self.scale_head = build_component(ActionScaleHead, self.device, sd.__getitem__, prefix, cfg=self.cfg)
         self.scale_bounds = (lo, hi)
         return self.scale_head
+
+    def _attach_before_enumerators(self, who: str, what_head: str):
+        """A head with a store of its own joins `stores` before anything that enumerates them when it is enabled (RuntimeError otherwise)."""
+        late = [what for what, on in (("enable_grad_clip", self._grad_clip is not None), ("enable_tensor_stats", self._tensor_stats is not None),
+                                      ("enable_ema", self.ema_enabled), ("enable_fp32_optimizer_state", self.store.fp32_state),
+                                      ("set_reference_policy", self._reference is not None), ("attach_reducer", getattr(self, "reducer", None) is not None)) if on]
+        if late:
+            raise RuntimeError(f"{who} after {', '.join(late)}: they enumerate the stores when they are enabled; attach the {what_head} first")
+
+    # -- the critic of PPO on the L1 head (ActionValueHead): opt-in, a store of its own, beside the scale head in either order ----------------------
+    value_head: Optional["ActionValueHead"] = None
+
+    def attach_value_head(self, state_dict: Optional[Dict[str, torch.Tensor]] = None):
+        """Attaches the value head: weight 0 and bias 0 (or `state_dict`'s `action_value_head.value.{weight, bias}`).  Its store joins `stores`
+        as the scale head's does, with the same ordering rule: BEFORE the clip slots, the tensor-statistics tables, the EMA shadows, fp32 optimizer
+        state, the reference snapshot and a reducer (RuntimeError otherwise).  Needs head='l1'."""
+        self._l1_head("attach_value_head")
+        self._not_in_ema_scope("attach_value_head")
+        if self.value_head is not None:
+            raise RuntimeError("attach_value_head: a value head is attached already")
+        self._attach_before_enumerators("attach_value_head", "value head")
+        prefix = "action_value_head."
+        sd = ActionValueHead.init_tensors(self.cfg, self.device, prefix)
+        if state_dict is not None:
+            for k, v in sd.items():
+                src = state_dict[k] if k in state_dict else state_dict[k[len(prefix):]]
+                if tuple(src.shape) != tuple(v.shape):
+                    raise ValueError(f"{k}: shape {tuple(src.shape)} != {tuple(v.shape)}")
+                sd[k] = src.to(self.device, BF16)
+        self.value_head = build_component(ActionValueHead, self.device, sd.__getitem__, prefix, cfg=self.cfg)
+        return self.value_head
+
+    def _critic(self, who: str) -> "ActionValueHead":
+        if self.value_head is None:
+            raise ValueError(f"{who} needs attach_value_head()")
+        return self.value_head
 
     def _learned(self, scale, who: str) -> bool:
         """True for scale == "learned" (ValueError without a scale head); a numeric scale takes the fixed-scale code whether or not one is attached."""
@@ -1871,9 +1933,10 @@ class VLAEngine:
         if self.head is not None:
             for p in self.head.plain_params():
                 out[p.name] = getattr(p, kind)
-        if self.scale_head is not None:
-            for p in self.scale_head.plain_params():
-                out[p.name] = getattr(p, kind)
+        for extra_head in (self.scale_head, self.value_head):
+            if extra_head is not None:
+                for p in extra_head.plain_params():
+                    out[p.name] = getattr(p, kind)
         return out
 
     def load_trainable(self, sd: Dict[str, torch.Tensor], strict: bool = True) -> List[str]:
@@ -2706,17 +2769,20 @@ class VLAEngine:
             raise RuntimeError(f"{who} needs an engine built with head='l1' (the Laplace policy is the L1 head's; this one has head={self.head_kind!r})")
         return action_head if action_head is not None else self.head
 
-    def _action_means(self, batch: dict, train: bool, head, proprio_projector=None, learned: bool = False):
+    def _action_means(self, batch: dict, train: bool, head, proprio_projector=None, learned: bool = False, hidden: bool = False):
         """The forward on the action rows and the L1 head on them -> (out, rows_idx, pred bf16 [B * chunk, action_dim], the head's saved state);
-        with `learned` also (h2, log_scale): the head's post-layer_norm2 activations and the scale head's output bf16 [B * chunk, action_dim]."""
+        with `learned` also (h2, log_scale): the head's post-layer_norm2 activations and the scale head's output bf16 [B * chunk, action_dim];
+        with `hidden` (and not `learned`) also h2 -- the same launches, one more view."""
         kw = {} if proprio_projector is None else dict(proprio_projector=proprio_projector)
         out = self.forward(batch["input_ids"], batch["attention_mask"], batch["pixel_values"], batch["labels"], proprio=batch.get("proprio"),
                            train=train, sel="actions", **kw)
         ah, idx = self.action_hidden(out)
-        if not learned:
+        if not learned and not hidden:
             pred, _, hsaved = head.fwd(ah, train=train)
             return out, idx, pred, hsaved
         pred, _, hsaved, h2 = head.fwd(ah, train=train, return_hidden=True)
+        if not learned:
+            return out, idx, pred, hsaved, h2
         return out, idx, pred, hsaved, h2, self.scale_head.fwd(h2)
 
     def _chunk_rows(self, t, dtype, B: int, G: int, what: str, per_draw: bool = False, per_dim: bool = False):
@@ -2740,7 +2806,7 @@ class VLAEngine:
             return t.view(B, C, G, t.shape[2]).permute(0, 2, 1, 3).contiguous()
         return t.view(B, C, G).permute(0, 2, 1).contiguous()
 
-    def sample_actions_laplace(self, batch: dict, scale, num_samples: int = 1, row_keys=None):
+    def sample_actions_laplace(self, batch: dict, scale, num_samples: int = 1, row_keys=None, return_value: bool = False):
         """Draws G = num_samples chunks per observation from the Laplace policy of scale `scale` (a scalar or one value per action dimension,
         in normalised action units) around the L1 head's prediction: one forward (inference mode) on the action rows, the head, ONE
         ovla_laplace_sample launch; nothing is read back.  Advances the token stream's `call` by one.  `row_keys` int32 [B, G] (observation draw
@@ -2748,7 +2814,9 @@ class VLAEngine:
         -> dict(actions fp32 [B, G, chunk, action_dim], logprob fp32 [B, G, chunk], mean bf16 [B, chunk, action_dim]) on the device.
         scale="learned" (attach_scale_head): the widths are the scale head's, per chunk step and dimension -- the head with its hidden output,
         the scale head, ONE ovla_laplace_sample_rows launch; the dict gains log_scale bf16 [B, chunk, action_dim] (the raw, unclamped output) and
-        entropy fp32 [B, chunk]."""
+        entropy fp32 [B, chunk].
+        return_value=True (attach_value_head): the dict gains value fp32 [B], the critic's value of each observation from the SAME forward
+        (action_values' bits: two launches after the draw); the draws keep their bits.  Without it every launch is the one issued before."""
         head = self._l1_head("sample_actions_laplace")
         learned = self._learned(scale, "sample_actions_laplace")
         cfg, B, G = self.cfg, batch["input_ids"].shape[0], int(num_samples)
@@ -2761,16 +2829,81 @@ class VLAEngine:
         if tuple(keys.shape) == (B, G):
             keys = keys.reshape(B, G, 1) * C + torch.arange(C, dtype=torch.int32, device=self.device)[None, None, :]
         keys = self._chunk_rows(keys, torch.int32, B, G, "row_keys")
+        if return_value:
+            self._critic("sample_actions_laplace(return_value=True)")
         with torch.no_grad():
             st = self.token_sample
             if learned:
-                _, _, pred, _, _, ls = self._action_means(batch, False, head, learned=True)
+                _, _, pred, _, h2, ls = self._action_means(batch, False, head, learned=True)
                 act, lp, ent = ops.laplace_sample_rows(pred, ls, self.scale_bounds, G, seed=st.seed, call=st.advance(), row_key=keys)
-                return dict(actions=self._chunk_out(act, B, G), logprob=self._chunk_out(lp, B, G), mean=pred.view(B, C, cfg.action_dim),
-                            log_scale=ls.view(B, C, cfg.action_dim), entropy=ent.view(B, C))
-            _, _, pred, _ = self._action_means(batch, False, head)
-            act, lp = ops.laplace_sample(pred, scale, G, seed=st.seed, call=st.advance(), row_key=keys)
-        return dict(actions=self._chunk_out(act, B, G), logprob=self._chunk_out(lp, B, G), mean=pred.view(B, C, cfg.action_dim))
+                res = dict(actions=self._chunk_out(act, B, G), logprob=self._chunk_out(lp, B, G), mean=pred.view(B, C, cfg.action_dim),
+                           log_scale=ls.view(B, C, cfg.action_dim), entropy=ent.view(B, C))
+            else:
+                h2 = None
+                if return_value:
+                    _, _, pred, _, h2 = self._action_means(batch, False, head, hidden=True)
+                else:
+                    _, _, pred, _ = self._action_means(batch, False, head)
+                act, lp = ops.laplace_sample(pred, scale, G, seed=st.seed, call=st.advance(), row_key=keys)
+                res = dict(actions=self._chunk_out(act, B, G), logprob=self._chunk_out(lp, B, G), mean=pred.view(B, C, cfg.action_dim))
+            if return_value:
+                res["value"] = self._values_of(h2)
+        return res
+
+    def _values_of(self, h2) -> torch.Tensor:
+        """The value head on h2 [B * chunk, D] and the pooling launch (ovla_value_loss without returns) -> fp32 [B]."""
+        return ops.value_loss(self.value_head.fwd(h2), self.cfg.chunk)
+
+    def action_values(self, batch: dict) -> torch.Tensor:
+        """The critic's value of every observation, fp32 [B] on the device: the inference forward on the action rows, the head with its hidden
+        output, the value head, ovla_value_loss without returns (the mean of the chunk's per-step outputs).  Nothing is read back."""
+        head = self._l1_head("action_values")
+        self._critic("action_values")
+        with torch.no_grad():
+            _, _, _, _, h2 = self._action_means(batch, False, head, hidden=True)
+            return self._values_of(h2)
+
+    def _value_targets(self, B: int, returns, old_values, value_clip: float):
+        """returns / old_values (host or device, B elements each) -> fp32 [B] device tensors (old: None without clipping); raises before any launch."""
+        def per_obs(t, what):
+            t = torch.as_tensor(t).to(self.device, F32)
+            if t.numel() != B:
+                raise ValueError(f"{what}: {tuple(t.shape)} for {B} observations")
+            return t.reshape(B).contiguous()
+
+        if not value_clip >= 0.0:
+            raise ValueError(f"value_clip = {value_clip} (must not be negative or NaN; 0: no clipping)")
+        if value_clip > 0.0 and old_values is None:
+            raise ValueError("value_clip > 0 needs old_values (the values the rollout recorded)")
+        return per_obs(returns, "returns"), (per_obs(old_values, "old_values") if value_clip > 0.0 else None)
+
+    def _value_step(self, h2, targets, value_clip: float, grad_scale: float) -> Dict[str, torch.Tensor]:
+        """The critic's side step on the step's own h2: the value head's forward, ONE ovla_value_loss launch, the value head's backward into its
+        own store (three launches; nothing else is written, nothing is read back).  `targets`: _value_targets' pair.
+        -> dict(value_loss, value_clip_frac, explained_variance device scalars, value fp32 [B])."""
+        vh = self.value_head
+        returns, old = targets
+        value, du, s = ops.value_loss(vh.fwd(h2), self.cfg.chunk, returns=returns, old_value=old, value_clip=value_clip, grad_scale=grad_scale)
+        vh.bwd(h2, du)
+        if getattr(self, "_overlap", False):
+            for dt, g in vh.store.flat_grad.items():
+                self.reducer.notify(vh.store, dt, g.numel())
+        return dict(value_loss=s[2] / s[0], value_clip_frac=s[1] / s[0], explained_variance=1.0 - s[5] / (s[6] - s[4] * s[4] / s[0]), value=value)
+
+    def train_step_value(self, batch: dict, returns, old_values=None, value_clip: float = 0.0, loss_scale: float = 1.0):
+        """The critic alone on a FROZEN policy (as train_step_scale_nll fits the scale): the inference-mode forward on the action rows, the head
+        with its hidden output, then the three launches of the value step with grad_scale = loss_scale / B:
+            loss = (1 / B) sum_b 0.5 max((v_b - R_b)^2, (clip(v_b; old_b +- value_clip) - R_b)^2)
+        No decoder backward, no LoRA, head or scale-head gradient is touched, nothing is read back.  `returns` [B], `old_values` [B] (with
+        value_clip > 0).  -> dict(value_loss, value_clip_frac, explained_variance, value)."""
+        self._not_in_ema_scope("train_step_value")
+        head = self._l1_head("train_step_value")
+        self._critic("train_step_value")
+        B = batch["input_ids"].shape[0]
+        targets = self._value_targets(B, returns, old_values, float(value_clip))
+        with torch.no_grad():
+            _, _, _, _, h2 = self._action_means(batch, False, head, hidden=True)
+            return self._value_step(h2, targets, float(value_clip), loss_scale / B)
 
     def action_logprobs(self, batch: dict, actions, scale):
         """Log-probability of given chunks [B, G, chunk, action_dim] under the Laplace policy around the current weights' prediction: the
@@ -2852,7 +2985,8 @@ class VLAEngine:
             return self._nll_of_target(pred, h2, target, loss_scale)
 
     def train_step_action_pg_group(self, batch: dict, actions, advantages, scale, old_logprobs=None, ref_means=None, kl_coef: float = 0.0, clip=(0.8, 1.2),
-                                   loss_scale: float = 1.0, action_head=None, proprio_projector=None, entropy_coef: float = 0.0, ref_log_scales=None):
+                                   loss_scale: float = 1.0, action_head=None, proprio_projector=None, entropy_coef: float = 0.0, ref_log_scales=None,
+                                   returns=None, old_values=None, value_coef: float = 0.5, value_clip: float = 0.0):
         """One GRPO / PPO micro-step on G drawn chunks per observation under the Laplace policy of the L1 head, from ONE forward and ONE backward:
             loss = (1 / (B chunk G)) sum_{b, g, c} -min(ratio A_bg, clip(ratio) A_bg)  +  kl_coef (1 / (B chunk)) sum_{b, c} kl
         with ratio = exp(logprob - old_logprob) per chunk step (1 without old_logprobs) and kl the closed-form KL(policy || reference) of two
@@ -2868,7 +3002,13 @@ class VLAEngine:
         the head's hidden output.  The KL is between Laplace distributions of different scale (`ref_log_scales` [B, chunk, action_dim] beside
         `ref_means`: reference_action_policy), and the loss gains - entropy_coef (1 / (B chunk)) sum_{b, c} entropy, the bonus that keeps the scale
         from collapsing.  The statistics gain entropy (mean per chunk step) and scale (mean b).  entropy_coef and ref_log_scales belong to the
-        learned scale alone (ValueError with a numeric one)."""
+        learned scale alone (ValueError with a numeric one).
+        `returns` [B] (attach_value_head): the PPO step.  The loss gains value_coef (1 / B) sum_b 0.5 max((v_b - R_b)^2, (clip(v_b; old_b +-
+        value_clip) - R_b)^2) with v_b the critic's value of observation b (`old_values` [B] with value_clip > 0): the value head's forward on
+        the step's own hidden output, ONE ovla_value_loss launch with grad_scale = loss_scale value_coef / B, the value head's backward -- three
+        launches into the value head's store alone, its gradient stops at the hidden output, so every other accumulator keeps the bits of the
+        same step without `returns`.  The statistics gain value_loss, value_clip_frac, explained_variance (device scalars) and value fp32 [B];
+        `loss` stays the policy's.  Without `returns` the step issues exactly the launches it issued before, with or without a value head."""
         self._not_in_ema_scope("train_step_action_pg_group")
         self._refuse_per_policy_film_training(True)
         head = self._l1_head("train_step_action_pg_group", action_head)
@@ -2899,6 +3039,12 @@ class VLAEngine:
             if ref_ls.numel() != B * cfg.chunk * cfg.action_dim:
                 raise ValueError(f"ref_log_scales: {tuple(ref_ls.shape)} for {B} observations of {cfg.chunk} steps of {cfg.action_dim} dimensions")
             ref_ls = ref_ls.reshape(B * cfg.chunk, cfg.action_dim).contiguous()
+        critic = returns is not None
+        if critic:
+            self._critic("train_step_action_pg_group(returns=...)")
+            targets = self._value_targets(batch["input_ids"].shape[0], returns, old_values, float(value_clip))
+        elif old_values is not None or value_clip != 0.0:
+            raise ValueError("old_values and value_clip belong to the value loss: they need returns")
         extra = {}
         if learned:
             out, idx, pred, hsaved, h2, ls = self._action_means(batch, True, head, proprio_projector, learned=True)
@@ -2910,10 +3056,16 @@ class VLAEngine:
             extra = dict(entropy=ent.mean(), scale=ls.float().clamp(*self.scale_bounds).exp().mean())
         else:
             ops.laplace_scales(scale, cfg.action_dim)
-            out, idx, pred, hsaved = self._action_means(batch, True, head, proprio_projector)
+            if critic:
+                out, idx, pred, hsaved, h2 = self._action_means(batch, True, head, proprio_projector, hidden=True)
+            else:
+                out, idx, pred, hsaved = self._action_means(batch, True, head, proprio_projector)
             n = pred.shape[0]
             lp, ratio, clipped, kl, dpred = ops.laplace_pg(pred, act, adv, scale, old_logprob=old, ref_pred=ref, kl_coef=kl_coef, clip=clip,
                                                            grad_scale=loss_scale / (n * G), kl_scale=loss_scale / n)
+        if critic:
+            with torch.no_grad():
+                extra.update(self._value_step(h2, targets, float(value_clip), loss_scale * float(value_coef) / B))
         dah = head.bwd(hsaved, dpred=dpred)
         if getattr(self, "_overlap", False) and hasattr(head, "store"):
             for dt, g in head.store.flat_grad.items():

@@ -23,7 +23,7 @@ import torch.nn as nn
 from . import ops
 from .config import VLAConfig
 from .diffusion import DDIMScheduler, SinusoidalPositionalEncoding
-from .engine import MAX_SLOTS, AttnCapture, ChunkGraph, DiffusionGraph, ActionHead, ActionScaleHead, MlpProjector, ParamStore, SlotProjectors, VLAEngine, build_component
+from .engine import MAX_SLOTS, AttnCapture, ChunkGraph, DiffusionGraph, ActionHead, ActionScaleHead, ActionValueHead, MlpProjector, ParamStore, SlotProjectors, VLAEngine, build_component
 from .policy_pool import split_passes
 from .weights import make_getter
 
@@ -324,11 +324,13 @@ class SampledActions(NamedTuple):
     NORMALISED action units -- the draw fp32 [B, chunk, action_dim], its log-probability per chunk step fp32 [B, chunk] under the Laplace
     policy around the head's prediction, and that prediction bf16 [B, chunk, action_dim].  `actions[:, None]` / `logprobs[:, None]` are the
     `actions` / `old_logprobs` of VLAEngine.train_step_action_pg_group.  With action_noise_scale="learned" also the scale head's raw log-scale
-    bf16 [B, chunk, action_dim] (None with a numeric scale)."""
+    bf16 [B, chunk, action_dim] (None with a numeric scale).  With a value head loaded (load_value_head) also the critic's value of each
+    observation fp32 [B] from the same forward (None without one): the `old_values` of a PPO step."""
     actions: torch.Tensor
     logprobs: torch.Tensor
     mean: torch.Tensor
     log_scale: Optional[torch.Tensor] = None
+    value: Optional[torch.Tensor] = None
 
 
 class ActionAttention:
@@ -788,7 +790,7 @@ class OpenVLAForActionPrediction(_StoreModule):
             raise ValueError(f"sample_keys: {keys.numel()} keys for {B} observations")
         rows = (keys[:, None] * C + torch.arange(C, dtype=torch.int64)[None, :]).reshape(-1, 1) & 0xFFFFFFFF
         rows = torch.where(rows >= 2 ** 31, rows - 2 ** 32, rows).to(torch.int32)
-        return dict(scale=b, learned=learned, keys=rows, out={})
+        return dict(scale=b, learned=learned, value=return_sample and self.value_head is not None, keys=rows, out={})
 
     def _laplace_advance(self, laplace, sample_seed):
         """The generator's three words of this draw (the engine's token stream, advanced by one; `sample_seed` replaces its seed)."""
@@ -810,16 +812,22 @@ class OpenVLAForActionPrediction(_StoreModule):
         return laplace["out"]["actions"]
 
     def _laplace_draw_learned(self, hidden, action_head, laplace):
-        """The learned-scale draw from the action hidden states [B, chunk * action_dim, D]: the L1 head with its hidden output, the scale head,
-        one ovla_laplace_sample_rows launch -> the draw fp32 [B, chunk, action_dim] (what VLAEngine.sample_actions_laplace(scale="learned")
-        issues after its forward)."""
+        """The draw that needs the head's hidden output, from the action hidden states [B, chunk * action_dim, D]: the L1 head with its hidden
+        output, then -- learned scale -- the scale head and one ovla_laplace_sample_rows launch, or -- numeric scale with a value wanted -- the
+        ovla_laplace_sample launch of _laplace_draw; with a value head and return_sample the value head and ovla_value_loss' pooling after it
+        -> the draw fp32 [B, chunk, action_dim] (what VLAEngine.sample_actions_laplace issues after its forward)."""
         comp, C, Ad = action_head.comp, self.cfg.chunk, self.cfg.action_dim
         B, w = hidden.shape[0], laplace["words"]
         with torch.no_grad():
             mean, _, _, h2 = comp.fwd(hidden.detach().to(BF16).contiguous().view(-1, hidden.shape[-1]), return_hidden=True)
-            ls = self.scale_head.fwd(h2)
-            act, lp, _ = ops.laplace_sample_rows(mean, ls, self.scale_bounds, 1, seed=w[0] | (w[1] << 32), call=w[2], row_key=laplace["keys"].to(self.device))
-        laplace["out"].update(actions=act.view(B, C, Ad), logprobs=lp.view(B, C), mean=mean.view(B, C, Ad), log_scale=ls.view(B, C, Ad))
+            if laplace["learned"]:
+                ls = self.scale_head.fwd(h2)
+                act, lp, _ = ops.laplace_sample_rows(mean, ls, self.scale_bounds, 1, seed=w[0] | (w[1] << 32), call=w[2], row_key=laplace["keys"].to(self.device))
+                laplace["out"].update(actions=act.view(B, C, Ad), logprobs=lp.view(B, C), mean=mean.view(B, C, Ad), log_scale=ls.view(B, C, Ad))
+            else:
+                self._laplace_draw(mean.view(B, C, Ad), laplace)
+            if laplace["value"]:
+                laplace["out"]["value"] = ops.value_loss(self.value_head.fwd(h2), C)
         return laplace["out"]["actions"]
 
     # -- the learned Laplace scale (engine.ActionScaleHead): a component of the model beside whichever L1 head a call passes ---------------------
@@ -849,12 +857,32 @@ class OpenVLAForActionPrediction(_StoreModule):
         """attach_scale_head from a fine-tuning run's `action_scale_head--{step}_checkpoint.pt`."""
         return self.attach_scale_head(bounds=bounds, state_dict=torch.load(path, map_location="cpu", weights_only=True))
 
+    # -- the critic of PPO (engine.ActionValueHead): a component of the model, as the scale head is ------------------------------------------------
+    value_head = None
+
+    def load_value_head(self, state_dict):
+        """Gives the model a value head from `value.weight` [1, llm_dim] / `value.bias` [1] (with or without the `action_value_head.` prefix; a
+        state dict, or the path of a saved one).  With it a noisy L1 decode with return_sample=True also reports the critic's value of each
+        observation (SampledActions.value); nothing else changes.  Replaces an earlier one."""
+        if not isinstance(state_dict, dict):
+            state_dict = torch.load(state_dict, map_location="cpu", weights_only=True)
+        prefix = "action_value_head."
+        given = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in state_dict.items()}
+        sd = ActionValueHead.init_tensors(self.cfg, self.device, prefix)
+        for k, v in sd.items():
+            src = given[k] if k in given else given[k[len(prefix):]]
+            if tuple(src.shape) != tuple(v.shape):
+                raise ValueError(f"{k}: shape {tuple(src.shape)} != {tuple(v.shape)}")
+            sd[k] = src.to(self.device, BF16)
+        self.value_head = build_component(ActionValueHead, self.device, sd.__getitem__, prefix, cfg=self.cfg)
+        return self.value_head
+
     @staticmethod
     def _sampled_actions(laplace, return_sample: bool) -> tuple:
         if not return_sample:
             return ()
         o = laplace["out"]
-        return (SampledActions(o["actions"], o["logprobs"], o["mean"], o.get("log_scale")),)
+        return (SampledActions(o["actions"], o["logprobs"], o["mean"], o.get("log_scale"), o.get("value")),)
 
     def _decode(self, pred, bins, hidden, sample=None):
         """Normalised actions [B, chunk, action_dim] from whichever the forward produced: the head's prediction (:923-927); the bin indices, when
@@ -989,7 +1017,7 @@ class OpenVLAForActionPrediction(_StoreModule):
                     hidden = ah.view(B, A, D).clone()
                     if heads is not None:
                         pred = eng.policy_heads_fwd(ah, heads)
-                    elif action_head is not None and laplace is not None and laplace["learned"]:
+                    elif action_head is not None and laplace is not None and (laplace["learned"] or laplace["value"]):
                         pred = self._laplace_draw_learned(hidden, action_head, laplace)
                     elif action_head is not None:
                         pred = action_head.predict_action(hidden)
@@ -1050,7 +1078,8 @@ class OpenVLAForActionPrediction(_StoreModule):
         SampledActions holding the normalised draw.  The call advances the engine's token stream by one; `sample_seed` / `sample_keys` as above.
         With action_noise_scale=None every launch is the one issued before.  action_noise_scale="learned" (attach_scale_head / load_scale_head):
         the widths are the scale head's, per chunk step and dimension (ovla_laplace_sample_rows); same refusals, and the SampledActions also
-        holds the log-scale."""
+        holds the log-scale.  With a value head (load_value_head) and return_sample=True the SampledActions also holds the critic's value of the
+        observation from the same forward (two launches after the draw); without one the field is None and nothing else changes."""
         cfg = self.cfg
         if use_film != self.engine.use_film:
             raise ValueError(f"use_film={use_film} but the model was built with use_film={self.engine.use_film}")

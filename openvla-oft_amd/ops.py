@@ -1306,6 +1306,84 @@ def laplace_pg_rows(pred, log_scale, bounds, actions, advantage, *, old_logprob=
     return logprob, ratio, clipped, kl, entropy, dpred, dlog_scale
 
 
+def _chk_n(t, dtype, name, n):
+    if t is not None:
+        _chk(t, dtype, name)
+        assert t.numel() == n and t.is_contiguous(), f"{name}: expected {n} contiguous elements"
+
+
+def value_loss(u, chunk, *, returns=None, old_value=None, valid=None, value_clip=0.0, grad_scale=None, value=None, du=None, stats=None):
+    """A value head's output pooled into one value per observation, and its clipped squared-error loss (ovla.h "Value head and generalised
+    advantage estimation": ovla_value_loss): u bf16 [B * chunk, 1] -> value fp32 [B]; with `returns` fp32 [B] (and old_value fp32 [B] under
+    value_clip > 0, valid int32 [B]) -> (value, du bf16 [B * chunk, 1] or None, stats fp32 [8]).  du exists with a grad_scale (or when given)."""
+    _chk(u, name="u")
+    chunk = int(chunk)
+    assert u.is_contiguous() and chunk > 0 and u.numel() % chunk == 0, f"u: {tuple(u.shape)} is not whole observations of {chunk} steps"
+    B, dev = u.numel() // chunk, u.device
+    value = torch.empty(B, dtype=torch.float32, device=dev) if value is None else value
+    if returns is not None:
+        stats = torch.empty(8, dtype=torch.float32, device=dev) if stats is None else stats
+        if grad_scale is not None and du is None:
+            du = torch.empty((B * chunk, 1), dtype=BF16, device=dev)
+    for t, dt, name, n in ((value, torch.float32, "value", B), (returns, torch.float32, "returns", B), (old_value, torch.float32, "old_value", B),
+                           (valid, torch.int32, "valid", B), (du, BF16, "du", B * chunk), (stats, torch.float32, "stats", 8)):
+        _chk_n(t, dt, name, n)
+    g = STRUCTS["ovla_value_loss_args"]()
+    g.u, g.returns, g.old_value, g.valid = u.data_ptr(), _p(returns), _p(old_value), _p(valid)
+    g.value, g.du, g.stats = value.data_ptr(), _p(du), _p(stats)
+    g.value_clip, g.grad_scale, g.B, g.chunk = float(value_clip), float(grad_scale or 0.0), B, chunk
+    _lib.call("ovla_value_loss", g, _stream())
+    return value if returns is None else (value, du, stats)
+
+
+def _host_lengths(length, host_lengths):
+    """The optional host copy of the trajectory lengths as a ctypes int32 array (None without one); the library validates it (OVLA_EINVAL)."""
+    if host_lengths is None:
+        return None
+    vals = [int(v) for v in host_lengths]
+    assert length is not None and len(vals) == length.numel(), "host_lengths must mirror length"
+    return (ctypes.c_int32 * len(vals))(*vals)
+
+
+def gae(reward, value, bootstrap, done, *, length=None, host_lengths=None, gamma=0.99, lam=0.95, adv=None, ret=None):
+    """Generalised advantage estimation over a rollout buffer (ovla.h: ovla_gae): reward, value fp32 [N, T], bootstrap fp32 [N], done uint8
+    [N, T] (1: the episode ended after this step), length int32 [N] (default T) -> (adv, ret fp32 [N, T]), +0 beyond a trajectory's length.
+    host_lengths (optional, the same values on the host): an entry outside [0, T] raises before anything is launched."""
+    _chk(reward, torch.float32, "reward")
+    assert reward.dim() == 2 and reward.is_contiguous()
+    (N, T), dev = reward.shape, reward.device
+    adv = torch.empty((N, T), dtype=torch.float32, device=dev) if adv is None else adv
+    ret = torch.empty((N, T), dtype=torch.float32, device=dev) if ret is None else ret
+    for t, dt, name, n in ((value, torch.float32, "value", N * T), (bootstrap, torch.float32, "bootstrap", N), (done, torch.uint8, "done", N * T),
+                           (length, torch.int32, "length", N), (adv, torch.float32, "adv", N * T), (ret, torch.float32, "ret", N * T)):
+        _chk_n(t, dt, name, n)
+    hl = _host_lengths(length, host_lengths)
+    g = STRUCTS["ovla_gae_args"]()
+    g.reward, g.value, g.bootstrap, g.done, g.length = reward.data_ptr(), _p(value), _p(bootstrap), _p(done), _p(length)
+    g.length_host = ctypes.cast(hl, ctypes.c_void_p).value if hl is not None else None
+    g.adv, g.ret = adv.data_ptr(), ret.data_ptr()
+    g.gamma, g.gamma_lambda = float(gamma), float(np.float32(np.float64(gamma) * np.float64(lam)))   # gamma * lam in double, rounded once
+    g.N, g.T = N, T
+    _lib.call("ovla_gae", g, _stream())
+    return adv, ret
+
+
+def advantage_normalize(adv, *, length=None, host_lengths=None, eps=1e-8):
+    """adv fp32 [N, T] in place <- (adv - mean) / (std + eps) over the elements inside their trajectory's length, mean and population std in
+    double in the contract's fixed order (ovla.h: ovla_advantage_normalize).  N * T <= 2^20."""
+    _chk(adv, torch.float32, "adv")
+    assert adv.dim() == 2 and adv.is_contiguous()
+    N, T = adv.shape
+    _chk_n(length, torch.int32, "length", N)
+    hl = _host_lengths(length, host_lengths)
+    g = STRUCTS["ovla_advantage_normalize_args"]()
+    g.adv, g.length = adv.data_ptr(), _p(length)
+    g.length_host = ctypes.cast(hl, ctypes.c_void_p).value if hl is not None else None
+    g.eps, g.N, g.T = float(eps), N, T
+    _lib.call("ovla_advantage_normalize", g, _stream())
+    return adv
+
+
 def _chk_step(step):
     assert step.dtype == torch.int32 and step.numel() == 1 and step.is_cuda, "the DDIM step index is one int32 on the device"
 

@@ -10,6 +10,14 @@ head's output layer predicts log b per chunk step and dimension).  That head is 
 (finetune(action_scale="fit"), VLAEngine.train_step_scale_nll), and with scale="learned" the policy gradient moves mean and scale together,
 the KL is to the reference's mean and scale (reference_action_policy) and `entropy_coef` keeps the scale from collapsing.  Either way the KL
 to the reference policy is closed-form, no estimator is needed.
+
+Those are bandit methods: G chunks of ONE observation are scored against each other, and nothing knows that a chunk is one step of an episode.
+gae and ppo_step_continuous are the episodic side (PPO): a value head beside the L1 head (VLAEngine.attach_value_head; action_values,
+sample_actions_laplace(return_value=True) record the critic's value with each rollout step), generalised advantage estimation over a
+caller-owned rollout buffer [N trajectories, T steps] on the device (ovla_gae, ovla_advantage_normalize: nothing is read back between the
+buffer and the training step), and one minibatch of that buffer through train_step_action_pg_group at G = 1 with the clipped value loss
+beside the clipped surrogate.  The critic's gradient stops at the head's hidden output: it fits the value on the policy's features and does
+not shape them.  The rollout buffer, the environments, minibatching and the optimizer loop stay the caller's.
 """
 from __future__ import annotations
 
@@ -17,6 +25,8 @@ from typing import Callable, Dict
 
 import numpy as np
 import torch
+
+from . import ops
 
 
 def group_advantages(rewards: torch.Tensor, eps: float = 1e-6) -> torch.Tensor:
@@ -99,3 +109,79 @@ def grpo_step_continuous(engine, batch: dict, reward_fn: Callable, *, group_size
     stats = dict(stats)
     stats.update(reward=rewards.mean(), advantages=adv)
     return stats
+
+
+def gae(rewards, values, bootstrap, dones, lengths=None, gamma: float = 0.99, lam: float = 0.95, normalize: bool = True, eps: float = 1e-8):
+    """Generalised advantage estimation over a rollout buffer, on the device: rewards, values [N, T], bootstrap [N] (the critic's value of the
+    observation after the last recorded step), dones [N, T] (true: the episode ended after this step), lengths [N] (steps recorded per
+    trajectory, default T) -> (advantages, returns) fp32 [N, T], +0 beyond a trajectory's length.  One ovla_gae launch and, with `normalize`,
+    one ovla_advantage_normalize launch on the advantages (mean 0, population std 1 over the recorded steps; the returns are not normalised);
+    nothing is read back.  `lengths` given on the HOST (a list, an array, a CPU tensor) is checked against [0, T] before the launch; a device
+    tensor is taken as it is and clamped by the kernels."""
+    tensors = [t for t in (rewards, values, bootstrap, dones, lengths) if isinstance(t, torch.Tensor) and t.is_cuda]
+    if not tensors:
+        raise ValueError("gae works on the device: at least one of its inputs must be a device tensor")
+    dev = tensors[0].device
+
+    def on_dev(t, dtype):
+        return torch.as_tensor(t).to(dev, dtype).contiguous()
+
+    r = on_dev(rewards, torch.float32)
+    if r.dim() != 2:
+        raise ValueError(f"rewards: {tuple(r.shape)} ([N trajectories, T steps])")
+    N, T = r.shape
+    v, bs, d = on_dev(values, torch.float32), on_dev(bootstrap, torch.float32).reshape(-1), on_dev(torch.as_tensor(dones) != 0, torch.uint8)
+    if tuple(v.shape) != (N, T) or tuple(d.shape) != (N, T) or bs.numel() != N:
+        raise ValueError(f"values {tuple(v.shape)}, dones {tuple(d.shape)}, bootstrap {tuple(bs.shape)} for rewards {(N, T)}")
+    ln = host = None
+    if lengths is not None:
+        if not (isinstance(lengths, torch.Tensor) and lengths.is_cuda):
+            host = [int(x) for x in torch.as_tensor(lengths).reshape(-1).tolist()]
+        ln = on_dev(lengths, torch.int32).reshape(-1)
+        if ln.numel() != N:
+            raise ValueError(f"lengths: {ln.numel()} for {N} trajectories")
+    adv, ret = ops.gae(r, v, bs, d, length=ln, host_lengths=host, gamma=gamma, lam=lam)
+    if normalize:
+        ops.advantage_normalize(adv, length=ln, host_lengths=host, eps=eps)
+    return adv, ret
+
+
+def ppo_step_continuous(engine, batch: dict, actions, old_logprobs, advantages, returns, old_values=None, *, scale, clip=(0.8, 1.2), value_coef: float = 0.5,
+                        value_clip: float = 0.0, kl_coef: float = 0.0, entropy_coef: float = 0.0, inner_steps: int = 1,
+                        loss_scale: float = 1.0) -> Dict[str, torch.Tensor]:
+    """One PPO iteration on one minibatch of a rollout buffer of an L1-head engine with a value head: `batch` the B observations, `actions`
+    [B, chunk, action_dim] the RAW chunks drawn at rollout time (sample_actions_laplace), `old_logprobs` [B, chunk] their log-probabilities then,
+    `advantages` [B] and `returns` [B] from gae, `old_values` [B] the critic's values then (needed with value_clip > 0).  The reference
+    policy's means (and log-scales under scale="learned") when one is set and kl_coef > 0, then `inner_steps` micro-steps of
+    train_step_action_pg_group at G = 1 with the value loss.  Gradients accumulate in the engine's flat buffers; nothing is read back.
+    -> the last micro-step's statistics (loss, logprob, ratio, clip_frac, kl, value_loss, value_clip_frac, explained_variance, value; entropy
+    and scale under scale="learned")."""
+    learned = isinstance(scale, str)
+    if entropy_coef != 0.0 and not learned:
+        raise ValueError('entropy_coef belongs to scale="learned": a fixed scale has a constant entropy')
+    cfg, B = engine.cfg, batch["input_ids"].shape[0]
+    act = torch.as_tensor(actions)
+    if tuple(act.shape) != (B, cfg.chunk, cfg.action_dim):
+        raise ValueError(f"actions: {tuple(act.shape)}, expected {(B, cfg.chunk, cfg.action_dim)}")
+    old_lp = torch.as_tensor(old_logprobs)
+    if tuple(old_lp.shape) != (B, cfg.chunk):
+        raise ValueError(f"old_logprobs: {tuple(old_lp.shape)}, expected {(B, cfg.chunk)}")
+    adv = torch.as_tensor(advantages)
+    if adv.numel() != B:
+        raise ValueError(f"advantages: {tuple(adv.shape)} for {B} observations")
+    ref, extra = None, {}
+    if kl_coef > 0.0 and engine.has_reference_policy:
+        if learned:
+            pol = engine.reference_action_policy(batch)
+            ref, extra["ref_log_scales"] = pol["mean"], pol["log_scale"]
+        else:
+            ref = engine.reference_action_means(batch)
+    if learned:
+        extra["entropy_coef"] = entropy_coef
+    stats = None
+    for _ in range(int(inner_steps)):
+        stats = engine.train_step_action_pg_group(batch, act.reshape(B, 1, cfg.chunk, cfg.action_dim), adv.reshape(B, 1), scale,
+                                                  old_logprobs=old_lp.reshape(B, 1, cfg.chunk), ref_means=ref, kl_coef=kl_coef if ref is not None else 0.0,
+                                                  clip=clip, loss_scale=loss_scale, returns=returns, old_values=old_values, value_coef=value_coef,
+                                                  value_clip=value_clip, **extra)
+    return dict(stats)
