@@ -1112,6 +1112,63 @@ typedef struct {
 int ovla_laplace_pg_rows(const ovla_laplace_pg_rows_args* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Preference optimisation on the Laplace policy (DPO / IPO on the L1 head: supervision by comparisons instead of rewards.  Per observation
+ * a CHOSEN and a REJECTED chunk and a reference prediction; the loss is a function of one scalar, the margin m between the two chunks'
+ * summed log-ratios to the reference, and its gradient with respect to the prediction is the group policy gradient of the pair -- the
+ * chosen chunk with advantage +k, the rejected one with -k, k out of m).  ovla_laplace_dpo reduces m over an observation's chunk steps,
+ * forms k and applies it in ONE launch: dpred / dlog_scale are what ovla_head_out_bwd takes, so a preference step is one training forward
+ * and one backward.  Conventions of the two sections above: stream-ordered, capturable, no atomics, no workspace; every operator one rounded
+ * fp32 operation in the bracketing written, no FMA contraction; an observation's bits depend on its own inputs only, never on B or on its
+ * position.  THE CONTRACT (identical in csrc/laplace_dpo.hip and in the numpy restatement tests/laplace_dpo_reference.py):
+ * One workgroup of 64 lanes per observation b, which owns rows b * chunk .. b * chunk + chunk - 1;  rows = B * chunk;
+ * 1 <= chunk <= OVLA_DPO_CHUNK_MAX;  1 <= adim <= 16.  pred, ref_pred bf16 [rows, adim];  chosen, rejected fp32 [rows, adim] (RAW chunks);
+ * weight fp32 [B] (optional, default 1; must be >= 0).  The scale is EITHER scale[16] / log_norm[16] by value, as ovla_laplace_pg takes them
+ * (both policies share it), OR log_scale and ref_log_scale bf16 [rows, adim] with s_lo / s_hi, each element by ovla_laplace_pg_rows' rules
+ * (s_c, inside, b = expf(s_c), inv_b = 1.0f / b, log_norm = s_c + LN2F); the two pointers come together and select this form.
+ * Per chunk step c (row r = b * chunk + c), by the body  acc = 0;  acc = acc - (fabsf(a_d - mu_d) * inv_b_d + log_norm_d), ascending d:
+ *   lp_w[c], lp_l[c]     the chosen and the rejected chunk under (pred, scale)
+ *   rlp_w[c], rlp_l[c]   the same two under (ref_pred, the reference's scale)
+ *   logprob[r] = (lp_w, lp_l), ref_logprob[r] = (rlp_w, rlp_l), fp32 [rows, 2] (each optional): the bits ovla_laplace_pg /
+ *   ovla_laplace_pg_rows reports for the same chunk on pred and on ref_pred.
+ * Per observation:
+ *   h_w = (lp_w[0] - rlp_w[0]) + (lp_w[1] - rlp_w[1]) + ... in ascending c, the first term taken as it is, each further term one rounded add;
+ *   h_l the same of the rejected chunk;  m = h_w - h_l.    h[b] = (h_w, h_l) fp32 [B, 2];  margin[b] = m.
+ *   loss_type 0 (sigmoid, eps = label_smoothing):  z = beta * m;  az = fabsf(z);  e = expf(-az) (accurate expf; in (0, 1] at any |z|);
+ *     den = 1.0f + e;  l = logf(den) (accurate logf);  s_big = 1.0f / den;  s_small = e / den  (IEEE divisions)
+ *     softplus(-z) = (z < 0 ? az : 0.0f) + l;   softplus(z) = (z > 0 ? az : 0.0f) + l
+ *     sigma(-z) = z >= 0 ? s_small : s_big;     sigma(z) = z >= 0 ? s_big : s_small;     one_m = 1.0f - eps
+ *     loss_b = (one_m * softplus(-z)) + (eps * softplus(z));     k = ((one_m * sigma(-z)) - (eps * sigma(z))) * beta
+ *   loss_type 1 (IPO):  tau = 1.0f / (2.0f * beta);  dm = m - tau;  loss_b = dm * dm;  k = -2.0f * dm      (all IEEE)
+ *   coef_b = (k * w_b) * grad_scale.    loss[b] = loss_b (NOT weighted);  coef[b] = coef_b: minus d(total loss) / d m, scaled.
+ * Gradient, per (r, d): the pair as a group of two in ovla_laplace_pg(_rows)' sum.  g = 0 is the chosen chunk with c_0 = coef_b, or with
+ *   c_0 = coef_b + ((nll_coef * w_b) * nll_scale) when nll_coef > 0 (the negative log-likelihood of the chosen chunk beside the preference
+ *   loss);  g = 1 is the rejected chunk with c_1 = -coef_b.  A sample with c == 0 is SKIPPED and its chunk is not read.  In ascending g over the
+ *   samples not skipped, the first term taken as it is, the second one rounded add, +0 when both are skipped:
+ *     acc_mu = sum of (sgn(mu_d - a_{g,d}) * inv_b) * c_g;     acc_s = sum of (1.0f - fabsf(a_{g,d} - mu_d) * inv_b) * c_g
+ *   dpred[r, d] = bf16(acc_mu);  dlog_scale[r, d] = inside ? bf16(acc_s) : +0 (inside is true under the by-value scale).  Each optional:
+ *   the bits ovla_laplace_pg / ovla_laplace_pg_rows stores at G = 2 for actions (chosen, rejected), advantages (c_0, c_1), grad_scale 1,
+ *   no old_logprob and no reference.
+ * An observation with w_b == 0 is SKIPPED: none of its chunks, predictions or scales is read, and +0 is stored (set, never multiplied
+ *   through) to its rows of logprob, ref_logprob, dpred and dlog_scale and to h, margin, loss and coef: a padding pair full of NaN cannot leak.
+ * The stated total is  (1 / B) sum_b w_b loss_b  +  nll_coef (1 / (B chunk)) sum_{b,c} w_b (-lp_w[b, c]);  the caller passes grad_scale =
+ * loss_scale / B and nll_scale = loss_scale / (B chunk).
+ * Refusals (OVLA_EINVAL, nothing launched): a null pred, ref_pred, chosen, rejected, h, margin, loss or coef; B <= 0; chunk outside
+ * [1, OVLA_DPO_CHUNK_MAX]; adim outside [1, 16]; log_scale without ref_log_scale or the reverse; by value: a scale that is not positive and
+ * finite; per element: s_lo > s_hi or a bound that is not finite; beta negative, infinite or NaN; nll_coef negative or NaN; label_smoothing
+ * outside [0, 0.5) or NaN; loss_type other than 0 or 1; loss_type 1 with beta == 0. */
+#define OVLA_DPO_CHUNK_MAX 64
+typedef struct {
+  const void* pred; const void* ref_pred; const void* log_scale; const void* ref_log_scale;
+  const float* chosen; const float* rejected; const float* weight;
+  float* logprob; float* ref_logprob; float* h; float* margin; float* loss; float* coef;
+  void* dpred; void* dlog_scale;
+  float scale[16], log_norm[16];
+  float s_lo, s_hi, beta, label_smoothing, grad_scale, nll_coef, nll_scale;
+  int32_t loss_type, B, chunk, adim;
+} ovla_laplace_dpo_args;
+int ovla_laplace_dpo(const ovla_laplace_dpo_args* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Value head and generalised advantage estimation (PPO on the L1 head: the Laplace kernels above are the policy's side; these are the
  * critic's).  A value head -- one linear map with adim = 1 on the head's post-layer_norm2 activations -- predicts one number per chunk
  * step; ovla_value_loss pools them into one value per observation and forms the clipped squared-error loss against a return with its

@@ -3078,6 +3078,116 @@ class VLAEngine:
             loss = loss - float(entropy_coef) * extra["entropy"]
         return dict(loss=loss, logprob=lp.mean(), ratio=ratio.mean(), clip_frac=clipped.to(F32).mean(), kl=kl_mean, **extra)
 
+    # -- preference optimisation on the Laplace policy: a chosen and a rejected chunk per observation (ovla.h: ovla_laplace_dpo) -----------------
+    def _preference_inputs(self, who: str, B: int, chosen, rejected, scale, beta, ref_means, ref_log_scales, weights, label_smoothing, loss_type, nll_coef):
+        """Validates and lays out what both preference entry points hand the launch; raises before any launch.
+        -> (learned, dict of ops.laplace_dpo's keyword arguments, weights fp32 [B] or None)."""
+        learned = self._learned(scale, who)
+        cfg = self.cfg
+        C, Ad = cfg.chunk, cfg.action_dim
+        if not learned and ref_log_scales is not None:
+            raise ValueError('ref_log_scales belongs to scale="learned"')
+        if ref_means is None:
+            raise ValueError(f"{who} needs ref_means (reference_action_means): a preference is a log-ratio to a reference policy")
+        if learned and ref_log_scales is None:
+            raise ValueError('scale="learned": ref_means and ref_log_scales come together (reference_action_policy)')
+        if C > ops.DPO_CHUNK_MAX:
+            raise ValueError(f"{who}: chunk = {C} (at most {ops.DPO_CHUNK_MAX} steps per observation)")
+        if loss_type not in ops.DPO_LOSS_TYPES:
+            raise ValueError(f"loss_type = {loss_type!r} (one of {sorted(ops.DPO_LOSS_TYPES)})")
+        if not (beta >= 0.0 and math.isfinite(beta)) or (loss_type == "ipo" and beta == 0.0):
+            raise ValueError(f"beta = {beta} (finite and not negative; positive for the IPO loss)")
+        if not 0.0 <= label_smoothing < 0.5:
+            raise ValueError(f"label_smoothing = {label_smoothing} (in [0, 0.5))")
+        if not nll_coef >= 0.0:
+            raise ValueError(f"nll_coef = {nll_coef} (must not be negative or NaN)")
+
+        def rows_of(t, dtype, what):
+            t = torch.as_tensor(t).to(self.device, dtype)
+            if tuple(t.shape) not in ((B, C, Ad), (B * C, Ad)):
+                raise ValueError(f"{what}: {tuple(t.shape)} for {B} observations of {C} steps of {Ad} dimensions")
+            return t.reshape(B * C, Ad).contiguous()
+
+        kw = dict(ref_pred=rows_of(ref_means, BF16, "ref_means"), chosen=rows_of(chosen, F32, "chosen"), rejected=rows_of(rejected, F32, "rejected"))
+        if learned:
+            kw.update(ref_log_scale=rows_of(ref_log_scales, BF16, "ref_log_scales"), bounds=self.scale_bounds)
+        else:
+            ops.laplace_scales(scale, Ad)
+            kw.update(scale=scale)
+        w = None
+        if weights is not None:
+            w = torch.as_tensor(weights).to(self.device, F32)
+            if w.numel() != B:
+                raise ValueError(f"weights: {tuple(w.shape)} for {B} observations")
+            w = w.reshape(B).contiguous()
+        kw.update(weight=w, beta=float(beta), label_smoothing=float(label_smoothing), loss_type=loss_type, nll_coef=float(nll_coef))
+        return learned, kw, w
+
+    def _preference_stats(self, r: dict, w, beta: float, B: int) -> Dict[str, torch.Tensor]:
+        """The launch's per-observation outputs -> device scalars, weighted means over the observations with w > 0 (a skipped observation's
+        outputs are +0 and its weight is 0), and coef fp32 [B].  Nothing is read back."""
+        C = self.cfg.chunk
+        w = torch.ones(B, dtype=F32, device=self.device) if w is None else w
+        mean = lambda t: (w * t).sum() / w.sum()   # noqa: E731
+        lp = r["logprob"].view(B, C, 2).mean(1)
+        return dict(loss=mean(r["loss"]), margin=mean(r["margin"]), reward_chosen=float(beta) * mean(r["h"][:, 0]), reward_rejected=float(beta) * mean(r["h"][:, 1]),
+                    accuracy=mean((r["margin"] > 0).to(F32)), logprob_chosen=mean(lp[:, 0]), logprob_rejected=mean(lp[:, 1]), coef=r["coef"])
+
+    def train_step_action_dpo(self, batch: dict, chosen, rejected, scale, *, beta: float, ref_means, ref_log_scales=None, weights=None, label_smoothing: float = 0.0,
+                              loss_type: str = "sigmoid", nll_coef: float = 0.0, loss_scale: float = 1.0, action_head=None, proprio_projector=None):
+        """One direct-preference-optimisation micro-step under the Laplace policy of the L1 head, from ONE forward and ONE backward:
+            loss = (1 / B) sum_b w_b l(beta m_b)  +  nll_coef (1 / (B chunk)) sum_{b, c} w_b (-logprob of the chosen chunk's step c)
+        with m_b the margin between the chosen and the rejected chunk's log-ratio to the reference policy, summed over the chunk's steps, and
+        l(z) = (1 - eps) softplus(-z) + eps softplus(z) (loss_type "sigmoid", eps = label_smoothing) or (m - 1 / (2 beta))^2 ("ipo").  The body is
+        train_step_action_pg_group's with one ovla_laplace_dpo launch in place of ovla_laplace_pg(_rows): the training forward on the action
+        rows, the head (and the scale head under scale="learned"), that launch -- it reduces the margin, turns it into the pair's implied
+        advantages and forms the gradient with respect to the prediction (and the log-scale) -- the scale head's backward when learned, the
+        head's and the decoder's backward into the flat gradient buffers.  `chosen`, `rejected` [B, chunk, action_dim]: RAW chunks in normalised
+        units; `ref_means` [B, chunk, action_dim] (reference_action_means; computed once per dataset if the caller likes), with `ref_log_scales`
+        under scale="learned" (reference_action_policy); `weights` [B] >= 0, an observation of weight 0 is skipped and may hold anything; host
+        or device tensors.
+        -> dict of device scalars, weighted means over the observations with w > 0: loss (the preference term), margin, reward_chosen
+        (beta times the chosen chunk's log-ratio), reward_rejected, accuracy (the share with m > 0), logprob_chosen, logprob_rejected (per chunk
+        step); and coef fp32 [B], the implied advantage of each pair as the launch applied it.  Nothing is read back."""
+        self._not_in_ema_scope("train_step_action_dpo")
+        self._refuse_per_policy_film_training(True)
+        head = self._l1_head("train_step_action_dpo", action_head)
+        B, C = batch["input_ids"].shape[0], self.cfg.chunk
+        learned, kw, w = self._preference_inputs("train_step_action_dpo", B, chosen, rejected, scale, beta, ref_means, ref_log_scales, weights, label_smoothing,
+                                                 loss_type, nll_coef)
+        kw.update(grad_scale=loss_scale / B, nll_scale=loss_scale / (B * C))
+        if learned:
+            out, idx, pred, hsaved, h2, ls = self._action_means(batch, True, head, proprio_projector, learned=True)
+            r = ops.laplace_dpo(pred, chunk=C, log_scale=ls, **kw)
+            self._scale_bwd(h2, r["dlog_scale"])
+        else:
+            out, idx, pred, hsaved = self._action_means(batch, True, head, proprio_projector)
+            r = ops.laplace_dpo(pred, chunk=C, **kw)
+        dah = head.bwd(hsaved, dpred=r["dpred"])
+        if getattr(self, "_overlap", False) and hasattr(head, "store"):
+            for dt, g in head.store.flat_grad.items():
+                self.reducer.notify(head.store, dt, g.numel())
+        self.backward_from_rows(dah, idx, out)
+        return self._preference_stats(r, w, beta, B)
+
+    def action_preference(self, batch: dict, chosen, rejected, scale, *, beta: float, ref_means, ref_log_scales=None, weights=None, label_smoothing: float = 0.0,
+                          loss_type: str = "sigmoid", action_head=None):
+        """train_step_action_dpo's launch without gradients, on the inference forward: margin and accuracy of held-out pairs under the current
+        weights.  Same arguments, same statistics (and coef at grad_scale 1 / B); nothing is written but the outputs, nothing is read back."""
+        head = self._l1_head("action_preference", action_head)
+        B, C = batch["input_ids"].shape[0], self.cfg.chunk
+        learned, kw, w = self._preference_inputs("action_preference", B, chosen, rejected, scale, beta, ref_means, ref_log_scales, weights, label_smoothing,
+                                                 loss_type, 0.0)
+        kw.update(grad_scale=1.0 / B, want_dpred=False, want_dlog_scale=False)
+        with torch.no_grad():
+            if learned:
+                _, _, pred, _, _, ls = self._action_means(batch, False, head, learned=True)
+                r = ops.laplace_dpo(pred, chunk=C, log_scale=ls, **kw)
+            else:
+                _, _, pred, _ = self._action_means(batch, False, head)
+                r = ops.laplace_dpo(pred, chunk=C, **kw)
+        return self._preference_stats(r, w, beta, B)
+
     # -- the next-token cross entropy on the counted rows: train_step_discrete above and modeling._LMLossFn (`output.loss`) ------------------
     def counted_rows(self, labels, S: int, P: int):
         """Host int64 labels [B, L] -> (bb, jj, rows_idx int32 [n_tok] device, targets int64 [n_tok] device).  Text position j + 1 with

@@ -1306,6 +1306,62 @@ def laplace_pg_rows(pred, log_scale, bounds, actions, advantage, *, old_logprob=
     return logprob, ratio, clipped, kl, entropy, dpred, dlog_scale
 
 
+DPO_CHUNK_MAX = 64         # ovla.h: OVLA_DPO_CHUNK_MAX
+DPO_LOSS_TYPES = {"sigmoid": 0, "ipo": 1}
+
+
+def laplace_dpo(pred, ref_pred, chosen, rejected, chunk, scale=None, *, log_scale=None, ref_log_scale=None, bounds=LAPLACE_SCALE_BOUNDS, weight=None, beta,
+                label_smoothing=0.0, loss_type="sigmoid", grad_scale=None, nll_coef=0.0, nll_scale=0.0, dpred=None, dlog_scale=None, want_dpred=True,
+                want_dlog_scale=None, want_logprob=True, logprob=None, ref_logprob=None, h=None, margin=None, loss=None, coef=None):
+    """The preference loss of a chosen and a rejected chunk per observation under the Laplace policy, and its gradient, in one launch (ovla.h
+    "Preference optimisation on the Laplace policy": ovla_laplace_dpo): pred, ref_pred bf16 [B * chunk, adim], chosen, rejected fp32
+    [B * chunk, adim], weight fp32 [B] (optional); the scale either `scale` (a scalar or [adim], shared by both policies) or log_scale with
+    ref_log_scale bf16 [B * chunk, adim] and `bounds`; loss_type "sigmoid" / "ipo" (or 0 / 1)
+    -> dict(logprob, ref_logprob fp32 [B * chunk, 2] (chosen, rejected), h fp32 [B, 2], margin, loss, coef fp32 [B], dpred, dlog_scale bf16
+    [B * chunk, adim] or None).  With grad_scale the gradients go to `dpred` / `dlog_scale` (new tensors without them; dlog_scale by default
+    only under a per-element scale; want_dpred=False / want_dlog_scale=False leaves that one out of the launch)."""
+    _chk(pred, name="pred")
+    chunk = int(chunk)
+    assert pred.dim() == 2 and pred.is_contiguous() and chunk > 0 and pred.shape[0] % chunk == 0, f"pred: {tuple(pred.shape)} is not whole observations of {chunk} steps"
+    (rows, adim), dev = pred.shape, pred.device
+    B = rows // chunk
+    rows_form = log_scale is not None or ref_log_scale is not None
+    assert rows_form != (scale is not None), "the scale is either `scale` or log_scale with ref_log_scale"
+    f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)   # noqa: E731
+    if want_logprob:
+        logprob = f32(rows, 2) if logprob is None else logprob
+        ref_logprob = f32(rows, 2) if ref_logprob is None else ref_logprob
+    h, margin = f32(B, 2) if h is None else h, f32(B) if margin is None else margin
+    loss, coef = f32(B) if loss is None else loss, f32(B) if coef is None else coef
+    if want_dlog_scale is None:
+        want_dlog_scale = rows_form
+    if grad_scale is not None and dpred is None and want_dpred:
+        dpred = torch.empty((rows, adim), dtype=BF16, device=dev)
+    if grad_scale is not None and dlog_scale is None and want_dlog_scale:
+        dlog_scale = torch.empty((rows, adim), dtype=BF16, device=dev)
+    for t, dt, name, n in ((ref_pred, BF16, "ref_pred", rows * adim), (log_scale, BF16, "log_scale", rows * adim), (ref_log_scale, BF16, "ref_log_scale", rows * adim),
+                           (chosen, torch.float32, "chosen", rows * adim), (rejected, torch.float32, "rejected", rows * adim), (weight, torch.float32, "weight", B),
+                           (logprob, torch.float32, "logprob", rows * 2), (ref_logprob, torch.float32, "ref_logprob", rows * 2), (h, torch.float32, "h", B * 2),
+                           (margin, torch.float32, "margin", B), (loss, torch.float32, "loss", B), (coef, torch.float32, "coef", B),
+                           (dpred, BF16, "dpred", rows * adim), (dlog_scale, BF16, "dlog_scale", rows * adim)):
+        if t is not None:
+            _chk(t, dt, name)
+            assert t.numel() == n and t.is_contiguous(), f"{name}: expected {n} contiguous elements"
+    g = STRUCTS["ovla_laplace_dpo_args"]()
+    g.pred, g.ref_pred, g.log_scale, g.ref_log_scale = pred.data_ptr(), _p(ref_pred), _p(log_scale), _p(ref_log_scale)
+    g.chosen, g.rejected, g.weight = _p(chosen), _p(rejected), _p(weight)
+    g.logprob, g.ref_logprob, g.h, g.margin, g.loss, g.coef = _p(logprob), _p(ref_logprob), h.data_ptr(), margin.data_ptr(), loss.data_ptr(), coef.data_ptr()
+    g.dpred, g.dlog_scale = _p(dpred), _p(dlog_scale)
+    g.s_lo, g.s_hi, g.beta, g.label_smoothing = float(bounds[0]), float(bounds[1]), float(beta), float(label_smoothing)
+    g.grad_scale, g.nll_coef, g.nll_scale = float(grad_scale or 0.0), float(nll_coef), float(nll_scale)
+    g.loss_type = DPO_LOSS_TYPES[loss_type] if isinstance(loss_type, str) else int(loss_type)
+    g.B, g.chunk, g.adim = B, chunk, adim
+    if not rows_form and 1 <= adim <= LAPLACE_MAX_ADIM:            # (otherwise the kernel's own refusal speaks)
+        _set_laplace_scales(g, scale, adim)
+    _lib.call("ovla_laplace_dpo", g, _stream())
+    return dict(logprob=logprob, ref_logprob=ref_logprob, h=h, margin=margin, loss=loss, coef=coef, dpred=dpred, dlog_scale=dlog_scale)
+
+
 def _chk_n(t, dtype, name, n):
     if t is not None:
         _chk(t, dtype, name)

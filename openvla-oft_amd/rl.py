@@ -18,6 +18,16 @@ caller-owned rollout buffer [N trajectories, T steps] on the device (ovla_gae, o
 buffer and the training step), and one minibatch of that buffer through train_step_action_pg_group at G = 1 with the clipped value loss
 beside the clipped surrogate.  The critic's gradient stops at the head's hidden output: it fits the value on the policy's features and does
 not shape them.  The rollout buffer, the environments, minibatching and the optimizer loop stay the caller's.
+
+Everything above needs a scalar reward for every drawn chunk.  preference_pairs, dpo_step_continuous and online_dpo_step_continuous train on
+COMPARISONS instead (direct preference optimisation on the same Laplace policy): per observation a chosen and a rejected chunk -- this rollout
+succeeded and that one failed, an operator preferred A over B, the demonstration beats the policy's own draw -- and a reference policy.  The
+loss is a function of the margin between the two chunks' summed log-ratios to the reference, and VLAEngine.train_step_action_dpo takes it
+from ONE training forward and one backward (ovla_laplace_dpo).  dpo_step_continuous runs that step on given pairs, fetching the reference's
+means (and log-scales under scale="learned") when the caller has not computed them once per dataset; online_dpo_step_continuous draws G
+chunks per observation, scores them with a reward function and lets preference_pairs pick the best and the worst as the pair;
+VLAEngine.action_preference reports margin and accuracy of held-out pairs.  `nll_coef` adds the chosen chunk's negative log-likelihood, the
+usual regulariser that keeps the chosen chunk's probability from falling with the rejected one's.
 """
 from __future__ import annotations
 
@@ -185,3 +195,68 @@ def ppo_step_continuous(engine, batch: dict, actions, old_logprobs, advantages, 
                                                   clip=clip, loss_scale=loss_scale, returns=returns, old_values=old_values, value_coef=value_coef,
                                                   value_clip=value_clip, **extra)
     return dict(stats)
+
+
+def preference_pairs(actions, rewards, min_gap: float = 0.0):
+    """The pair of a group: actions [B, G, chunk, action_dim], rewards [B, G] -> (chosen, rejected [B, chunk, action_dim], weight fp32 [B]) where
+    `actions` lives, nothing read back.  chosen is the draw of the highest reward, rejected that of the lowest, the lowest index winning a tie;
+    weight is 0 where max - min <= min_gap (a group that does not tell its draws apart: train_step_action_dpo skips it), else 1."""
+    act = torch.as_tensor(actions)
+    r = torch.as_tensor(rewards).to(act.device, torch.float32)
+    if act.dim() != 4 or tuple(r.shape) != tuple(act.shape[:2]):
+        raise ValueError(f"actions {tuple(act.shape)} ([B, G, chunk, action_dim]) with rewards {tuple(r.shape)} ([B, G])")
+    B, G = r.shape
+    order = torch.arange(G, device=r.device).expand(B, G)
+    hi, lo = r.max(dim=1, keepdim=True).values, r.min(dim=1, keepdim=True).values
+    first = lambda hit: torch.where(hit, order, G).min(dim=1).values   # noqa: E731  (the lowest index among the hits; every row has one)
+    i_hi, i_lo = first(r == hi), first(r == lo)
+    rows = torch.arange(B, device=r.device)
+    weight = ((hi - lo).reshape(B) > float(min_gap)).to(torch.float32)
+    return act[rows, i_hi], act[rows, i_lo], weight
+
+
+def dpo_step_continuous(engine, batch: dict, chosen, rejected, *, scale, beta: float, ref_means=None, ref_log_scales=None, weights=None, label_smoothing: float = 0.0,
+                        loss_type: str = "sigmoid", nll_coef: float = 0.0, inner_steps: int = 1, loss_scale: float = 1.0) -> Dict[str, torch.Tensor]:
+    """One DPO iteration on one batch of an L1-head engine: `chosen`, `rejected` [B, chunk, action_dim] the RAW chunks of each observation's
+    pair, `weights` [B] (0 skips a pair).  Without `ref_means` the reference policy's means (and log-scales under scale="learned") are fetched
+    from the engine's reference snapshot (set_reference_policy: one inference forward); a caller that trains several epochs on a fixed dataset
+    computes them once and passes them.  ValueError with neither: DPO has no meaning without a reference.  Then `inner_steps` micro-steps of
+    train_step_action_dpo; gradients accumulate in the engine's flat buffers, nothing is read back.  -> the last micro-step's statistics."""
+    learned = isinstance(scale, str)
+    if ref_means is None:
+        if not engine.has_reference_policy:
+            raise ValueError("dpo_step_continuous needs a reference: engine.set_reference_policy() or ref_means")
+        if learned:
+            pol = engine.reference_action_policy(batch)
+            ref_means, ref_log_scales = pol["mean"], pol["log_scale"]
+        else:
+            ref_means = engine.reference_action_means(batch)
+    stats = None
+    for _ in range(int(inner_steps)):
+        stats = engine.train_step_action_dpo(batch, chosen, rejected, scale, beta=beta, ref_means=ref_means, ref_log_scales=ref_log_scales, weights=weights,
+                                             label_smoothing=label_smoothing, loss_type=loss_type, nll_coef=nll_coef, loss_scale=loss_scale)
+    return dict(stats)
+
+
+def online_dpo_step_continuous(engine, batch: dict, reward_fn: Callable, *, group_size: int, scale, beta: float, clamp=(-1.0, 1.0), min_gap: float = 0.0,
+                               ref_means=None, ref_log_scales=None, label_smoothing: float = 0.0, loss_type: str = "sigmoid", nll_coef: float = 0.0,
+                               inner_steps: int = 1, loss_scale: float = 1.0) -> Dict[str, torch.Tensor]:
+    """One online DPO iteration: draw `group_size` chunks per observation from the Laplace policy (sample_actions_laplace, one forward),
+    reward_fn(batch, actions [B, G, chunk, action_dim]) -> rewards [B, G] on the draws CLAMPED to `clamp` (what a robot would execute; None: the
+    raw draws), the best and the worst draw of each group as its pair (preference_pairs; a group whose rewards lie within `min_gap` is
+    skipped), then dpo_step_continuous on the RAW draws.  -> its statistics plus `reward` (the mean) and `weights` [B], all on the device."""
+    if int(group_size) < 2:
+        raise ValueError(f"group_size = {group_size}: a pair needs two draws")
+    if ref_means is None and not engine.has_reference_policy:
+        raise ValueError("online_dpo_step_continuous needs a reference: engine.set_reference_policy() or ref_means")
+    draw = engine.sample_actions_laplace(batch, scale, num_samples=group_size)
+    B, G = draw["actions"].shape[:2]
+    executed = draw["actions"] if clamp is None else draw["actions"].clamp(float(clamp[0]), float(clamp[1]))
+    rewards = torch.as_tensor(reward_fn(batch, executed)).to(engine.device, torch.float32)
+    if tuple(rewards.shape) != (B, G):
+        raise ValueError(f"reward_fn returned {tuple(rewards.shape)}, expected {(B, G)}")
+    chosen, rejected, weight = preference_pairs(draw["actions"], rewards, min_gap)
+    stats = dpo_step_continuous(engine, batch, chosen, rejected, scale=scale, beta=beta, ref_means=ref_means, ref_log_scales=ref_log_scales, weights=weight,
+                                label_smoothing=label_smoothing, loss_type=loss_type, nll_coef=nll_coef, inner_steps=inner_steps, loss_scale=loss_scale)
+    stats.update(reward=rewards.mean(), weights=weight)
+    return stats
